@@ -284,6 +284,41 @@ CONFIGS = {     # BASELINE.json configs: frames, height, width, windows, channel
     "window": (12, 5424, 5424, 1, 1),   # one window per step (sub-report; --frames)
 }
 CHANNEL_OFFSETS = (0.0, -2.0, -4.0)
+DUMP_BYTES = 48 << 20                   # --dump-outputs: float64 label samples of all windows of all ranks together
+DUMP_SEED = 20240601
+
+
+def dump_positions(bounds, H, W, world):
+    """--dump-outputs: per window the flat voxel positions whose labels are written -- None (the whole window) where the window
+    fits its share of DUMP_BYTES, else a fixed, seeded, sorted sample; depends only on the window shapes"""
+    import numpy as np
+    cap = DUMP_BYTES // 8 // (len(bounds) * world)
+    pos = []
+    for k, (lo, hi) in enumerate(bounds):
+        n = (hi - lo) * H * W
+        pos.append(None if n <= cap else np.unique(np.random.default_rng(DUMP_SEED + k).integers(0, n, cap)))
+    return pos
+
+
+def dump_outputs(out_dir, got, samples, rank, world):
+    """write what the last timed step delivered as out_dir/labels_wKK.npy (float64; rankR_ in front under --gpus N > 1):
+    `got` the stitched label windows, or in hand-out mode {"windows": the window-local labels at the dumped positions,
+    "luts": local id -> consistent id}, mapped here to the consistent ids a stitched window holds"""
+    import numpy as np
+    from tobac_flow_amd.parallel import apply_global_lut
+    if isinstance(got, dict):
+        wins = [apply_global_lut(s, lut) for s, lut in zip(got["windows"], got["luts"])]
+    else:
+        wins = [samples(k, w) for k, w in enumerate(got)]
+    os.makedirs(out_dir, exist_ok=True)
+    files, total = [], 0
+    for k, w in enumerate(wins):
+        name = ("rank%d_" % rank if world > 1 else "") + "labels_w%02d.npy" % k
+        arr = w.cpu().numpy().astype(np.float64)
+        np.save(os.path.join(out_dir, name), arr)
+        files.append(name)
+        total += arr.nbytes
+    return {"dir": out_dir, "files": files, "bytes": total}
 
 
 def main():
@@ -345,7 +380,13 @@ def main():
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="diagnostic: do not record HIP events around the library's launches in the timed region "
                          "(roofline = null); the difference to a default run is what the instrumentation costs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the label ids the last timed step delivered for the last channel, one "
+                         "DIR/labels_wKK.npy (float64) per window: the whole window, or a fixed, seeded sample of its voxels where all "
+                         "windows together would exceed 48 MB; the same arguments give the same inputs, so two builds compare file for file")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))
 
@@ -402,6 +443,18 @@ def main():
     inflight = {}
     timeline = os.environ.get("TF_BENCH_TIMELINE") is not None      # development aid: when each part of a step starts and ends
     info = {"floods": ws_stats, "reference_order": ref_order}
+    # --dump-outputs: the sampled positions live on the device before the timed region (a gather per window, after it --
+    # or in hand-out mode as each window of the last channel is handed out)
+    dump_pos = None
+    if a.dump_outputs:
+        dump_pos = [None if p is None else torch.from_numpy(p).to(bt_all.device) for p in dump_positions(bounds, H, W, world)]
+
+    def dump_sample(k, lab):
+        flat = lab.reshape(-1)
+        lo, hi = bounds[k]
+        if flat.numel() != (hi - lo) * H * W:                # (the positions were drawn for this shape: checked before the gather)
+            raise RuntimeError(f"--dump-outputs: window {k} holds {tuple(lab.shape)}, expected {(hi - lo, H, W)}")
+        return flat.clone() if dump_pos[k] is None else flat[dump_pos[k].to(flat.device)]
 
     def mark(what, ms):
         print("  t+%7.1f ms  %s" % (ms, what), file=sys.stderr, flush=True)
@@ -439,7 +492,8 @@ def main():
                                       max_in_flight=a.inflight, stream_windows=a.stream_windows,
                                       flow_workspace_gb=float(os.environ["TF_BENCH_FLOW_GB"]) if "TF_BENCH_FLOW_GB" in os.environ else None,
                                       info=info, mark=mark if timeline else None,
-                                      on_window=(lambda c, k, lab: None) if hand_out else None)
+                                      on_window=(lambda c, k, lab: dump_sample(k, lab) if (dump_pos and c == C - 1) else None)
+                                      if hand_out else None)
         inflight["n"] = info.get("floods_in_flight", 1)
         inflight["flow_workspace_gb"] = info.get("flow_workspace_gb")
         inflight["channels_begun_during_the_flow"] = info.get("channels_begun_during_the_flow")
@@ -451,7 +505,7 @@ def main():
                     dist.all_reduce(tn, op=dist.ReduceOp.MAX)
                     n_obj = int(tn.item())
                 objects.append(n_obj)
-            return None, objects
+            return (res[-1] if dump_pos else None), objects
         return keep[0], objects
 
     def barrier():
@@ -531,6 +585,7 @@ def main():
     retries_timed = torch.cuda.memory_stats().get("num_alloc_retries", 0) - retries_t0
     prof = _lib.profile_collect()
     _lib.profile_enable(False)
+    dumped = dump_outputs(a.dump_outputs, out_labels, dump_sample, rank, world) if a.dump_outputs else None
     del out_labels
     n_timed = len(ws_stats)
     alone_ms = None
@@ -696,6 +751,8 @@ def main():
                "peak_device_memory_GB": round(torch.cuda.max_memory_allocated() / 1e9, 1),
                "allocator_retries_in_the_timed_region": int(retries_timed),      # (> 0: the device ran out and the caching allocator flushed its cache -- seconds)
                "roofline": roof}
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         # which watershed schedule the timed windows ran: stats[5] = 1 / 0 probe (speculative root phase + conflict test,
         # conflict found / not found), -1 = root phase skipped on the conflict memo of watershed.py (identical labels)
         timed = np.array(ws_stats[n_warm:n_timed], np.int64)

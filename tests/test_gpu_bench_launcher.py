@@ -96,3 +96,27 @@ def test_bench_pipeline_equals_the_plain_calls():
     plain = _bench("--frames", "44", "--n-windows", "4", "--no-stream-windows")
     assert streamed["watershed"]["windows_begun_during_the_flow"] and not plain["watershed"]["windows_begun_during_the_flow"]
     assert streamed["config"]["objects_after_stitch"] == plain["config"]["objects_after_stitch"] == want > 10
+
+
+def test_bench_dump_outputs_writes_the_last_steps_labels(tmp_path):
+    """--dump-outputs DIR: the label ids the last timed step delivered, one float64 file per window.  Under --rotate 1 every
+    step floods the same stack, so one plain step and two pipelined steps (detect_stack_sequence) write the same files; with
+    three channels, the windows handed out with window-local ids and mapped by their tables write what the stitched windows do."""
+    import numpy as np
+    one = _bench("--frames", "44", "--n-windows", "4", "--dump-outputs", str(tmp_path / "one"))
+    two = _bench("--frames", "44", "--n-windows", "4", "--steps", "2", "--dump-outputs", str(tmp_path / "two"))
+    assert not one["steps_pipelined"]["on"] and two["steps_pipelined"]["on"] and two["steps"] == 2 and len(two["step_ms"]) == 2
+    files = ["labels_w%02d.npy" % k for k in range(4)]
+    assert one["outputs_dumped"]["files"] == two["outputs_dumped"]["files"] == files
+    assert 0 < one["outputs_dumped"]["bytes"] <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "one" / f), np.load(tmp_path / "two" / f)
+        assert a.dtype == np.float64 and (a > 0).any() and np.array_equal(a, b), f
+    f3 = ("--config", "F3", "--frames", "14", "--n-windows", "2", "--height", "1500", "--width", "2500")
+    handed = _bench(*f3, "--dump-outputs", str(tmp_path / "handed"))
+    kept = _bench(*f3, "--no-hand-out", "--dump-outputs", str(tmp_path / "kept"))
+    assert "handed out" in handed["config"]["delivery"] and "resident" in kept["config"]["delivery"]
+    assert handed["outputs_dumped"]["files"] == kept["outputs_dumped"]["files"] == files[:2]
+    for f in files[:2]:
+        a, b = np.load(tmp_path / "handed" / f), np.load(tmp_path / "kept" / f)
+        assert (a > 0).any() and np.array_equal(a, b), f

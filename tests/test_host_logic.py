@@ -49,11 +49,21 @@ def test_a_starved_chain_report_becomes_an_exception(monkeypatch):
         model.check_launches("create_flow")
     with pytest.raises(RuntimeError):
         model.check_launches()
-    # status slots (round 6): without a device there is no pinned ring -- acquire hands out 0 (= share the device's word), the
-    # checks report nothing, a slot number outside the ring is an argument error
-    assert L.tf_farneback_status_acquire() == 0 and L.tf_farneback_status_check(0) == 0 and L.tf_farneback_status_check(7) == 0
+    # status slots (round 6): without a device there is no pinned ring -- acquire hands out 0 (= share the device's word); with
+    # one (the whole suite run on a GPU machine) every acquire hands out a slot of its own, never the shared word.  Either way
+    # the checks report nothing and a slot number outside the ring is an argument error.  (Whether there is a device is asked
+    # of the library's own runtime, which the ring lives in.)
+    slot = L.tf_farneback_status_acquire()
+    if L.tf_device_count() > 0:
+        other = L.tf_farneback_status_acquire()
+        assert 0 < slot < 256 and 0 < other < 256 and other != slot
+        assert L.tf_farneback_status_check(slot) == 0 and L.tf_farneback_status_check(other) == 0
+        L.tf_farneback_status_release(other)
+    else:
+        assert slot == 0
+    assert L.tf_farneback_status_check(0) == 0 and L.tf_farneback_status_check(7) == 0
     assert L.tf_farneback_status_check(4096) == -1
-    L.tf_farneback_status_release(0)
+    L.tf_farneback_status_release(slot)
     L.tf_farneback_status_release(4096)
     assert model.params.status_slot == 0
 
@@ -937,3 +947,37 @@ def test_select_peaks_grid_form_equals_the_all_pairs_form():
             for num in (np.inf, 7):
                 a, b = select_peaks(coords, vals, d, num), _select_peaks_all_pairs(coords, vals, d, num)
                 assert a.shape == b.shape and np.array_equal(a, b), (ndim, n, d, num)
+
+
+def test_bench_dump_outputs_samples_fixed_positions_and_maps_handed_out_windows():
+    """bench.py --dump-outputs (host part): the sampled positions depend only on the window shapes, stay inside each window,
+    keep all windows of all ranks under 64 MB of float64, and a small window is written whole; the hand-out form (window-local
+    ids at the sampled positions + the local -> consistent tables) writes the same files as the stitched windows."""
+    import sys
+    import tempfile
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from tobac_flow_amd.parallel import apply_global_lut
+    bounds = [(0, 16), (12, 28), (24, 40)]
+    H, W = 1500, 2500
+    for world in (1, 2):
+        pos = bench.dump_positions(bounds, H, W, world)
+        again = bench.dump_positions(bounds, H, W, world)
+        assert all(p is not None and np.array_equal(p, q) for p, q in zip(pos, again))
+        assert all(p.min() >= 0 and p.max() < (hi - lo) * H * W and np.all(np.diff(p) > 0) for p, (lo, hi) in zip(pos, bounds))
+        assert 8 * world * sum(p.size for p in pos) <= 64 << 20
+    assert bench.dump_positions([(0, 4)], 10, 12, 1) == [None]
+    rng = np.random.default_rng(3)
+    local = [torch.from_numpy(rng.integers(-1, 6, (4, 10, 12)).astype(np.int32)) for _ in range(2)]
+    luts = [np.array([0, 3, 4, 5, 6, 7]), np.array([0, 1, 2, 8, 9, 10])]
+    stitched = [apply_global_lut(l, lut) for l, lut in zip(local, luts)]
+    sample = lambda k, lab: lab.reshape(-1).clone()
+    with tempfile.TemporaryDirectory() as d1, tempfile.TemporaryDirectory() as d2:
+        a = bench.dump_outputs(d1, stitched, sample, 0, 1)
+        b = bench.dump_outputs(d2, {"windows": [sample(k, l) for k, l in enumerate(local)], "luts": luts}, sample, 0, 1)
+        assert a["files"] == b["files"] == ["labels_w00.npy", "labels_w01.npy"] and a["bytes"] == 2 * 8 * 4 * 10 * 12
+        for f in a["files"]:
+            x, y = np.load(os.path.join(d1, f)), np.load(os.path.join(d2, f))
+            assert x.dtype == np.float64 and np.array_equal(x, y)
+        assert np.array_equal(np.load(os.path.join(d1, "labels_w00.npy")), stitched[0].numpy().ravel())

@@ -1,6 +1,7 @@
 """The oracle pinned against the reference's own outputs (tests/golden/watershed_ref.npz was produced
-by the reference itself: tests/golden/make_watershed_golden.py) and, when oracle/_ref is built (i.e.
-when /root/reference is present), live against the reference's compiled Cython kernel."""
+by the reference itself: tests/golden/make_watershed_golden.py; tests/golden/watershed_ref_kernel.npz by its
+compiled Cython kernel: tests/golden/make_watershed_kernel_golden.py) and, when oracle/_ref is built (i.e.
+when the reference's sources were present at build time), live against that kernel."""
 import numpy as np
 import pytest
 
@@ -20,13 +21,21 @@ def test_c_twin_matches_reference_golden(golden_ws, name):
 
 @pytest.mark.parametrize("name", CASES)
 def test_c_twin_matches_live_reference_kernel(golden_ws, name):
-    if not ref_loader.available():
-        pytest.skip("oracle/_ref not built (reference absent on this machine)")
+    """The C twin against the reference's compiled flood kernel, fed the same raveled arguments, on the case and on its field
+    rounded to steps of 1/8 (plateaus ordered by the heap's internal order): against the kernel's labels stored in
+    tests/golden/watershed_ref_kernel.npz (tests/golden/make_watershed_kernel_golden.py) and, where oracle/_ref is built,
+    against the kernel itself."""
+    import os
+    kernel = np.load(os.path.join(os.path.dirname(__file__), "golden", "watershed_ref_kernel.npz"))
     c = golden_ws[name]
     conn = int(c["conn"])
-    a = ws_oracle.watershed(c["fwd"], c["bwd"], c["field"], c["markers"], c.get("mask"), conn)
-    b = ws_oracle.watershed(c["fwd"], c["bwd"], c["field"], c["markers"], c.get("mask"), conn, use_ref=True)
-    assert np.array_equal(a, b)
+    quantised = (np.round(c["field"] * 8) / 8).astype(np.float32)      # (as the fixture's generator rounds it)
+    for key, field in (("labels", c["field"]), ("labels_q8", quantised)):
+        args = (c["fwd"], c["bwd"], field, c["markers"], c.get("mask"), conn)
+        a = ws_oracle.watershed(*args)
+        assert np.array_equal(a, kernel[name + "/" + key]), key
+        if ref_loader.available():
+            assert np.array_equal(a, ws_oracle.watershed(*args, use_ref=True)), key
 
 
 def test_idealised_order_characterisation(golden_ws):
