@@ -1791,17 +1791,43 @@ static size_t fb_hand_floats(int64_t h, int64_t w) {
     const int64_t nx = (w + FBI_OW - 1) / FBI_OW;
     return FBI_HDR / 4 + 2 * (size_t)(2 * (nx - 1) * h * FBI_HW);
 }
-static size_t fb_pair_floats(int64_t H, int64_t W, bool fused) {
-    // per pair: tmp (n + 2H + 64), blur, I, R[2] (5n each), 2 flow scratch (2n each); the 5-plane matrix M (5n) only for the
-    // unfused fallback (window sizes other than 13): the fused iteration never stores it
+// level k's image size and the largest plane / row-blur scratch among the levels k_lo .. k_hi
+static void fb_level_size(int H, int W, const tf_farneback_params *p, int k, int *h, int *w) {
+    double scale = 1; for (int i = 0; i < k; i++) scale *= p->pyr_scale;
+    *w = (int)lrint(W * scale); *h = (int)lrint(H * scale);
+}
+static void fb_phase_sizes(int H, int W, const tf_farneback_params *p, int k_hi, int k_lo, size_t *tmp_floats, size_t *plane) {
+    size_t t = 0, pl = 0;
+    for (int k = k_lo; k <= k_hi; k++) {
+        int h, w; fb_level_size(H, W, p, k, &h, &w);
+        pl = std::max(pl, (size_t)h * w);
+        // the two-pass blur of a full-size level keeps a whole image (+ rows), the sampled blur H rows of w float2
+        t = std::max(t, k == 0 ? (size_t)H * W + 2 * (size_t)H + 64 : std::max((size_t)H * W / 4 + 2 * (size_t)H + 64, 2 * (size_t)H * w + 64));
+        t = std::max(t, fb_hand_floats(h, w));
+    }
+    if (k_lo == 0) t = std::max(t, std::max((size_t)H * W + 2 * (size_t)H + 64, fb_hand_floats(H, W)));
+    *tmp_floats = t; *plane = pl;
+}
+// floats of blur scratch per pair for all levels: the full-size blur (n + 2H + 64), the hand-over words and the sampled blur's
+// H rows of w float2 -- 2 H w floats, more than n from a pyramid scale above 0.5 on (1.2 n at level 1 of scale 0.6: sized
+// by n + 2H + 64, one pair's rows ran into the next pair's scratch)
+static size_t fb_full_tmp_floats(int64_t H, int64_t W, const tf_farneback_params *p) {
+    size_t t = 0, pl = 0;
+    fb_phase_sizes((int)H, (int)W, p, fb_levels(H, W, p), 0, &t, &pl);
+    return t;
+}
+static size_t fb_pair_floats(int64_t H, int64_t W, const tf_farneback_params *p) {
+    // per pair: tmp (fb_full_tmp_floats), blur, I, R[2] (5n each), 2 flow scratch (2n each); the 5-plane matrix M (5n) only for
+    // the unfused fallback (window sizes other than 13): the fused iteration never stores it
     const size_t n = (size_t)H * W;
-    return tf_align_up(std::max(n + 2 * (size_t)H + 64, fb_hand_floats(H, W)), 64) + 2 * tf_align_up(n, 64) + (fused ? 10 : 15) * tf_align_up(n, 64) + 2 * tf_align_up(2 * n, 64);
+    const bool fused = p->win_size == FBI_WIN;
+    return tf_align_up(fb_full_tmp_floats(H, W, p), 64) + 2 * tf_align_up(n, 64) + (fused ? 10 : 15) * tf_align_up(n, 64) + 2 * tf_align_up(2 * n, 64);
 }
 
 extern "C" size_t tf_farneback_workspace_bytes_batch(int64_t B, int64_t H, int64_t W, const tf_farneback_params *p)
 {
     if (B <= 0 || H <= 0 || W <= 0 || !p) return 0;
-    return (size_t)B * fb_pair_floats(H, W, p->win_size == FBI_WIN) * sizeof(float) + 8192;
+    return (size_t)B * fb_pair_floats(H, W, p) * sizeof(float) + 8192;
 }
 
 // Pairs per tf_farneback_batch call that fill the GPU best.  The iteration kernel runs one workgroup per (pair, strip,
@@ -1814,7 +1840,7 @@ extern "C" int64_t tf_farneback_batch_hint(int64_t H, int64_t W, const tf_farneb
     int dev = 0, n_cu = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
     const int64_t slots = (int64_t)n_cu * 8 / (FBI_T / 64);                     // two waves per SIMD; one (strip, direction) per workgroup of FBI_T threads
-    const size_t per_pair_bytes = fb_pair_floats(H, W, p->win_size == FBI_WIN) * sizeof(float);
+    const size_t per_pair_bytes = fb_pair_floats(H, W, p) * sizeof(float);
     int64_t cap = max_pairs;
     if (max_bytes > 0 && (int64_t)(max_bytes / per_pair_bytes) < cap) cap = (int64_t)(max_bytes / per_pair_bytes);
     if (cap < 1) cap = 1;
@@ -1968,23 +1994,6 @@ static bool fb_carve(TfArena &ar, int B, size_t tmp_floats, size_t plane, bool f
     S->fbuf[0] = ar.take<float>(S->bs_f * B); S->fbuf[1] = ar.take<float>(S->bs_f * B);
     return ar.ok();
 }
-// level k's image size and the largest plane / row-blur scratch among the levels k_lo .. k_hi
-static void fb_level_size(int H, int W, const tf_farneback_params *p, int k, int *h, int *w) {
-    double scale = 1; for (int i = 0; i < k; i++) scale *= p->pyr_scale;
-    *w = (int)lrint(W * scale); *h = (int)lrint(H * scale);
-}
-static void fb_phase_sizes(int H, int W, const tf_farneback_params *p, int k_hi, int k_lo, size_t *tmp_floats, size_t *plane) {
-    size_t t = 0, pl = 0;
-    for (int k = k_lo; k <= k_hi; k++) {
-        int h, w; fb_level_size(H, W, p, k, &h, &w);
-        pl = std::max(pl, (size_t)h * w);
-        // the two-pass blur of a full-size level keeps a whole image (+ rows), the sampled blur H rows of w float2
-        t = std::max(t, k == 0 ? (size_t)H * W + 2 * (size_t)H + 64 : std::max((size_t)H * W / 4 + 2 * (size_t)H + 64, 2 * (size_t)H * w + 64));
-        t = std::max(t, fb_hand_floats(h, w));
-    }
-    if (k_lo == 0) t = std::max(t, std::max((size_t)H * W + 2 * (size_t)H + 64, fb_hand_floats(H, W)));
-    *tmp_floats = t; *plane = pl;
-}
 
 // pyramid levels k_hi .. k_lo for B pairs (pointers at the first pair of the range); cur / pw / ph carry the state of the
 // levels above over to the next call
@@ -2043,7 +2052,7 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
                     Ik = I;
                 }
             } else {
-                // blur + resize fused on the sampled columns / rows (tmp holds rowf: H * w float2 <= n + 2H floats)
+                // blur + resize fused on the sampled columns / rows (tmp holds rowf: H * w float2, fb_full_tmp_floats)
                 TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 8.0 * (double)H * w * 2 + 4.0 * plane) * B, s);
                 FbResizeGeom rg; rg.sh = H; rg.sw = W; rg.dh = h; rg.dw = w; rg.scale_x = rsx; rg.scale_y = rsy;
                 // LDS-staged form when a workgroup's source segment fits (64 outputs * stride + ksize bytes per row)
@@ -2260,7 +2269,7 @@ extern "C" int tf_farneback_batch_split(const uint8_t *prev, const uint8_t *next
     if (parts == 1) {
         TfArena ar(ws, ws_bytes);
         FbScratch S;
-        if (!fb_carve(ar, B, std::max((size_t)H * W + 2 * (size_t)H + 64, fb_hand_floats(H, W)), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
+        if (!fb_carve(ar, B, fb_full_tmp_floats(H, W, p), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
         const int rc = fb_run_levels(prev, next, B, img_stride, H, W, p, out, flow_stride, S, levels, 0, cur, &pw, &ph, pp, s);
         if (rc) return rc;
     } else {
@@ -2286,7 +2295,7 @@ extern "C" int tf_farneback_batch_split(const uint8_t *prev, const uint8_t *next
             const int Bp = B - b0 < per ? B - b0 : per;
             TfArena ar(ws, ws_bytes);                                 // (the coarse phase's scratch is dead: stream order)
             FbScratch S;
-            if (!fb_carve(ar, Bp, std::max((size_t)H * W + 2 * (size_t)H + 64, fb_hand_floats(H, W)), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
+            if (!fb_carve(ar, Bp, fb_full_tmp_floats(H, W, p), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
             float *const outp[2] = {flow_fwd ? flow_fwd + (int64_t)b0 * flow_stride : nullptr, flow_bwd ? flow_bwd + (int64_t)b0 * flow_stride : nullptr};
             int curp[2] = {cur[0], cur[1]}, pwp = pw, php = ph;
             const int rc = fb_run_levels(prev + (int64_t)b0 * img_stride, next + (int64_t)b0 * img_stride, Bp, img_stride, H, W, p, outp, flow_stride, S,
@@ -2358,7 +2367,7 @@ extern "C" int tf_farneback_batch_phase(const uint8_t *prev, const uint8_t *next
         for (int d = 0; d < 2; d++) if (out[d] && cur[d] != 0) { tf_set_error("tf_farneback: internal slot parity error (phase 1)"); return TF_EINVAL; }
         return TF_OK;
     }
-    if (!fb_carve(ar, B, std::max((size_t)H * W + 2 * (size_t)H + 64, fb_hand_floats(H, W)), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
+    if (!fb_carve(ar, B, fb_full_tmp_floats(H, W, p), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
     int cur[2] = {0, 0}, pw = 0, ph = 0;                              // the flow of level FB_SPLIT_LEVEL sits in slot 0 = the output frames
     fb_level_size(H, W, p, FB_SPLIT_LEVEL, &ph, &pw);
     const int rc = fb_run_levels(prev, next, B, img_stride, H, W, p, out, flow_stride, S, FB_SPLIT_LEVEL - 1, 0, cur, &pw, &ph, pp, s);

@@ -648,9 +648,10 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
         TF_CHECK_LAUNCH();
     }
     if (!flow_done) {
-        // no tiled last iteration (sweep path, or no iterations at all; B == 1 here): flow = W + dW, with dW = 0 if nothing ran
+        // no tiled last iteration: the sweep path (B == 1 here), or no iterations at all (any B, tile path with
+        // fixed_point_iterations == 0).  flow = W + dW, with dW = 0 in every image's plane if nothing ran
+        if (!dW_cur) { TF_CHECK_HIP(hipMemsetAsync(dW, 0, (size_t)np * (size_t)B * 8, s)); dW_cur = dW; }
         for (int64_t b = 0; b < B; b++) {
-            if (!dW_cur) { TF_CHECK_HIP(hipMemsetAsync(dW, 0, (size_t)n * 8, s)); dW_cur = dW; }
             hipLaunchKernelGGL(k_vr_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Wf + b * bs.flow, dW_cur + b * bs.plane, n, (float2 *)flow + b * bs.flow);
             TF_CHECK_LAUNCH();
         }
