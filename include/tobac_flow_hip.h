@@ -92,8 +92,7 @@ typedef struct {
 } tf_farneback_params;
 /* chain_form: the row-sum chains of the iteration kernel as one lane per chain (leaves LDS for the kernels of other streams,
  * e.g. floods of finished windows: what a caller that runs other work beside the flow wants) or in two parts one row group
- * apart (39 KB of LDS per workgroup, a CU is full: 8 % faster when the flow has the GPU to itself).  DEFAULT = one lane.
- * TF_FBI_TWO_PART_CHAIN=0 / 1 in the environment overrides it (development switch). */
+ * apart (39 KB of LDS per workgroup, a CU is full: 8 % faster when the flow has the GPU to itself).  DEFAULT = one lane. */
 #define TF_FB_CHAIN_DEFAULT 0
 #define TF_FB_CHAIN_ONE_LANE 1
 #define TF_FB_CHAIN_TWO_PART 2

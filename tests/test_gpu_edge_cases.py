@@ -318,51 +318,40 @@ def test_watershed_refuses_a_nan_field_where_it_matters(tf):
             tf.watershed(z, z, bad, markers)
 
 
-def test_development_switches_do_not_change_results(tf, tmp_path):
-    """Library switches that select an alternative kernel for the same arithmetic (development switches) must
-    give bit-identical flows: the generic polynomial-expansion kernel instead of the register-blocked polyN = 5 one, the
-    one-launch-per-half-sweep SOR instead of the fused tile kernel, the two-pass blur instead of the fused 3 x 3 one.
-    The switches are read once per process, so the alternative runs in a child process."""
-    import subprocess
-    import sys
+def test_both_chain_forms_give_the_same_flows(tf):
+    """tf_farneback_params.chain_form schedules the row-sum chains of the iteration kernel: one lane per chain (what callers
+    that run floods beside the flow ask for: create_flow with on_frames_ready) or two parts one row group apart
+    (calculate_flow).  Both must give bit-identical flows in both directions -- here in one process, through the model's
+    parameter block, on a shape with one full strip and a ragged one (210 columns) and one with four full strips and a
+    ragged one (544 columns)."""
+    import torch
+    from tobac_flow_amd import _lib
+    from tobac_flow_amd.utils.flow_utils import FarnebackFlow
+    from tobac_flow_amd.utils.normalisation_utils import linear_norm
     rng = np.random.default_rng(21)
-    code = ("import sys, numpy as np; sys.path.insert(0, %r); import tobac_flow_amd.flow as tf; "
-            "a = np.load(%r); f, b = tf.calculate_flow(a, 'Farneback', vr_steps=1); np.save(%r, np.stack([f, b]))")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # a width that is no multiple of four (byte staging with reflected borders) and one that is (word staging; deep
-    # pyramid: blur kernels up to 39 taps)
-    for tag, shape in (("a", (3, 150, 210)), ("b", (2, 272, 544))):
+    for shape in ((3, 150, 210), (2, 272, 544)):
         a = ndi.gaussian_filter(rng.normal(size=shape), (0, 2.5, 2.5)).astype(np.float32) * 30 + 250
-        np.save(tmp_path / f"in_{tag}.npy", a)
-        fw, bw = tf.calculate_flow(a, "Farneback", vr_steps=1)
-        # (round 4) the iteration kernel's scheduling knobs: both directions of a strip in one workgroup, strips that let their
-        # left neighbour get ahead before they start, one column group of tickets whatever the launch size, one ticket list
-        # instead of one per XCD, every chain in two parts one row group apart instead of walked whole by one lane
-        for var in ("TF_FB_POLYEXP_GENERIC", "TF_VR_SOR_SWEEPS", "TF_VR_WEIGHTS_PASS", "TF_FB_BLUR_TWOPASS", "TF_FB_BLUR_NO_LDS",
-                    "TF_FBI_JOIN_DIRECTIONS", "TF_FBI_SLACK_ROWS", "TF_FBI_COLUMN_GROUPS", "TF_FBI_ONE_TICKET_LIST", "TF_FBI_TWO_PART_CHAIN"):
-            out = tmp_path / f"{var}_{tag}.npy"
-            # (calculate_flow asks for the two-part chain when it hands out no windows: the switch's OTHER value is the test here)
-            env = dict(os.environ, **{var: "13" if var == "TF_FBI_SLACK_ROWS" else ("0" if var == "TF_FBI_TWO_PART_CHAIN" else "1")})
-            subprocess.check_call([sys.executable, "-c", code % (root, str(tmp_path / f"in_{tag}.npy"), str(out))], env=env)
-            alt = np.load(out)
-            assert np.array_equal(alt[0], fw, equal_nan=True) and np.array_equal(alt[1], bw, equal_nan=True), (var, tag)
-        # the one switch that is NOT bit-neutral: round 3's iteration kernel (window sums as a tree, reciprocal + Newton step),
-        # kept for A/B timing -- within the north star's 1e-4 px of the sequential form on the raw vectors
-        raw = tf.calculate_flow(a, "Farneback")
-        out = tmp_path / f"tree_{tag}.npy"
-        code_raw = code.replace("vr_steps=1", "vr_steps=0")
-        subprocess.check_call([sys.executable, "-c", code_raw % (root, str(tmp_path / f"in_{tag}.npy"), str(out))], env=dict(os.environ, TF_FB_ROW_SUMS_TREE="1"))
-        alt = np.load(out)
-        d = max(np.nanmax(np.abs(alt[0] - raw[0])), np.nanmax(np.abs(alt[1] - raw[1])))
-        assert d <= 1e-4, d                                  # (often 0 at this size: the orders differ in the last bits of a double)
+        fr = torch.from_numpy(np.ascontiguousarray(tf.to_8bit(linear_norm(a), 0, 1))).cuda()
+        B, H, W = shape[0] - 1, shape[1], shape[2]
+        out = []
+        for form in (_lib.FB_CHAIN_ONE_LANE, _lib.FB_CHAIN_TWO_PART):
+            model = FarnebackFlow()
+            model.params.chain_form = form
+            f, b = (torch.empty((B, H, W, 2), dtype=torch.float32, device="cuda") for _ in range(2))
+            model.calc_batch_dev(fr[:-1].contiguous(), fr[1:].contiguous(), f, b)
+            model.check_launches()
+            out.append((f.cpu().numpy(), b.cpu().numpy()))
+        (f1, b1), (f2, b2) = out
+        assert np.isfinite(f1).all() and np.isfinite(b1).all(), shape
+        assert np.array_equal(f1, f2) and np.array_equal(b1, b2), shape
 
 
-def test_a_starved_chain_is_an_error_not_a_flow_of_nans(tf, tmp_path):
+def test_a_chain_starved_by_the_test_hook_is_an_error_not_a_flow_of_nans(tf, tmp_path):
     """VERDICT r4 weak 4 / ADVICE r4: a row-sum chain of k_fb_iter whose left neighbour's hand-over words never arrive gives up
     after a bounded number of polls and continues with NaN -- that must reach the caller as an error (TF_ESTARVED ->
-    TobacFlowHipError), never as a Flow with NaN rows and rc 0.  (i) Forced on the device: a child process in which the strips
-    never store their words (TF_FBI_SEQ_ABLATE=64) and the poll bound is 4 (TF_FBI_POLL_LIMIT): every chain right of strip 0
-    starves, create_flow raises.  (ii) The host path alone: the status word set from the host (tf_farneback_debug_set_starved)
+    TobacFlowHipError), never as a Flow with NaN rows and rc 0.  (i) Forced on the device: a child process with the library's
+    test hook TF_FBI_TEST_STARVE=4, in which the strips never store their words and the poll bound is 4: every chain right of
+    strip 0 starves, create_flow raises.  (ii) The host path alone: the status word set from the host (tf_farneback_debug_set_starved)
     makes the next batch call return TF_ESTARVED on entry, the report clears it, and the following call computes the same flow
     as before."""
     import subprocess
@@ -382,7 +371,7 @@ def test_a_starved_chain_is_an_error_not_a_flow_of_nans(tf, tmp_path):
             "    assert 'gave up' in str(e) and '-6' in str(e), str(e); print('STARVED-RAISED')\n"
             "else:\n"
             "    print('NO-ERROR')\n") % (root, str(tmp_path / "in.npy"))
-    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TF_FBI_SEQ_ABLATE="64", TF_FBI_POLL_LIMIT="4"),
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TF_FBI_TEST_STARVE="4"),
                          capture_output=True, text=True, timeout=600)
     assert "STARVED-RAISED" in out.stdout, (out.stdout, out.stderr[-2000:])
     # (ii) host path in this process: the status word of a flow's own (round 6: one per model object = per flow) set from the

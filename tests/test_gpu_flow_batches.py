@@ -13,9 +13,6 @@ Inputs are smooth seeded uint8 frames whose content drifts by a pixel per frame.
 """
 import ctypes
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -23,7 +20,6 @@ import scipy.ndimage as ndi
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TF_VR_FAST_DIVIDE, TF_VR_FAST_SOR = 1, 2
 SENTINEL = 1234.5                     # flow-buffer words outside the output frames (finite: a stray read is a wrong number)
 POISON = (0.75, -3.0)                 # workspace fills of the poisoned-scratch tests (finite: see section 4)
@@ -426,36 +422,28 @@ def test_farneback_batch_equals_the_pairs(name, shape, B):
         _fb_same_as_pairs(got, name, H, W, B, f"one direction {dirs}")
 
 
-def test_farneback_large_batch_reaches_the_lds_blur_with_unaligned_frames(tmp_path):
+def test_farneback_large_batch_reaches_the_lds_blur_with_unaligned_frames():
     """515 x 777: pyramid level 4 (scale 0.5) and level 5 (scale 0.6) have a source stride >= 12, where the row blur stages
     its rows in LDS (k_fb_blur_rows_sampled_lds): aligned 32-bit words where the image base, the batch stride and W are
     multiples of four, bytes with reflected borders otherwise.  H * W is odd and W is no multiple of four, so in a batch of
-    back-to-back frames every pair after the first takes the byte staging from an unaligned base.  The same batch in a
-    child process with TF_FB_BLUR_NO_LDS=1 (the global-memory form; the switch is read once per process) gives the same bits."""
+    back-to-back frames every pair after the first takes the byte staging from an unaligned base.  The batch through the
+    model's calc_batch_dev gives the pairs' bits (and so the oracle's, test_farneback_pair_against_the_oracle)."""
+    t = _torch()
+    from tobac_flow_amd.utils.flow_utils import FarnebackFlow
     (H, W), B = FB_LARGE
     assert (H * W) % 4 and W % 4
     for name in FB_LARGE_SETS:
         assert _fb_lds_levels(H, W, _fb_kw(name)), name
-    assert not _fb_lds_levels(272, 544, _fb_kw("default"))          # (the largest shape of the development-switch test)
-    fr = _fb_expected(FB_LARGE_SETS[0], H, W, B)[0]
-    np.save(tmp_path / "frames.npy", fr)
-    code = ("import sys, numpy as np, torch; sys.path.insert(0, %r)\n"
-            "from tobac_flow_amd.utils.flow_utils import FarnebackFlow\n"
-            "fr = torch.from_numpy(np.load(%r)).cuda(); B, H, W = fr.shape[0] - 1, fr.shape[1], fr.shape[2]\n"
-            "out = []\n"
-            "for kw in %r:\n"
-            "    m = FarnebackFlow(**kw)\n"
-            "    f, b = (torch.empty((B, H, W, 2), dtype=torch.float32, device='cuda') for _ in range(2))\n"
-            "    m.calc_batch_dev(fr[:-1], fr[1:], f, b)\n"
-            "    m.check_launches()\n"
-            "    out.append(np.stack([f.cpu().numpy(), b.cpu().numpy()]))\n"
-            "np.save(%r, np.stack(out))\n") % (ROOT, str(tmp_path / "frames.npy"), [_fb_kw(n) for n in FB_LARGE_SETS], str(tmp_path / "out.npy"))
-    subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, TF_FB_BLUR_NO_LDS="1"), timeout=600)
-    alt = np.load(tmp_path / "out.npy")
-    for i, name in enumerate(FB_LARGE_SETS):
+    assert not _fb_lds_levels(272, 544, _fb_kw("default"))          # (the largest shape of the chain-form test)
+    fr = t.from_numpy(_fb_expected(FB_LARGE_SETS[0], H, W, B)[0].copy()).cuda()
+    for name in FB_LARGE_SETS:
+        m = FarnebackFlow(**_fb_kw(name))
+        f, b = (t.empty((B, H, W, 2), dtype=t.float32, device="cuda") for _ in range(2))
+        m.calc_batch_dev(fr[:-1], fr[1:], f, b)
+        m.check_launches()
         _, fwd, bwd = _fb_expected(name, H, W, B)
-        _same_bits(alt[i, 0], fwd, f"{name}: forward flows without the LDS blur")
-        _same_bits(alt[i, 1], bwd, f"{name}: backward flows without the LDS blur")
+        _same_bits(f.cpu().numpy(), fwd, f"{name}: forward flows of the batch")
+        _same_bits(b.cpu().numpy(), bwd, f"{name}: backward flows of the batch")
 
 
 # ----------------------------------------------------------------------------- 3. split and phase

@@ -20,9 +20,8 @@
 //     down a column with the last 13 rows of M in a register ring and OpenCV's running column sum, the column sums of a row
 //     group go to LDS, and (round 4) OpenCV's running ROW sum is carried through them by 25 chain lanes and from column strip
 //     to column strip through tagged words in global memory: the flow is bit-identical to the oracle's.  The 5-channel M of
-//     OpenCV never exists in HBM.  (k_fb_iter_tree, round 3: window sums as a tree, within 7e-5 px; TF_FB_ROW_SUMS_TREE=1.)
-//     The unfused pair k_fb_update_matrices + k_fb_blur_solve (LDS tiles, one channel at a time) serves window sizes other
-//     than 13;
+//     OpenCV never exists in HBM.  The unfused pair k_fb_update_matrices + k_fb_blur_solve (LDS tiles, one channel at a
+//     time) serves window sizes other than 13;
 //   * all of these are HBM / L2- or latency-bound stencils: no MFMA.
 #include "tf_common.h"
 #include <math.h>
@@ -42,52 +41,10 @@ __device__ __forceinline__ int fb_reflect101(int p, int len) {
 // ---- Gaussian blur (cv::GaussianBlur on CV_32F: row pass then symmetric column pass) -----------
 struct FbKernel { int ksize; float k[FB_MAX_KSIZE]; };
 
-template <typename TIn>
-__global__ void __launch_bounds__(256)
-k_fb_blur_rows(const TIn *__restrict__ src, int H, int W, const FbKernel kk, float *__restrict__ dst, int64_t bs_src, int64_t bs_dst)
-{
-    src += (int64_t)blockIdx.z * bs_src; dst += (int64_t)blockIdx.z * bs_dst;
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= W || y >= H) return;
-    const int ksize = kk.ksize, r = ksize >> 1;
-    const float *k = kk.k;
-    const TIn *S = src + (int64_t)y * W;
-    float s;
-    if (ksize == 3) {
-        s = (float)S[x] * k[1] + ((float)S[fb_reflect101(x - 1, W)] + (float)S[fb_reflect101(x + 1, W)]) * k[0];
-    } else if (ksize == 5) {
-        s = (float)S[x] * k[2] + ((float)S[fb_reflect101(x - 1, W)] + (float)S[fb_reflect101(x + 1, W)]) * k[1]
-          + ((float)S[fb_reflect101(x - 2, W)] + (float)S[fb_reflect101(x + 2, W)]) * k[0];
-    } else {
-        s = k[0] * (float)S[fb_reflect101(x - r, W)];
-        if (x - r >= 0 && x + r < W) { for (int i = 1; i < ksize; i++) s += k[i] * (float)S[x - r + i]; }
-        else { for (int i = 1; i < ksize; i++) s += k[i] * (float)S[fb_reflect101(x - r + i, W)]; }
-    }
-    dst[(int64_t)y * W + x] = s;
-}
-
-__global__ void __launch_bounds__(256)
-k_fb_blur_cols(const float *__restrict__ src, int H, int W, const FbKernel kk, float *__restrict__ dst, int64_t bs_src, int64_t bs_dst)
-{
-    src += (int64_t)blockIdx.z * bs_src; dst += (int64_t)blockIdx.z * bs_dst;
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= W || y >= H) return;
-    const int r = kk.ksize >> 1;
-    const float *k = kk.k;
-    float s = k[r] * src[(int64_t)y * W + x];
-    if (y - r >= 0 && y + r < H) {
-        for (int i = 1; i <= r; i++) s += k[r + i] * (src[(int64_t)(y + i) * W + x] + src[(int64_t)(y - i) * W + x]);
-    } else {
-        for (int i = 1; i <= r; i++)
-            s += k[r + i] * (src[(int64_t)fb_reflect101(y + i, H) * W + x] + src[(int64_t)fb_reflect101(y - i, H) * W + x]);
-    }
-    dst[(int64_t)y * W + x] = s;
-}
-
-// 3 x 3 Gaussian blur in one pass (the kernel size of pyramid levels 0 and 1 with the default pyr_scale): every thread
-// forms the three row sums its column pass needs, with exactly the expressions of k_fb_blur_rows / k_fb_blur_cols, so the
-// result is bit-identical to the two-pass form while the float intermediate (4 B written + 4 B read per pixel) never
-// exists: 1 B read + 4 B written per pixel instead of 13.
+// 3 x 3 Gaussian blur in one pass (the kernel size of every full-size or exact-2x level, fb_run_levels): every thread
+// forms the three row sums its column pass needs, with exactly the expressions of OpenCV's row pass and symmetric column
+// pass, so the result is bit-identical to the two-pass form while the float intermediate (4 B written + 4 B read per
+// pixel) never exists: 1 B read + 4 B written per pixel instead of 13.
 template <typename TIn>
 __global__ void __launch_bounds__(256)
 k_fb_blur3_fused(const TIn *__restrict__ src, int H, int W, const FbKernel kk, float *__restrict__ dst, int64_t bs_src, int64_t bs_dst)
@@ -130,7 +87,7 @@ k_fb_blur3_fused(const TIn *__restrict__ src, int H, int W, const FbKernel kk, f
         const float ru = vu[e + 1] * k[1] + (vu[e] + vu[e + 2]) * k[0];
         const float rd = vd[e + 1] * k[1] + (vd[e] + vd[e + 2]) * k[0];
         float s = k[1] * r0;
-        s += k[2] * (rd + ru);                                // k_fb_blur_cols: k[r + 1] * (tmp[y + 1] + tmp[y - 1])
+        s += k[2] * (rd + ru);                                // column pass: k[r + 1] * (tmp[y + 1] + tmp[y - 1])
         o[e] = s;
     }
     float *D = dst + (int64_t)y * W + x0;
@@ -372,7 +329,7 @@ k_fb_blur_rows_sampled(const TIn *__restrict__ src, FbResizeGeom g, const FbKern
 #define FBL_ROW_WORDS (FBL_ROW_BYTES / 4 + FBL_ROW_BYTES / 32 + 8)
 __global__ void __launch_bounds__(256)
 k_fb_blur_rows_sampled_lds(const uint8_t *__restrict__ src, FbResizeGeom g, const FbKernel kk, float2 *__restrict__ rowf,
-                           int64_t bs_src, int64_t bs_dst, int unit_shift, int word_env)
+                           int64_t bs_src, int64_t bs_dst, int unit_shift)
 {
     __shared__ unsigned s_row[4][FBL_ROW_WORDS];
     src += (int64_t)blockIdx.z * bs_src; rowf += (int64_t)blockIdx.z * bs_dst;
@@ -422,14 +379,14 @@ k_fb_blur_rows_sampled_lds(const uint8_t *__restrict__ src, FbResizeGeom g, cons
     const float *k = kk.k;
     const uint8_t *L = (const uint8_t *)s_row[ry];
     // the word reads may touch the word after the last staged one (its value is never used: alignbyte drops it for the bytes
-    // that matter, but the index must be inside the LDS row); TF_FB_BLUR_BYTES=1: the byte reads of rounds 2 - 5
-    const bool word_reads = word_env && (((span + 3) >> 2) + 2 + (((span + 3) & ~3) >> unit_shift) < FBL_ROW_WORDS);
+    // that matter, but the index must be inside the LDS row; a segment too long for that takes the per-byte loop below)
+    const bool word_reads = ((span + 3) >> 2) + 2 + (((span + 3) & ~3) >> unit_shift) < FBL_ROW_WORDS;
     // byte a of the segment lives at a + 4 * (a >> unit_shift)
     auto at = [&](int a) { return (float)L[a + ((a >> unit_shift) << 2)]; };
     const int b0 = sx - r - lo, b1 = sx1 - r - lo;
     float s0, s1;
     static_assert(FBL_ROW_WORDS > 0, "");
-    if (b1 == b0 + 1 && (word_reads)) {
+    if (b1 == b0 + 1 && word_reads) {
         // (round 6) the same two chains fed from 32-bit LDS reads: byte a of the segment lives in word (a >> 2) + (a >> unit_shift),
         // a quad that starts at an arbitrary byte is v_alignbyte of two neighbouring words -- one LDS read per four taps
         // instead of four byte reads (the kernel was bound by its LDS instructions)
@@ -456,21 +413,7 @@ k_fb_blur_rows_sampled_lds(const uint8_t *__restrict__ src, FbResizeGeom g, cons
             cur = n3; lo = hi; a += 4;
         }
         for (; i < ksize; i++) { const float nxt = at(b0 + i + 1); s0 += k[i] * cur; s1 += k[i] * nxt; cur = nxt; }
-    } else if (b1 == b0 + 1) {
-        float cur = at(b0 + 1);
-        s0 = k[0] * at(b0); s1 = k[0] * cur;
-        int i = 1;
-        for (; i + 7 < ksize; i += 8) {
-            float nn[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) nn[u] = at(b0 + i + 1 + u);
-            s0 += k[i] * cur; s1 += k[i] * nn[0];
-#pragma unroll
-            for (int u = 1; u < 8; u++) { s0 += k[i + u] * nn[u - 1]; s1 += k[i + u] * nn[u]; }
-            cur = nn[7];
-        }
-        for (; i < ksize; i++) { const float nxt = at(b0 + i + 1); s0 += k[i] * cur; s1 += k[i] * nxt; cur = nxt; }
-    } else {
+    } else {                                                            // (same sums, same order, one byte per tap)
         s0 = k[0] * at(b0); s1 = k[0] * at(b1);
         for (int i = 1; i < ksize; i++) { s0 += k[i] * at(b0 + i); s1 += k[i] * at(b1 + i); }
     }
@@ -534,8 +477,6 @@ struct FbPoly { int n; float g[FB_MAX_POLY_N + 1], xg[FB_MAX_POLY_N + 1], xxg[FB
 // (float4 {y, x, yy, xx} + float {xy}).  HBM traffic = 4 B read + 20 B written per level pixel.
 #define FBP_W 64
 #define FBP_H 16
-// development switch: TF_FB_POLYEXP_GENERIC=1 routes polyN = 5 through the generic kernel too (same results)
-static bool fb_polyexp_generic() { static const bool v = getenv("TF_FB_POLYEXP_GENERIC") != nullptr; return v; }
 #define FBP_MAXN FB_MAX_POLY_N
 __global__ void __launch_bounds__(256)
 k_fb_polyexp(const float *__restrict__ I, int H, int W, FbPoly pp, float *__restrict__ R, int64_t plane,
@@ -598,22 +539,19 @@ k_fb_polyexp(const float *__restrict__ I, int H, int W, FbPoly pp, float *__rest
 // for FOUR output rows (14 tile values feed 4 x 11 taps), a thread of the horizontal pass owns FOUR consecutive output
 // columns of one row (14 values of each moment, fetched as three 16-byte and one 8-byte LDS reads from rows padded to
 // a multiple of four floats).  LDS reads per output drop from 11 + 33 to 3.5 + 10.5; every output is still formed by the
-// expressions of k_fb_polyexp in the same order (bit-identical, tests compare the two).
-// Round 6: the tile HEIGHT is a template parameter (16 = the default; 32: the halo rows, the vertical pass' 10 extra rows and
-// the two barriers are paid once per 32 output rows -- image reads 1.88 x -> 1.52 x the tile, 3 instead of 5 workgroups of LDS
-// per CU: 3 % faster with nothing beside it, 30 % slower in the timed region of bench.py, where the floods' kernels share the
-// CUs -- TF_FB_POLYEXP_TH=32 opts in, profiles/round6_polyexp_notes.txt has the measurements).
+// expressions of k_fb_polyexp in the same order (bit-identical to the oracle, as k_fb_polyexp is).
+// (Round 6, measured and not adopted: 64 x 32 tiles -- 3 % faster with nothing beside the kernel, 30 % slower in the timed
+// region of bench.py, where the floods' kernels share the CUs; profiles/round6_polyexp_notes.txt.)
 #define FBP5_TS (FBP_W + 2 * 5 + 2)      /* row stride of the moment tiles: 76 floats, 16-byte aligned rows */
-template <int FBP5_H>
 __global__ void __launch_bounds__(256)
 k_fb_polyexp5(const float *__restrict__ I, int H, int W, FbPoly pp, float *__restrict__ R, int64_t plane,
               int64_t bs_I, int64_t bs_R)
 {
-    constexpr int n = 5, tw = FBP_W + 2 * n, th = FBP5_H + 2 * n;
+    constexpr int n = 5, tw = FBP_W + 2 * n, th = FBP_H + 2 * n;
     __shared__ float tI[th * tw];
-    __shared__ __attribute__((aligned(16))) float tT[3][FBP5_H * FBP5_TS];
+    __shared__ __attribute__((aligned(16))) float tT[3][FBP_H * FBP5_TS];
     I += (int64_t)blockIdx.z * bs_I; R += (int64_t)blockIdx.z * bs_R;
-    const int bx = blockIdx.x * FBP_W, by = blockIdx.y * FBP5_H;
+    const int bx = blockIdx.x * FBP_W, by = blockIdx.y * FBP_H;
     const int tid = threadIdx.y * 64 + threadIdx.x;
     {
         // all loads of a thread first, the LDS stores afterwards: a store right behind its load makes every trip of the
@@ -632,7 +570,7 @@ k_fb_polyexp5(const float *__restrict__ I, int H, int W, FbPoly pp, float *__res
     float g[n + 1], xg[n + 1], xxg[n + 1];
 #pragma unroll
     for (int k = 0; k <= n; k++) { g[k] = pp.g[k]; xg[k] = pp.xg[k]; xxg[k] = pp.xxg[k]; }
-    for (int i = tid; i < tw * (FBP5_H / 4); i += 256) {
+    for (int i = tid; i < tw * (FBP_H / 4); i += 256) {
         const int rg = i / tw, tx = i - rg * tw;
         float v[14];
 #pragma unroll
@@ -653,12 +591,8 @@ k_fb_polyexp5(const float *__restrict__ I, int H, int W, FbPoly pp, float *__res
         }
     }
     __syncthreads();
-    const int x4 = (tid & 15) * 4;
-    if (bx + x4 >= W) return;
-#pragma unroll
-    for (int part = 0; part < FBP5_H / 16; part++) {
-    const int oy = (tid >> 4) + 16 * part, y = by + oy;
-    if (y >= H) break;
+    const int x4 = (tid & 15) * 4, oy = tid >> 4, y = by + oy;
+    if (bx + x4 >= W || y >= H) return;
     float a[14], b[14], c[14];
     {
         const float *pa = tT[0] + oy * FBP5_TS + x4, *pb = tT[1] + oy * FBP5_TS + x4, *pc = tT[2] + oy * FBP5_TS + x4;
@@ -696,19 +630,13 @@ k_fb_polyexp5(const float *__restrict__ I, int H, int W, FbPoly pp, float *__res
                                        (float)(b1 * pp.ig03 + b5 * pp.ig33), (float)(b1 * pp.ig03 + b4 * pp.ig33));
         R[4 * plane + o] = (float)(b6 * pp.ig55);
     }
-    }
 }
 
 static void fb_launch_polyexp(const float *I, int h, int w, const FbPoly &pp, float *R, int64_t plane, int64_t bs_I, int64_t bs_R, int B, hipStream_t s)
 {
-    static const int th_env = getenv("TF_FB_POLYEXP_TH") ? atoi(getenv("TF_FB_POLYEXP_TH")) : 0;      // development switch: 16 / 32
-    const dim3 block(64, 4);
-    if (pp.n != 5 || fb_polyexp_generic())
-        hipLaunchKernelGGL(k_fb_polyexp, dim3((w + FBP_W - 1) / FBP_W, (h + FBP_H - 1) / FBP_H, B), block, 0, s, I, h, w, pp, R, plane, bs_I, bs_R);
-    else if (th_env == 32)                                   // 64 x 32 tiles: 3 % faster alone, 30 % SLOWER beside the floods (round 6, measured): opt-in
-        hipLaunchKernelGGL(k_fb_polyexp5<32>, dim3((w + FBP_W - 1) / FBP_W, (h + 31) / 32, B), block, 0, s, I, h, w, pp, R, plane, bs_I, bs_R);
-    else
-        hipLaunchKernelGGL(k_fb_polyexp5<16>, dim3((w + FBP_W - 1) / FBP_W, (h + 15) / 16, B), block, 0, s, I, h, w, pp, R, plane, bs_I, bs_R);
+    const dim3 grid((w + FBP_W - 1) / FBP_W, (h + FBP_H - 1) / FBP_H, B), block(64, 4);
+    if (pp.n == 5) hipLaunchKernelGGL(k_fb_polyexp5, grid, block, 0, s, I, h, w, pp, R, plane, bs_I, bs_R);
+    else hipLaunchKernelGGL(k_fb_polyexp, grid, block, 0, s, I, h, w, pp, R, plane, bs_I, bs_R);
 }
 
 // ---- FarnebackUpdateMatrices ---------------------------------------------------------------------
@@ -775,14 +703,12 @@ k_fb_update_matrices(const float *__restrict__ R0, const float *__restrict__ R1,
 
 // ---- fused iteration: UpdateMatrices -> 13x13 box sums (double) -> 2x2 solve -----------------------
 // One launch = one Farnebaeck iteration of BOTH directions for a batch of frame pairs.  A workgroup owns a strip of
-// FBI_OW = 116 output columns (+ 6 halo columns each side) over the WHOLE height, with FBI_T = 128 threads (two waves)
-// per direction: 256 threads when both directions run (round 3), so that they share the R rows they both read.
-// Thread j walks DOWN its column: at every row it evaluates M = UpdateMatrices(R0, R1, flow_old) in
+// FBI_OW = 116 output columns (+ 6 halo columns each side) of one direction over the WHOLE height, with FBI_T = 128
+// threads (two waves).  Thread j walks DOWN its column: at every row it evaluates M = UpdateMatrices(R0, R1, flow_old) in
 // registers, keeps the last 13 rows of M in a register ring and the running 13-row column sums in
-// double (OpenCV's recurrence, float-rounded differences included); the five column sums go to an LDS row, from
-// which thread t takes (row t / 29, quad t % 29): four 13-wide window sums that share their ten middle terms, four
-// 2x2 solves, flow_new.  The 5-plane matrix M never exists in HBM: per level pixel
-// the kernel moves R0 (20 B) + R1 (20 B) + flow in (8 B) + flow out (8 B).
+// double (OpenCV's recurrence, float-rounded differences included); the five column sums of a row group go to LDS rows,
+// along which OpenCV's running row sums are carried (below), then the 2x2 solves, flow_new.  The 5-plane matrix M never
+// exists in HBM: per level pixel the kernel moves R0 (20 B) + R1 (20 B) + flow in (8 B) + flow out (8 B).
 // The per-row evaluation is BRANCH-FREE (out-of-image gathers read a valid dummy address and are
 // discarded by selects) so that the loads of FBI_NB rows are in flight together, and the flow of the next
 // row group is fetched before the LDS phase of the current one.  Occupancy: two waves per SIMD = two four-wave workgroups per CU.
@@ -797,12 +723,10 @@ struct FbIterArgs {
     const float *R[2]; const float *fin[2]; float *fout[2]; int dir[2]; int nd, nx; int64_t bs_R, bs_fin[2], bs_fout[2];
     // sequential row sums (k_fb_iter): hand-over words of batch item 0 (item b adds b * bs_hand words), this launch's tag, its ticket counter
     unsigned long long *hand; int64_t bs_hand; unsigned epoch; int *ticket;
-    int abl;                        // timing aid (TF_FBI_SEQ_ABLATE): 1 no wait for the left neighbour, 2 no chain, 4 no solve, 16 hand-over without the chain (all wrong flows); 64 no hand-over stores (the chains right of strip 0 starve: tests of TF_ESTARVED); 8 count waiting chains, 128 no priority for the chain wave, 256 priority 1 instead of 3 (right flows)
-    int xcd_lists;                  // 1: one ticket list per XCD (pairs dealt round robin), 0: one list
-    int nq;                         // 1: a workgroup holds all directions of its strip; 2: one direction per workgroup, directions take tickets
-    int nb, nxg, slack_rows;        // pairs in the launch; strips per column group (ticket order); rows a strip lets its left neighbour get ahead before it starts
+    int nb, nxg;                    // pairs in the launch; strips per column group (ticket order)
     int *starved;                   // host-visible word (fb_starved_word): set by a chain whose left neighbour's words never arrived -- its row is NaN, the call is an error
-    int poll_limit;                 // polls before such a chain gives up (1 << 22: several seconds; TF_FBI_POLL_LIMIT: tests)
+    int poll_limit;                 // polls before such a chain gives up (1 << 22: several seconds)
+    int starve;                     // test hook (fb_test_starve_polls): no hand-over stores, so every chain right of strip 0 starves
 };
 #define FBI_G 5                     // rows per group (13 = 4 + 4 + 5)
 #ifndef FBI_NB
@@ -820,11 +744,11 @@ struct FbIterCtx {
     // the four corners of the bilinear gather share ONE per-thread offset: the corner displacement (+1 element,
     // +1 row, both) is folded into four wave-uniform base pointers
     const char *R1c[4], *R1ec[4];
-    int H, W; int j, dj, tg, tq, x_strip, xc, y0, y1; float xscale; bool xborder;
+    int H, W; int j, x_strip, xc; float xscale; bool xborder;
     bool strip_xborder;             // wave-uniform: some column of this strip lies in OpenCV's border band (xborder of any thread)
     // sequential row sums: strip index / count, the (row of the group, channel) this lane scans, hand-over slots of the left
     // neighbour (read) and of this strip (written), the launch's tag
-    int sx, nx, sr, sch; const unsigned long long *hin; unsigned long long *hout; unsigned epoch; int abl; int *spins; int *starved; int poll_limit;
+    int sx, nx, sr, sch; const unsigned long long *hin; unsigned long long *hout; unsigned epoch; int starve; int *starved; int poll_limit;
     int rsr, rsch; bool full;       // (row, channel) of a right-half chain lane (j - 32); a full strip of FBI_OW output columns
 };
 
@@ -841,18 +765,17 @@ __device__ __forceinline__ float2 fb_iter_flow_at(const FbIterCtx &c, int s)
 }
 
 // issue every load of one M evaluation (same arithmetic as fb_matrix_at, branch-free)
-template <int ABL = 0>
 __device__ __forceinline__ void fb_taps_load(const FbIterCtx &c, int s, float2 fl, FbTaps &t)
 {
     typedef fb_off_t off_t;
     const int y = tf_clampi(s, 0, c.H - 1);
-    const off_t o = ABL == 2 ? (off_t)c.xc : (off_t)y * (off_t)c.W + (off_t)c.xc;      // ABL 2: every gather from row 0
+    const off_t o = (off_t)y * (off_t)c.W + (off_t)c.xc;
     t.dx = fl.x; t.dy = fl.y;
     const float fx = c.xc + t.dx, fy = y + t.dy;
     const int x1 = tf_cvfloor(fx), y1 = tf_cvfloor(fy);
     const bool inb = (unsigned)x1 < (unsigned)(c.W - 1) && (unsigned)y1 < (unsigned)(c.H - 1);
     // out of the image: the patch at element 0 is read instead (always valid, see the base pointers) and discarded
-    const off_t q = ABL == 2 ? (off_t)(inb ? x1 : 0) : (inb ? (off_t)y1 * (off_t)c.W + (off_t)x1 : (off_t)0);
+    const off_t q = inb ? (off_t)y1 * (off_t)c.W + (off_t)x1 : (off_t)0;
     const off_t q16 = q * 16, q4 = q * 4;
     t.q0 = fb_ld<float4>(c.R0, o * 16);
     t.q04 = fb_ld<float>(c.R0e, o * 4);
@@ -906,107 +829,21 @@ __device__ __forceinline__ void fb_taps_eval(const FbIterCtx &c, int s, const Fb
     m[4] = r6 * r2 + r5 * r3;
 }
 
-// LDS row of column sums: column i lives at i + i/4 (one pad per four) so that both access patterns are
-// conflict-free: the vertical phase writes consecutive i, the horizontal phase reads i = 4 q + k (stride 5).
-#define FBI_VS (FBI_T + FBI_T / 4)
-#define FBI_Q (FBI_OW / 4)          // 29 quads of 4 outputs per strip row
-
-// horizontal phase for one (row g, quad q): 16 column sums per channel -> four 13-wide window sums ->
-// four 2x2 solves.  The four windows share the ten middle terms.
-__device__ __forceinline__ void fb_iter_quad(const FbIterCtx &c, int yo, int g, int q, const double *vrow)
-{
-    typedef fb_off_t off_t;
-    const int x0 = c.x_strip + 4 * q;
-    if (yo < c.y0 || yo >= c.y1 || x0 >= c.W) return;
-    const double *base = vrow + (g * 5) * FBI_VS + 5 * q;
-    double sum[5][4];
-#pragma unroll
-    for (int ch = 0; ch < 5; ch++) {
-        double v[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = base[ch * FBI_VS + k + (k >> 2)];
-        // balanced tree over the ten shared terms
-        const double T = (((v[3] + v[4]) + (v[5] + v[6])) + ((v[7] + v[8]) + (v[9] + v[10]))) + (v[11] + v[12]);
-        const double lo = v[1] + v[2], hi = v[13] + v[14];
-        sum[ch][0] = v[0] + lo + T;
-        sum[ch][1] = lo + T + v[13];
-        sum[ch][2] = v[2] + T + hi;
-        sum[ch][3] = T + hi + v[15];
-    }
-    float2 *out = (float2 *)(c.fout + ((off_t)yo * (off_t)c.W + (off_t)x0) * 8);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const double g11 = sum[0][u], g12 = sum[1][u], g22 = sum[2][u], h1 = sum[3][u], h2 = sum[4][u];
-        // flow = (G h)/(det G + 1e-3) with G, h the window MEANS: evaluated on the window SUMS with the
-        // regulariser scaled by 169^2 instead (saves five multiplies); hardware reciprocal + one Newton step
-        const double det = g11 * g22 - g12 * g12 + 1e-3 * (double)(FBI_WIN * FBI_WIN) * (double)(FBI_WIN * FBI_WIN);
-        double idet = __builtin_amdgcn_rcp(det);
-        idet = idet * (2.0 - det * idet);
-        float2 f;
-        f.x = (float)((g11 * h2 - g12 * h1) * idet);
-        f.y = (float)((g22 * h1 - g12 * h2) * idet);
-        if (x0 + u < c.W) out[u] = f;
-    }
-}
-
-// one group of G consecutive window rows s0 .. s0+G-1 with STATIC ring slots K0 .. K0+G-1:
-//   1. evaluate M for NB rows at a time (their loads in flight together), slide the 13-row column sums,
-//      park them in LDS,
-//   2. fetch the flow of the next group's GN rows,
-//   3. one barrier, then the horizontal phase: thread t takes (row t / 29, quad t % 29); a 5-row group has 145 items,
-//      so its threads 0 .. 16 take a second one.
-// ABL 1 (development aid, env TF_FBI_ABLATE=1): synthetic M instead of the gathers; ABL 2: the gathers read row 0 only
-// (same instructions, cache-resident data).
-template <int K0, int G, int GN, int NB, int ABL>
-__device__ __forceinline__ void fb_iter_group(const FbIterCtx &c, int s0, float (&ring)[FBI_WIN][5], double (&S)[5],
-                                              float2 (&fl)[FBI_G], double *vrow)
-{
-#pragma unroll
-    for (int g0 = 0; g0 < G; g0 += NB) {
-        FbTaps t[NB];
-        float m[NB][5];
-#pragma unroll
-        for (int r = 0; r < NB; r++)
-            if (g0 + r < G && ABL != 1) fb_taps_load<ABL>(c, s0 + g0 + r, fl[g0 + r], t[r]);
-#pragma unroll
-        for (int r = 0; r < NB; r++)
-            if (g0 + r < G) {
-                const int g = g0 + r, s = s0 + g;
-                if (ABL == 1) { m[r][0] = (float)s; m[r][1] = (float)c.xc; m[r][2] = 1.f; m[r][3] = 2.f; m[r][4] = (float)(s + c.xc); }
-                else fb_taps_eval(c, s, t[r], m[r]);
-#pragma unroll
-                for (int ch = 0; ch < 5; ch++) {
-                    S[ch] += (double)(m[r][ch] - ring[K0 + g][ch]); ring[K0 + g][ch] = m[r][ch];
-                    vrow[(g * 5 + ch) * FBI_VS + c.dj] = S[ch];
-                }
-            }
-    }
-    if (ABL != 1) {
-#pragma unroll
-        for (int g = 0; g < GN; g++) fl[g] = fb_iter_flow_at(c, s0 + G + g);
-    }
-    __syncthreads();
-    if (c.j < G * FBI_Q) fb_iter_quad(c, s0 + c.tg - FBI_M, c.tg, c.tq, vrow);
-    if (G * FBI_Q > FBI_T && c.j < G * FBI_Q - FBI_T) {
-        const int item = c.j + FBI_T, tg = item / FBI_Q;
-        fb_iter_quad(c, s0 + tg - FBI_M, tg, item - tg * FBI_Q, vrow);
-    }
-    __syncthreads();
-}
-
 // Workgroup width (round 2): 128 threads = two waves.  The occupancy is two waves per SIMD whatever the width, i.e. FOUR
 // independent barrier domains per CU instead of the two of 256-thread workgroups: the phases of a workgroup (gathers,
 // matrix arithmetic, LDS column sums, window sums + solve) run one after the other, so what overlaps them is the number
 // of workgroups in different phases.  12 x 5424^2 step: 132.4 ms (256 threads, 5 % halo columns) -> 115.4 ms (128
 // threads, 10 %) -> 126.2 ms (64 threads, 23 %).  The rows-in-flight count FBI_NB no longer matters (2 / 4 / 5: 116.3 /
-// 116.1 / 116.3 ms): with every gather redirected to a cache-resident row (TF_FBI_ABLATE=2) the 256-thread kernel
-// took 117.9 instead of 132.5 ms and without gathers and matrix arithmetic (TF_FBI_ABLATE=1) 51.7 ms -- the kernel is
-// bound by the SUM of its VALU (about 55 ms at full issue rate), L1 (22 ms) and LDS (22 ms) work, not by HBM latency.
-// Occupancy is two waves per SIMD by construction (65 ring registers + the 72 of the horizontal phase; 64 KB of LDS):
-// the launch bound says so, which lets the compiler schedule for the 256-register budget (5 % faster than the
-// default bound).  Forcing three waves spills the ring (+70 %); row groups 4 + 4 + 4 + 1 with 51 KB of LDS cost
-// 2 % for the extra barrier pair and gain nothing while the registers hold the kernel at two waves.
-// Workgroup = (pair, strip of FBI_OW columns), all rows, both directions (two waves each).
+// 116.1 / 116.3 ms): with every gather redirected to a cache-resident row (an ablation of round 2) the 256-thread kernel
+// took 117.9 instead of 132.5 ms and without gathers and matrix arithmetic 51.7 ms -- the kernel is bound by the SUM of its
+// VALU (about 55 ms at full issue rate), L1 (22 ms) and LDS (22 ms) work, not by HBM latency.
+// Occupancy is two waves per SIMD by construction (65 ring registers + the chain and solve phases): the launch bound says
+// so, which lets the compiler schedule for the 256-register budget (5 % faster than the default bound).  Forcing three
+// waves spills the ring (+70 %).
+// Workgroup = (pair, strip of FBI_OW columns, direction), all rows.  (Round 3 put both directions of a strip into one
+// four-wave workgroup, so that they share the R rows they both read: -23 % HBM bytes, the same time; with the chains of
+// round 4 four independent two-wave workgroups per CU overlap the chains' latency-bound stretches better -- config F:
+// 2.05 s of k_fb_iter per step against 2.25 s.)
 //
 // Why whole columns.  OpenCV's vertical running sum, term for term (FarnebackUpdateFlow_Blur; oracle/c/farneback.c:263-281):
 //   vsum  = M[0] * (m + 2)  [float product]  + M[1] + ... + M[m-1]          (rows clamped to H - 1)
@@ -1025,110 +862,17 @@ __device__ __forceinline__ void fb_iter_group(const FbIterCtx &c, int s0, float 
 //   start delays that de-phase the workgroups: no effect
 // So the remedy is not in the kernel but in the batch: the host layer sizes a launch to a whole number of rounds
 // (tf_farneback_batch_hint: 21 pairs = 1974 chains = 96 % of two rounds at 5424^2), which a stack of frames allows.
-template <int NB, int ABL>
-__global__ void __launch_bounds__(2 * FBI_T, 2)
-k_fb_iter_tree(FbIterArgs a, int H, int W, int64_t plane)
-{
-    // BOTH directions of a strip in ONE workgroup: waves 0 - 1 walk the column strip for direction dir[0], waves 2 - 3 for
-    // dir[1], in step (they share the barriers).  Each direction reads its own expansion row by row and gathers from the
-    // other's -- the very rows the other direction is reading: with the two in one workgroup every R row is fetched from
-    // HBM once instead of twice (as separate workgroups they drift apart, and an XCD's L2 turns over every few
-    // microseconds at this kernel's rate: measured traffic was that of NO sharing, 1.6 - 1.9 x the compulsory bytes).
-    // Occupancy is unchanged: 4 waves and 64 KB of LDS per workgroup, two workgroups per CU.
-    __shared__ double vrow_all[2][FBI_G * 5 * FBI_VS];
-    const int q = __builtin_amdgcn_readfirstlane(threadIdx.x / FBI_T); // wave-uniform: 0 / 1 (one direction only: 128 threads, q = 0)
-    double *vrow = vrow_all[q];
-    const int b = blockIdx.x / a.nx, sx = blockIdx.x - b * a.nx;
-    const int d = a.dir[q];                                            // 0: prev -> next, 1: next -> prev
-    FbIterCtx c;
-    const float *R0 = a.R[d] + b * a.bs_R, *R1 = a.R[1 - d] + b * a.bs_R;
-    c.R0 = (const char *)R0; c.R0e = (const char *)(R0 + 4 * plane);
-    {
-        // corner displacements in elements; a level narrower / shorter than two pixels has no in-image patch at all
-        // (inb is never true): all four corners then alias element 0 so that the discarded reads stay in bounds
-        const bool patch = W >= 2 && H >= 2;
-        const int64_t dcorner[4] = {0, patch ? 1 : 0, patch ? W : 0, patch ? (int64_t)W + 1 : 0};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            c.R1c[k] = (const char *)R1 + dcorner[k] * 16;
-            c.R1ec[k] = (const char *)(R1 + 4 * plane) + dcorner[k] * 4;
-        }
-    }
-    c.fin = (const char *)(a.fin[q] + b * a.bs_fin[q]); c.fout = (char *)(a.fout[q] + b * a.bs_fout[q]);
-    c.H = H; c.W = W;
-    c.j = threadIdx.x - q * FBI_T;
-    c.dj = c.j + (c.j >> 2);
-    c.tg = c.j / FBI_Q; c.tq = c.j - c.tg * FBI_Q;
-    c.x_strip = sx * FBI_OW;
-    c.xc = tf_clampi(c.x_strip + c.j - FBI_M, 0, W - 1);              // column this thread evaluates M for (replicate border)
-    c.y0 = 0;
-    c.y1 = H;                                                         // output rows [0, H)
-    {
-        const float border[5] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f};
-        const int xb = W - 1 - c.xc;
-        float lo = 1.f, hi = 1.f;
-#pragma unroll
-        for (int k = 0; k < 5; k++) { lo = c.xc == k ? border[k] : lo; hi = xb == k ? border[k] : hi; }
-        c.xscale = lo * hi;
-        c.xborder = (unsigned)(c.xc - 5) >= (unsigned)(W - 10);
-        c.strip_xborder = W < 10 || c.x_strip - FBI_M < 5 || c.x_strip + FBI_T - FBI_M - 1 > W - 6;     // (columns x_strip - 6 .. x_strip + 121, clamped)
-    }
-    float ring[FBI_WIN][5];
-    double S[5];
-    float2 fl[FBI_G];
-    {
-        // rows 0 .. m-1 -> ring slots m+1 .. 2m; slots 0 .. m+1 hold row 0 (OpenCV's max(y - m - 1, 0) for the rows above the
-        // image); three rows at a time (their loads in flight together, few registers live next to the ring)
-#pragma unroll
-        for (int r0 = 0; r0 < FBI_M; r0 += 3) {
-            float2 f0[3];
-            FbTaps t[3];
-            float mm[3][5];
-#pragma unroll
-            for (int r = 0; r < 3; r++) f0[r] = (ABL != 1) ? fb_iter_flow_at(c, r0 + r) : make_float2(0.f, 0.f);
-#pragma unroll
-            for (int r = 0; r < 3; r++) if (ABL != 1) fb_taps_load<ABL>(c, r0 + r, f0[r], t[r]);
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                const int row = r0 + r;
-                if (ABL == 1) { mm[r][0] = (float)row; mm[r][1] = (float)c.xc; mm[r][2] = 1.f; mm[r][3] = 2.f; mm[r][4] = (float)(row + c.xc); }
-                else fb_taps_eval(c, row, t[r], mm[r]);
-#pragma unroll
-                for (int ch = 0; ch < 5; ch++) {
-                    if (row == 0) {
-                        S[ch] = (double)(mm[r][ch] * (float)(FBI_M + 2));
-#pragma unroll
-                        for (int k = 0; k <= FBI_M + 1; k++) ring[k][ch] = mm[r][ch];       // rows -(m+1) .. 0
-                    } else {
-                        S[ch] += (double)mm[r][ch];
-                        ring[FBI_M + 1 + row][ch] = mm[r][ch];
-                    }
-                }
-            }
-        }
-    }
-    const int s_last = H - 1 + FBI_M;                                  // window rows needed (inclusive; clamped to H - 1)
-#pragma unroll
-    for (int g = 0; g < FBI_G; g++) fl[g] = (ABL != 1) ? fb_iter_flow_at(c, FBI_M + g) : make_float2(0.f, 0.f);
-    // row s enters ring slot (s - m) mod 13, which holds row s - 13 = (output row) - m - 1: OpenCV's srow0.
-    // rows past s_last are evaluated (clamped, harmless) but never produce output
-    for (int base = FBI_M; base <= s_last; base += FBI_WIN) {
-        fb_iter_group<0, 4, 4, NB, ABL>(c, base, ring, S, fl, vrow);
-        fb_iter_group<4, 4, 5, NB, ABL>(c, base + 4, ring, S, fl, vrow);
-        fb_iter_group<8, 5, 4, NB, ABL>(c, base + 8, ring, S, fl, vrow);
-    }
-}
 
-// ---- the same iteration with OpenCV's ROW sums too (round 4): bit-identical flow ---------------------------------------------
+// ---- OpenCV's ROW sums (round 4): bit-identical flow ---------------------------------------------
 // FarnebackUpdateFlow_Blur forms the 13-wide window sums of a row as a RUNNING sum in double, left to right over the
 // whole row (oracle/c/farneback.c:282-292):
 //   g  = vsum[0] * (m + 2) + vsum[1] + ... + vsum[m - 1];     x = 0 .. W-1:   g += vsum[x + m] - vsum[x - m - 1]
 // (columns left / right of the image replicate the border).  Every rounding of that chain stays in g for the rest of the
-// row, so no other order of the additions reproduces it (k_fb_iter_tree above: max 7e-5 px away at 5424^2, which the
-// refinement's 1/32-px remap bins amplify to 0.02 px in the composed flow).  A floating-point chain is sequential by
+// row, so no other order of the additions reproduces it (round 3's window sums as a tree: max 7e-5 px away at 5424^2, which
+// the refinement's 1/32-px remap bins amplify to 0.02 px in the composed flow).  A floating-point chain is sequential by
 // definition; what is parallel is the number of chains -- rows x 5 channels x strips x directions x pairs:
 //   * a workgroup still owns a strip of FBI_OW columns over all rows and forms OpenCV's column sums as before;
-//   * per row group, lane (row r, channel ch) of each direction's first wave walks the strip's 116 columns:
+//   * per row group, lane (row r, channel ch) of the workgroup's first wave walks the strip's 116 columns:
 //     g += V[x + 6] - V[x - 7] out of LDS, and leaves g in the slot whose column sum is no longer needed (25 chains side by
 //     side; the other lanes have nothing to do for ~1 us: the price of the order);
 //   * the chain ENTERS the strip with the g and the V[x_strip - 7] its left neighbour left at the same row: strips hand
@@ -1139,8 +883,7 @@ k_fb_iter_tree(FbIterArgs a, int H, int W, int64_t plane)
 //   * workgroups take their (pair, strip, direction) from a TICKET counter in arrival order, strips of a pair left to right
 //     (column group by column group when the launch needs several rounds of resident workgroups): a workgroup only ever
 //     waits for a lower ticket, which is running or done -- no deadlock whatever the dispatch order;
-//   * the 2 x 2 solve is OpenCV's expression on the window MEANS, with a true division (k_fb_iter_tree: scaled
-//     regulariser, reciprocal + Newton step).
+//   * the 2 x 2 solve is OpenCV's expression on the window MEANS, with a true division.
 #define FBI_VS2 (FBI_T + 9)         // LDS row stride in doubles, odd: lanes (r, ch) of a scan hit different banks (137 * 2 mod 64 = 18)
 #define FBI_HDR 16384               // bytes of ticket counters in front of a batch's hand-over words: 16 ints per launch of a level (8 used: one per XCD)
 #define FBI_HW 20                   // hand-over words per row and strip: (g, V[next strip's x - 7]) x 5 channels x two halves, stored as four planes of H x 5
@@ -1168,7 +911,7 @@ __device__ __forceinline__ bool fb_hand_valid(const FbIterCtx &c, const FbHand &
 // (`h`: as fetched at the top of the row group -- the neighbour is normally ahead: they are there -- polled here if not)
 __device__ __forceinline__ void fb_chain_enter(const FbIterCtx &c, int yo, int ch, const double *row, FbHand h, double &g, double &sub)
 {
-    if (c.sx == 0 || (c.abl & 1)) {
+    if (c.sx == 0) {
         const double v0 = row[FBI_M];                                  // column 0
         g = v0 * (double)(FBI_M + 2);
 #pragma unroll
@@ -1180,9 +923,7 @@ __device__ __forceinline__ void fb_chain_enter(const FbIterCtx &c, int yo, int c
         // seconds -- so that the grid drains whatever happens.  A chain that gives up continues with NaN AND says so: it sets
         // the launch's host-visible `starved` word, which turns the call that owns the launch into TF_ESTARVED -- a device
         // slowed down enough for this, by a profiler's serialisation or a preempted queue, must not hand out NaN rows with rc 0)
-        if (!ok && c.spins) atomicAdd(c.spins, 1);                     // (development aid: chains that found their words missing at scan time)
         for (int spin = 0; !ok && spin < c.poll_limit; spin++) {
-            if (c.spins) atomicAdd(c.spins + 1, 1);
             __builtin_amdgcn_s_sleep(1);
             fb_hand_load(c, yo, ch, h);
             ok = fb_hand_valid(c, h);
@@ -1198,7 +939,7 @@ __device__ __forceinline__ void fb_chain_enter(const FbIterCtx &c, int yo, int c
 // (g, V[next strip's x - 7]) for the strip to the right
 __device__ __forceinline__ void fb_hand_store(const FbIterCtx &c, int yo, int ch, double g, double sub)
 {
-    if (c.sx >= c.nx - 1 || (c.abl & 64)) return;                    // (64: test aid -- the words never leave: every chain to the right starves)
+    if (c.sx >= c.nx - 1 || c.starve) return;                        // (test hook: the words never leave, every chain to the right starves)
     unsigned long long *pg = c.hout + (int64_t)yo * 5 + ch;
     const int64_t pl = (int64_t)c.H * 5;
     const unsigned long long tag = (unsigned long long)c.epoch << 32;
@@ -1261,8 +1002,7 @@ __device__ __forceinline__ void fb_iter_scan(const FbIterCtx &c, int yo, int ch,
     const int n_out = min(FBI_OW, c.W - c.x_strip);                    // (wave-uniform)
     double g, sub;
     fb_chain_enter(c, yo, ch, row, h, g, sub);
-    if (c.abl & 16) {                                                  // timing aid: hand-over without the chain (wrong flows)
-    } else if (n_out == FBI_OW) fb_chain_run<FBI_OW>(row, g, sub);
+    if (n_out == FBI_OW) fb_chain_run<FBI_OW>(row, g, sub);
     else {
         for (int i = 0; i < n_out; i++) {                              // the ragged last strip
             const double mnv = row[i + 2 * FBI_M], nxv = row[i];
@@ -1290,7 +1030,11 @@ __device__ __forceinline__ void fb_iter_solve(const FbIterCtx &c, int yo, const 
     *(float2 *)(c.fout + ((off_t)yo * (off_t)c.W + (off_t)(c.x_strip + c.j)) * 8) = f;
 }
 
-template <int K0, int G, int GN, int NB, int ABL, int VS = FBI_VS2>
+// one group of G consecutive window rows s0 .. s0+G-1 with STATIC ring slots K0 .. K0+G-1:
+//   1. evaluate M for NB rows at a time (their loads in flight together), slide the 13-row column sums, park them in LDS,
+//   2. fetch the flow of the next group's GN rows,
+//   3. barrier, the row-sum chains, barrier, the solves of the group's pixels.
+template <int K0, int G, int GN, int NB, int VS = FBI_VS2>
 __device__ __forceinline__ void fb_iter_group_seq(const FbIterCtx &c, int s0, float (&ring)[FBI_WIN][5], double (&S)[5],
                                                   float2 (&fl)[FBI_G], double *vrow)
 {
@@ -1304,13 +1048,12 @@ __device__ __forceinline__ void fb_iter_group_seq(const FbIterCtx &c, int s0, fl
         float m[NB][5];
 #pragma unroll
         for (int r = 0; r < NB; r++)
-            if (g0 + r < G && ABL != 1) fb_taps_load<ABL>(c, s0 + g0 + r, fl[g0 + r], t[r]);
+            if (g0 + r < G) fb_taps_load(c, s0 + g0 + r, fl[g0 + r], t[r]);
 #pragma unroll
         for (int r = 0; r < NB; r++)
             if (g0 + r < G) {
-                const int g = g0 + r, s = s0 + g;
-                if (ABL == 1) { m[r][0] = (float)s; m[r][1] = (float)c.xc; m[r][2] = 1.f; m[r][3] = 2.f; m[r][4] = (float)(s + c.xc); }
-                else fb_taps_eval(c, s, t[r], m[r]);
+                const int g = g0 + r;
+                fb_taps_eval(c, s0 + g, t[r], m[r]);
 #pragma unroll
                 for (int ch = 0; ch < 5; ch++) {
                     S[ch] += (double)(m[r][ch] - ring[K0 + g][ch]); ring[K0 + g][ch] = m[r][ch];
@@ -1318,21 +1061,19 @@ __device__ __forceinline__ void fb_iter_group_seq(const FbIterCtx &c, int s0, fl
                 }
             }
     }
-    if (ABL != 1) {
 #pragma unroll
-        for (int g = 0; g < GN; g++) fl[g] = fb_iter_flow_at(c, s0 + G + g);
-    }
+    for (int g = 0; g < GN; g++) fl[g] = fb_iter_flow_at(c, s0 + G + g);
     __syncthreads();
-    if (chain_lane && !(c.abl & 2)) {                                  // 20 or 25 chains, lanes of the direction's first wave
+    if (chain_lane) {                                                  // 20 or 25 chains, lanes of the workgroup's first wave
         // the chain is the serial stretch of the workgroup -- one wave, bound by its instruction count, everybody else at the
         // barrier -- while the SIMD's other wave (another workgroup's column phase) has work for both issue slots: the
         // chain wave takes priority in the arbitration for its duration (level-0 launch of 21 pairs: 19.7 -> 18.3 ms)
-        if (!(c.abl & 128)) { if (c.abl & 256) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(3); }
+        __builtin_amdgcn_s_setprio(3);
         fb_iter_scan(c, s0 + c.sr - FBI_M, c.sch, vrow + c.j * VS, hand);             // (row r, channel ch) = LDS row r * 5 + ch = j
-        if (!(c.abl & 128)) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     }
     __syncthreads();
-    if (c.j < FBI_OW && c.x_strip + c.j < c.W && !(c.abl & 4)) {
+    if (c.j < FBI_OW && c.x_strip + c.j < c.W) {
 #pragma unroll
         for (int r = 0; r < G; r++) {
             const int yo = s0 + r - FBI_M;
@@ -1408,19 +1149,19 @@ __device__ __forceinline__ void fb_iter_chain_parts(const FbIterCtx &c, int s0, 
     const int jr = c.j - 32;
     const bool chainL = G > 0 && c.j < G * 5 && s0 + c.sr - FBI_M < c.H;
     const bool chainR = PG > 0 && has_prev && jr >= 0 && jr < PG * 5 && s0p + c.rsr - FBI_M < c.H;
-    if ((chainL || chainR) && !(c.abl & 2)) {
-        if (!(c.abl & 128)) __builtin_amdgcn_s_setprio(3);             // (the serial stretch of the workgroup: see fb_iter_group_seq)
+    if (chainL || chainR) {
+        __builtin_amdgcn_s_setprio(3);                                 // (the serial stretch of the workgroup: see fb_iter_group_seq)
         double g, sub, *base;
         if (chainR) { base = Rb + jr * FBI_HR + 1; g = gR; sub = subR; }
         else { base = M + c.j * FBI_HS; fb_chain_enter(c, s0 + c.sr - FBI_M, c.sch, base, hand, g, sub); }
         fb_chain_run_lr(base, g, sub, !chainR);
         if (chainR) fb_hand_store(c, s0p + c.rsr - FBI_M, c.rsch, g, sub);
         else { gmid[c.j] = g; Rb[c.j * FBI_HR] = sub; }                // (the right lanes hold both entries in registers since before the barrier)
-        if (!(c.abl & 128)) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     }
 }
 
-template <int K0, int G, int GN, int NB, int ABL, int PG>
+template <int K0, int G, int GN, int NB, int PG>
 __device__ __forceinline__ void fb_iter_group_half(const FbIterCtx &c, int s0, float (&ring)[FBI_WIN][5], double (&S)[5],
                                                    float2 (&fl)[FBI_G], double *lds, bool has_prev)
 {
@@ -1433,13 +1174,12 @@ __device__ __forceinline__ void fb_iter_group_half(const FbIterCtx &c, int s0, f
         float m[NB][5];
 #pragma unroll
         for (int r = 0; r < NB; r++)
-            if (g0 + r < G && ABL != 1) fb_taps_load<ABL>(c, s0 + g0 + r, fl[g0 + r], t[r]);
+            if (g0 + r < G) fb_taps_load(c, s0 + g0 + r, fl[g0 + r], t[r]);
 #pragma unroll
         for (int r = 0; r < NB; r++)
             if (g0 + r < G) {
-                const int g = g0 + r, s = s0 + g;
-                if (ABL == 1) { m[r][0] = (float)s; m[r][1] = (float)c.xc; m[r][2] = 1.f; m[r][3] = 2.f; m[r][4] = (float)(s + c.xc); }
-                else fb_taps_eval(c, s, t[r], m[r]);
+                const int g = g0 + r;
+                fb_taps_eval(c, s0 + g, t[r], m[r]);
 #pragma unroll
                 for (int ch = 0; ch < 5; ch++) {
                     S[ch] += (double)(m[r][ch] - ring[K0 + g][ch]); ring[K0 + g][ch] = m[r][ch];
@@ -1447,10 +1187,8 @@ __device__ __forceinline__ void fb_iter_group_half(const FbIterCtx &c, int s0, f
                 }
             }
     }
-    if (ABL != 1) {
 #pragma unroll
-        for (int g = 0; g < GN; g++) fl[g] = fb_iter_flow_at(c, s0 + G + g);
-    }
+    for (int g = 0; g < GN; g++) fl[g] = fb_iter_flow_at(c, s0 + G + g);
     double gR, subR;
     fb_right_entry(c, lds, gR, subR);
     __syncthreads();
@@ -1458,7 +1196,7 @@ __device__ __forceinline__ void fb_iter_group_half(const FbIterCtx &c, int s0, f
     __syncthreads();
     const bool in_x = c.x_strip + c.j < c.W;
     if (c.j < FBI_HL) {                                                // first wave: the left-part pixels of this group
-        if (in_x && !(c.abl & 4)) {
+        if (in_x) {
 #pragma unroll
             for (int r = 0; r < G; r++) {
                 const int yo = s0 + r - FBI_M;
@@ -1466,7 +1204,7 @@ __device__ __forceinline__ void fb_iter_group_half(const FbIterCtx &c, int s0, f
             }
         }
     } else {                                                           // second wave: the right-part pixels of the previous group ...
-        if (PG > 0 && has_prev && c.j < FBI_OW && in_x && !(c.abl & 4)) {
+        if (PG > 0 && has_prev && c.j < FBI_OW && in_x) {
 #pragma unroll
             for (int r = 0; r < (PG > 0 ? PG : 1); r++) {
                 const int yo = s0 - PG + r - FBI_M;
@@ -1488,14 +1226,14 @@ __device__ __forceinline__ void fb_iter_group_half(const FbIterCtx &c, int s0, f
     __syncthreads();
 }
 
-// NDW = directions per workgroup: 2 = both directions of a strip share a workgroup (and the R rows they read), 1 = every
-// (strip, direction) is a two-wave workgroup of its own, four per CU (a.nq = 2 then: directions take tickets of their own)
+// One workgroup per (pair, strip, direction): two waves, four workgroups per CU.
 // HP = 1: the chain in two parts one row group apart (full strips; a ragged last strip chains whole, on the same LDS rows)
-template <int NB, int ABL, int NDW, int HP>
-__global__ void __launch_bounds__(NDW * FBI_T, 2)
+#define FBI_LISTS 8                  // ticket lists: one per XCD
+template <int NB, int HP>
+__global__ void __launch_bounds__(FBI_T, 2)
 k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
 {
-    __shared__ double vrow_all[NDW][HP ? FBI_HP_DOUBLES : FBI_G * 5 * FBI_VS2];
+    __shared__ double vrow[HP ? FBI_HP_DOUBLES : FBI_G * 5 * FBI_VS2];
     // TICKETS, ONE LIST PER XCD.  Pair b belongs to the list of XCD b mod 8 -- with all its strips, both directions and all
     // column groups -- and a workgroup takes the next item of ITS XCD's list (s_getreg XCC_ID): the two directions of a
     // strip, which read each other's expansion rows, then run on the same XCD within microseconds and share them in its
@@ -1506,38 +1244,38 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
     // is running or done whichever XCD it came from -- no deadlock whatever the dispatch order.
     __shared__ int s_ticket[2];
     if (threadIdx.x == 0) {
-        const int xcc = a.xcd_lists ? (int)(__builtin_amdgcn_s_getreg(6164) & 7u) : 0;      // HW_REG_XCC_ID (id 20), bits 3:0
-        const int n_lists = a.xcd_lists ? 8 : 1;
+        const int xcc = (int)(__builtin_amdgcn_s_getreg(6164) & 7u);  // HW_REG_XCC_ID (id 20), bits 3:0
         int found = -1, y = 0;
-        for (int k = 0; k < n_lists && found < 0; k++) {
-            y = (xcc + k) & (n_lists - 1);
-            const int n_pairs = a.nb > y ? (a.nb - y + n_lists - 1) / n_lists : 0;
+        for (int k = 0; k < FBI_LISTS && found < 0; k++) {
+            y = (xcc + k) & (FBI_LISTS - 1);
+            const int n_pairs = a.nb > y ? (a.nb - y + FBI_LISTS - 1) / FBI_LISTS : 0;
             if (n_pairs == 0) continue;
             const int t = atomicAdd(a.ticket + y, 1);
-            if (t < n_pairs * a.nx * a.nq) found = t;                  // (the grid has exactly one workgroup per item: some list has one left)
+            if (t < n_pairs * a.nx * a.nd) found = t;                  // (the grid has exactly one workgroup per item: some list has one left)
         }
         s_ticket[0] = found; s_ticket[1] = y;
     }
     __syncthreads();
     const int ticket = __builtin_amdgcn_readfirstlane(s_ticket[0]), list = __builtin_amdgcn_readfirstlane(s_ticket[1]);
     if (ticket < 0) return;                                            // (cannot happen: more workgroups than items)
-    const int n_lists = a.xcd_lists ? 8 : 1, list_pairs = (a.nb - list + n_lists - 1) / n_lists;
-    const int qw = __builtin_amdgcn_readfirstlane(threadIdx.x / FBI_T); // wave-uniform: which half of the workgroup (0 when it has one direction)
-    double *vrow = vrow_all[qw];
-    // ticket -> (pair, strip): column groups of nxg strips, group by group; inside a group pair by pair, strips left to right
-    // (a strip's left neighbour always holds a lower ticket).  A launch that needs several rounds of resident workgroups
-    // runs one column group per round: the start delays below then add up over nxg strips, not over all of them.
-    const int per_group = list_pairs * a.nxg * a.nq;
+    const int list_pairs = (a.nb - list + FBI_LISTS - 1) / FBI_LISTS;
+    // ticket -> (pair, strip, direction): column groups of nxg strips, group by group; inside a group pair by pair, strips left
+    // to right, the directions of a strip one after the other (a strip's left neighbour always holds a lower ticket).  A launch
+    // that needs several rounds of resident workgroups runs one column group per round: the skew of the strips' pipeline then
+    // adds up over nxg strips, not over all of them.
+    const int per_group = list_pairs * a.nxg * a.nd;
     const int cg = ticket / per_group, tr = ticket - cg * per_group, n_cg = min(a.nxg, a.nx - cg * a.nxg);
-    const int bi = tr / (n_cg * a.nq), tr2 = tr - bi * n_cg * a.nq, sxl = tr2 / a.nq;
-    const int b = list + n_lists * bi;
+    const int bi = tr / (n_cg * a.nd), tr2 = tr - bi * n_cg * a.nd, sxl = tr2 / a.nd;
+    const int b = list + FBI_LISTS * bi;
     const int sx = cg * a.nxg + sxl;
-    const int q = NDW == 2 ? qw : tr2 - sxl * a.nq;                    // index into the launch's directions
+    const int q = tr2 - sxl * a.nd;                                    // index into the launch's directions
     const int d = a.dir[q];                                            // 0: prev -> next, 1: next -> prev
     FbIterCtx c;
     const float *R0 = a.R[d] + b * a.bs_R, *R1 = a.R[1 - d] + b * a.bs_R;
     c.R0 = (const char *)R0; c.R0e = (const char *)(R0 + 4 * plane);
     {
+        // corner displacements in elements; a level narrower / shorter than two pixels has no in-image patch at all
+        // (inb is never true): all four corners then alias element 0 so that the discarded reads stay in bounds
         const bool patch = W >= 2 && H >= 2;
         const int64_t dcorner[4] = {0, patch ? 1 : 0, patch ? W : 0, patch ? (int64_t)W + 1 : 0};
 #pragma unroll
@@ -1548,12 +1286,11 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
     }
     c.fin = (const char *)(a.fin[q] + b * a.bs_fin[q]); c.fout = (char *)(a.fout[q] + b * a.bs_fout[q]);
     c.H = H; c.W = W;
-    c.j = threadIdx.x - qw * FBI_T;
-    c.dj = c.j; c.tg = 0; c.tq = 0;
+    c.j = threadIdx.x;
     c.sr = c.j / 5; c.sch = c.j - c.sr * 5;
     c.rsr = c.j >= 32 ? (c.j - 32) / 5 : 0; c.rsch = c.j >= 32 ? (c.j - 32) - c.rsr * 5 : 0;
     c.full = W - sx * FBI_OW >= FBI_OW;
-    c.sx = sx; c.nx = a.nx; c.epoch = a.epoch; c.abl = a.abl; c.spins = (a.abl & 8) ? a.ticket - 16 * (a.epoch - 1) + FBI_HDR / 4 - 4 : nullptr;
+    c.sx = sx; c.nx = a.nx; c.epoch = a.epoch; c.starve = a.starve;
     c.starved = a.starved; c.poll_limit = a.poll_limit;
     {
         // hand-over slots of (pair b, direction q, strip): [q][strip 0 .. nx - 2][row][FBI_HW words]
@@ -1563,8 +1300,6 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
     }
     c.x_strip = sx * FBI_OW;
     c.xc = tf_clampi(c.x_strip + c.j - FBI_M, 0, W - 1);              // column this thread evaluates M for (replicate border)
-    c.y0 = 0;
-    c.y1 = H;
     {
         const float border[5] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f};
         const int xb = W - 1 - c.xc;
@@ -1579,21 +1314,21 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
     double S[5];
     float2 fl[FBI_G];
     {
-        // rows 0 .. m-1 -> ring slots m+1 .. 2m; slots 0 .. m+1 hold row 0 (as in k_fb_iter_tree)
+        // rows 0 .. m-1 -> ring slots m+1 .. 2m; slots 0 .. m+1 hold row 0 (OpenCV's max(y - m - 1, 0) for the rows above the
+        // image); three rows at a time (their loads in flight together, few registers live next to the ring)
 #pragma unroll
         for (int r0 = 0; r0 < FBI_M; r0 += 3) {
             float2 f0[3];
             FbTaps t[3];
             float mm[3][5];
 #pragma unroll
-            for (int r = 0; r < 3; r++) f0[r] = (ABL != 1) ? fb_iter_flow_at(c, r0 + r) : make_float2(0.f, 0.f);
+            for (int r = 0; r < 3; r++) f0[r] = fb_iter_flow_at(c, r0 + r);
 #pragma unroll
-            for (int r = 0; r < 3; r++) if (ABL != 1) fb_taps_load<ABL>(c, r0 + r, f0[r], t[r]);
+            for (int r = 0; r < 3; r++) fb_taps_load(c, r0 + r, f0[r], t[r]);
 #pragma unroll
             for (int r = 0; r < 3; r++) {
                 const int row = r0 + r;
-                if (ABL == 1) { mm[r][0] = (float)row; mm[r][1] = (float)c.xc; mm[r][2] = 1.f; mm[r][3] = 2.f; mm[r][4] = (float)(row + c.xc); }
-                else fb_taps_eval(c, row, t[r], mm[r]);
+                fb_taps_eval(c, row, t[r], mm[r]);
 #pragma unroll
                 for (int ch = 0; ch < 5; ch++) {
                     if (row == 0) {
@@ -1608,27 +1343,16 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
             }
         }
     }
+    // row s enters ring slot (s - m) mod 13, which holds row s - 13 = (output row) - m - 1: OpenCV's srow0.
+    // rows past s_last (window rows needed, inclusive; clamped to H - 1) are evaluated (harmless) but never produce output
     const int s_last = H - 1 + FBI_M;
 #pragma unroll
-    for (int g = 0; g < FBI_G; g++) fl[g] = (ABL != 1) ? fb_iter_flow_at(c, FBI_M + g) : make_float2(0.f, 0.f);
-    if (sx > 0 && a.slack_rows > 0 && !(a.abl & 1)) {
-        // SLACK.  Strips that start together run in lockstep: each finds its left neighbour's words missing at every row
-        // group, polls, and passes every hiccup on to all strips right of it (measured: 55 % of the chains waited, the launch
-        // took 1.5 x the time of its parts).  So a strip starts only when its left neighbour is slack_rows ahead: the
-        // words are then there when the row group asks for them, and a neighbour's hiccup is absorbed by the lead.
-        if (threadIdx.x == 0) {
-            const unsigned long long *p = c.hin + (int64_t)min(a.slack_rows, H - 1) * 5;
-            // (a wait that gives up here is not an error: the slack is a scheduling hint, every chain below still enters through
-            // fb_chain_enter, which is where a missing word is polled for and -- if it never comes -- reported)
-            for (int spin = 0; spin < a.poll_limit && (unsigned)(fb_hand_ld(p) >> 32) != a.epoch; spin++) __builtin_amdgcn_s_sleep(8);
-        }
-        __syncthreads();
-    }
+    for (int g = 0; g < FBI_G; g++) fl[g] = fb_iter_flow_at(c, FBI_M + g);
     if (HP && c.full) {
         for (int base = FBI_M; base <= s_last; base += FBI_WIN) {
-            fb_iter_group_half<0, 4, 4, NB, ABL, 5>(c, base, ring, S, fl, vrow, base > FBI_M);
-            fb_iter_group_half<4, 4, 5, NB, ABL, 4>(c, base + 4, ring, S, fl, vrow, true);
-            fb_iter_group_half<8, 5, 4, NB, ABL, 4>(c, base + 8, ring, S, fl, vrow, true);
+            fb_iter_group_half<0, 4, 4, NB, 5>(c, base, ring, S, fl, vrow, base > FBI_M);
+            fb_iter_group_half<4, 4, 5, NB, 4>(c, base + 4, ring, S, fl, vrow, true);
+            fb_iter_group_half<8, 5, 4, NB, 4>(c, base + 8, ring, S, fl, vrow, true);
         }
         // flush: the right part of the last group (its rows past H - 1 produce nothing)
         const int s0p = FBI_M + ((s_last - FBI_M) / FBI_WIN) * FBI_WIN + 8;
@@ -1637,7 +1361,7 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
         fb_right_entry(c, vrow, gR, subR);                              // (no left part in the flush: nobody writes these entries)
         fb_iter_chain_parts<0, 5>(c, s0p + 5, s0p, true, none, vrow, gR, subR);
         __syncthreads();
-        if (c.j >= FBI_HL && c.j < FBI_OW && c.x_strip + c.j < c.W && !(c.abl & 4)) {
+        if (c.j >= FBI_HL && c.j < FBI_OW && c.x_strip + c.j < c.W) {
 #pragma unroll
             for (int r = 0; r < 5; r++) {
                 const int yo = s0p + r - FBI_M;
@@ -1647,9 +1371,9 @@ k_fb_iter(FbIterArgs a, int H, int W, int64_t plane)
         return;
     }
     for (int base = FBI_M; base <= s_last; base += FBI_WIN) {
-        fb_iter_group_seq<0, 4, 4, NB, ABL, (HP ? FBI_HS : FBI_VS2)>(c, base, ring, S, fl, vrow);
-        fb_iter_group_seq<4, 4, 5, NB, ABL, (HP ? FBI_HS : FBI_VS2)>(c, base + 4, ring, S, fl, vrow);
-        fb_iter_group_seq<8, 5, 4, NB, ABL, (HP ? FBI_HS : FBI_VS2)>(c, base + 8, ring, S, fl, vrow);
+        fb_iter_group_seq<0, 4, 4, NB, (HP ? FBI_HS : FBI_VS2)>(c, base, ring, S, fl, vrow);
+        fb_iter_group_seq<4, 4, 5, NB, (HP ? FBI_HS : FBI_VS2)>(c, base + 4, ring, S, fl, vrow);
+        fb_iter_group_seq<8, 5, 4, NB, (HP ? FBI_HS : FBI_VS2)>(c, base + 8, ring, S, fl, vrow);
     }
 }
 
@@ -1801,7 +1525,8 @@ static void fb_phase_sizes(int H, int W, const tf_farneback_params *p, int k_hi,
     for (int k = k_lo; k <= k_hi; k++) {
         int h, w; fb_level_size(H, W, p, k, &h, &w);
         pl = std::max(pl, (size_t)h * w);
-        // the two-pass blur of a full-size level keeps a whole image (+ rows), the sampled blur H rows of w float2
+        // a full-size level: a whole image (+ rows; what a two-pass blur needs -- the size workspaces and batch hints have been
+        // computed from), the sampled blur H rows of w float2
         t = std::max(t, k == 0 ? (size_t)H * W + 2 * (size_t)H + 64 : std::max((size_t)H * W / 4 + 2 * (size_t)H + 64, 2 * (size_t)H * w + 64));
         t = std::max(t, fb_hand_floats(h, w));
     }
@@ -1948,6 +1673,14 @@ extern "C" int tf_farneback_debug_set_starved_slot(int slot)
     return TF_OK;
 }
 extern "C" int tf_farneback_debug_set_starved(void) { return tf_farneback_debug_set_starved_slot(0); }
+// (test hook for the device side: TF_FBI_TEST_STARVE=<polls> in the environment -- the strips never store their hand-over
+// words and a chain gives up after <polls> polls, so every chain right of strip 0 starves and the call must end in TF_ESTARVED;
+// read once per process.  -1: not set)
+static int fb_test_starve_polls()
+{
+    static const int v = getenv("TF_FBI_TEST_STARVE") ? atoi(getenv("TF_FBI_TEST_STARVE")) : -1;
+    return v;
+}
 
 // Workgroups of the iteration kernel's full-resolution launch for B pairs (both directions), and how many of them the
 // device holds at once: a launch costs whole rounds of resident workgroups, so a caller that may cut a batch into parts
@@ -2013,7 +1746,6 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
     for (int d = 0; d < 2; d++) { slot[d][0] = out[d]; slot_bs[d][0] = flow_stride; slot[d][1] = S.fbuf[d]; slot_bs[d][1] = S.bs_f; }
     int pw = *pw_io, ph = *ph_io;
     const dim3 block(64, 4);
-    const dim3 gfull((W + 63) / 64, (H + 3) / 4, B);
     const bool fused = p->win_size == FBI_WIN;
     for (int k = k_hi; k >= k_lo; k--) {
         double scale = 1; for (int i = 0; i < k; i++) scale *= p->pyr_scale;
@@ -2030,21 +1762,16 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
             const int irx = (int)(rsx + 0.5), iry = (int)(rsy + 0.5);
             const bool same = (w == W && h == H);
             const bool area2 = !same && fabs(rsx - irx) < DBL_EPSILON && fabs(rsy - iry) < DBL_EPSILON && irx == 2 && iry == 2;
-            static const bool two_pass = getenv("TF_FB_BLUR_TWOPASS") != nullptr;            // development aid
-            if (area2 && hk.ksize == 3 && !two_pass && W >= 2 && H >= 2 && 2 * w <= W && 2 * h <= H) {
+            if (area2 && hk.ksize == 3 && W >= 2 && H >= 2 && 2 * w <= W && 2 * h <= H) {
                 TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 4.0 * plane) * B, s);                   // u8 r + quarter-size f32 w
                 hipLaunchKernelGGL(k_fb_blur3_area2<uint8_t>, glev, block, 0, s, img[i], H, W, hk, I, h, w, img_stride, bs_n);
                 Ik = I;
             } else if (same || area2) {
+                // levels are at least 32 px (fb_levels), so the scale here is within 1/64 of 1 or of 0.5: sigma <= 0.53, 3 taps
+                TF_REQUIRE(hk.ksize == 3, "tf_farneback: full-size or exact-2x level with a blur longer than 3 taps");
                 {
-                    if (hk.ksize == 3 && !two_pass) {
-                        TfProfScope ps(TFK_FB_BLUR, 5.0 * n * B, s);  // u8 r + f32 w
-                        hipLaunchKernelGGL(k_fb_blur3_fused<uint8_t>, dim3((W + 255) / 256, (H + 3) / 4, B), block, 0, s, img[i], H, W, hk, blur, img_stride, bs_n);
-                    } else {
-                        TfProfScope ps(TFK_FB_BLUR, 13.0 * n * B, s); // u8 r + f32 w, then f32 r + f32 w
-                        hipLaunchKernelGGL(k_fb_blur_rows<uint8_t>, gfull, block, 0, s, img[i], H, W, hk, tmp, img_stride, bs_tmp);
-                        hipLaunchKernelGGL(k_fb_blur_cols, gfull, block, 0, s, tmp, H, W, hk, blur, bs_tmp, bs_n);
-                    }
+                    TfProfScope ps(TFK_FB_BLUR, 5.0 * n * B, s);      // u8 r + f32 w
+                    hipLaunchKernelGGL(k_fb_blur3_fused<uint8_t>, dim3((W + 255) / 256, (H + 3) / 4, B), block, 0, s, img[i], H, W, hk, blur, img_stride, bs_n);
                 }
                 if (area2) {
                     TfProfScope ps(TFK_FB_RESIZE, (4.0 * n + 4.0 * plane) * B, s);
@@ -2056,17 +1783,15 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
                 TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 8.0 * (double)H * w * 2 + 4.0 * plane) * B, s);
                 FbResizeGeom rg; rg.sh = H; rg.sw = W; rg.dh = h; rg.dw = w; rg.scale_x = rsx; rg.scale_y = rsy;
                 // LDS-staged form when a workgroup's source segment fits (64 outputs * stride + ksize bytes per row)
-                static const bool no_lds = getenv("TF_FB_BLUR_NO_LDS") != nullptr;                 // development aid
                 const int64_t seg = (int64_t)(64 * rsx) + hk.ksize + 8;
                 // (measured at 5424^2, 8 images: stride 32 / 16: 958 -> 282 / 554 -> 322 us; stride 8 / 4: 355 -> 415 / 380 -> 673 us --
                 // short kernels gain nothing from staging and pay for the barrier: LDS form from stride 12 on)
-                if (!no_lds && hk.ksize > 5 && rsx >= 12. && seg <= FBL_ROW_BYTES && W >= hk.ksize) {
+                if (hk.ksize > 5 && rsx >= 12. && seg <= FBL_ROW_BYTES && W >= hk.ksize) {
                     int unit_shift = 2;                                 // pad unit = largest power of two <= stride, >= 8 bytes;
                     while ((2 << unit_shift) <= (int)rsx) unit_shift++; // unit 4 (shift 2) would pad every word: then no padding
                     if (unit_shift < 3) unit_shift = 30;
-                    static const int word_env = getenv("TF_FB_BLUR_BYTES") ? 0 : 1;                // development aid: byte reads
                     hipLaunchKernelGGL(k_fb_blur_rows_sampled_lds, dim3((w + 63) / 64, (H + 3) / 4, B), block, 0, s, img[i], rg, hk,
-                                       (float2 *)tmp, img_stride, bs_tmp / 2, unit_shift, word_env);
+                                       (float2 *)tmp, img_stride, bs_tmp / 2, unit_shift);
                 } else
                     hipLaunchKernelGGL(k_fb_blur_rows_sampled<uint8_t>, dim3((w + 63) / 64, (H + 3) / 4, B), block, 0, s, img[i], rg, hk,
                                        (float2 *)tmp, img_stride, bs_tmp / 2);
@@ -2108,55 +1833,38 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
         if (fused) {
             // whole columns per workgroup (k_fb_iter): parallelism = strips x directions x pairs
             const int nx = (w + FBI_OW - 1) / FBI_OW;
-            const dim3 gi((unsigned)(nx * B), 1, 1), bi(FBI_T * nd);
             FbIterArgs ia;
             ia.R[0] = R[0]; ia.R[1] = R[1]; ia.bs_R = bs_R; ia.nd = nd; ia.nx = nx;
-            // development switch: TF_FB_ROW_SUMS_TREE=1 -> the round-3 kernel (window sums as a tree: within 1e-4 px of OpenCV's order, not identical)
-            static const bool tree = getenv("TF_FB_ROW_SUMS_TREE") != nullptr;
-            // TF_FBI_TWO_PART_CHAIN=1: the chain in two parts one row group apart (HP form; same flows).  Alone on the GPU it is the
-            // faster form (level-0 launch of 21 pairs: 18.0 against 19.7 ms); it is NOT the default because its 39 KB of LDS per
-            // workgroup fill the CU (4 x 39 = 156 of 160 KB): in the pipelined benchmark the floods of the finished windows run
-            // beside the flow in what the one-lane form leaves free (4 x 27 KB), and with the two-part form they displace
-            // iteration workgroups instead -- the kernel then reads 1 985 against 1 860 ms per config-F step, the step is the same
-            // (4.75 s either way, back to back on one box)
-            // (tf_farneback_params.chain_form: PER CALL -- the host layer asks for the two-part form when nothing is going to run
-            // beside this call's flow; a process-wide switch, as in round 4, let one thread's plain create_flow turn it on under
-            // another thread's pipelined one)
-            static const char *chain_env = getenv("TF_FBI_TWO_PART_CHAIN");
-            const bool whole_chain = chain_env ? atoi(chain_env) == 0 : p->chain_form != TF_FB_CHAIN_TWO_PART;
+            // The chain in two parts one row group apart (HP form; same flows) is the faster form alone on the GPU (level-0
+            // launch of 21 pairs: 18.0 against 19.7 ms), but its 39 KB of LDS per workgroup fill the CU (4 x 39 = 156 of
+            // 160 KB): in the pipelined benchmark the floods of the finished windows run beside the flow in what the one-lane
+            // form leaves free (4 x 27 KB), and with the two-part form they displace iteration workgroups instead -- the kernel
+            // then reads 1 985 against 1 860 ms per config-F step, the step is the same (4.75 s either way, back to back on one
+            // box).  So it is chosen PER CALL (tf_farneback_params.chain_form): the host layer asks for the two-part form when
+            // nothing is going to run beside this call's flow; a process-wide switch, as in round 4, let one thread's plain
+            // create_flow turn it on under another thread's pipelined one.
+            const bool whole_chain = p->chain_form != TF_FB_CHAIN_TWO_PART;
             // sequential row sums: the strips' hand-over words and the launches' ticket counters live in the blur scratch,
             // idle from the polynomial expansion of this level to the blur of the next: [1 KB of counters][words] per pair
             const size_t hand_words = (size_t)nd * (size_t)(nx - 1) * (size_t)h * FBI_HW;
-            static const int seq_abl = getenv("TF_FBI_SEQ_ABLATE") ? atoi(getenv("TF_FBI_SEQ_ABLATE")) : 0;
-            ia.abl = seq_abl;
             {
-                // column groups: one per round of resident workgroups (two 4-wave workgroups per CU)
-                const int slots = fb_resident_slots();                       // resident two-wave workgroups (one direction each) of THIS device
-                // one direction per workgroup (four two-wave workgroups per CU) unless TF_FBI_JOIN_DIRECTIONS=1: the chains make a
-                // workgroup latency-bound for a third of its time, and four independent workgroups per CU overlap those
-                // stretches better than two (config F: 2.05 s of k_fb_iter per step against 2.25 s), at the price of reading the
-                // R rows once per direction again (round 3 joined the directions for that: -23 % HBM bytes, same time)
-                static const bool join_env = getenv("TF_FBI_JOIN_DIRECTIONS") != nullptr;
-                ia.nq = (!join_env && nd == 2) ? 2 : 1;
-                static const bool one_list_env = getenv("TF_FBI_ONE_TICKET_LIST") != nullptr;
-                ia.xcd_lists = one_list_env ? 0 : 1;
-                const int rounds = (int)(((int64_t)nx * B * 2 + slots - 1) / slots);   // (a joined workgroup counts as two)
-                static const int slack_env = getenv("TF_FBI_SLACK_ROWS") ? atoi(getenv("TF_FBI_SLACK_ROWS")) : -1;
-                static const int groups_env = getenv("TF_FBI_COLUMN_GROUPS") ? atoi(getenv("TF_FBI_COLUMN_GROUPS")) : 0;
-                const int n_groups = groups_env > 0 ? std::min(groups_env, nx) : std::min(rounds, nx);
-                ia.nb = B; ia.nxg = (nx + n_groups - 1) / n_groups; ia.slack_rows = slack_env >= 0 ? slack_env : 0;
+                // column groups: one per round of resident workgroups (four two-wave workgroups per CU, one direction each)
+                const int slots = fb_resident_slots();                       // of THIS device
+                const int rounds = (int)(((int64_t)nx * B * 2 + slots - 1) / slots);
+                const int n_groups = std::min(rounds, nx);
+                ia.nb = B; ia.nxg = (nx + n_groups - 1) / n_groups;
             }
             ia.hand = (unsigned long long *)((char *)tmp + FBI_HDR); ia.bs_hand = bs_tmp / 2; ia.ticket = (int *)tmp; ia.epoch = 0;
-            static const int poll_env = getenv("TF_FBI_POLL_LIMIT") ? atoi(getenv("TF_FBI_POLL_LIMIT")) : -1;
-            ia.poll_limit = poll_env >= 0 ? poll_env : (1 << 22);
-            ia.starved = tree ? nullptr : fb_starved_word(true, p->status_slot);
-            if (!tree && !ia.starved) { tf_set_error("tf_farneback: no pinned status word for the iteration kernel (hipHostMalloc failed)"); return TF_EHIP; }
-            if (!tree) {
-                TF_REQUIRE(FBI_HDR + hand_words * 8 <= (size_t)bs_tmp * sizeof(float), "tf_farneback: blur scratch too small for the strips' hand-over words");
-                TF_REQUIRE(p->num_iters <= 250, "tf_farneback: more than 250 iterations per level");
-                TF_CHECK_HIP(hipMemsetAsync(tmp, 0, FBI_HDR, s));
-                for (int b = 0; b < B && hand_words > 0; b++) TF_CHECK_HIP(hipMemsetAsync((char *)(tmp + (int64_t)b * bs_tmp) + FBI_HDR, 0, hand_words * 8, s));
-            }
+            const int starve_polls = fb_test_starve_polls();
+            ia.starve = starve_polls >= 0;
+            ia.poll_limit = ia.starve ? starve_polls : (1 << 22);
+            ia.starved = fb_starved_word(true, p->status_slot);
+            if (!ia.starved) { tf_set_error("tf_farneback: no pinned status word for the iteration kernel (hipHostMalloc failed)"); return TF_EHIP; }
+            TF_REQUIRE(FBI_HDR + hand_words * 8 <= (size_t)bs_tmp * sizeof(float), "tf_farneback: blur scratch too small for the strips' hand-over words");
+            TF_REQUIRE(p->num_iters <= 250, "tf_farneback: more than 250 iterations per level");
+            TF_CHECK_HIP(hipMemsetAsync(tmp, 0, FBI_HDR, s));
+            for (int b = 0; b < B && hand_words > 0; b++) TF_CHECK_HIP(hipMemsetAsync((char *)(tmp + (int64_t)b * bs_tmp) + FBI_HDR, 0, hand_words * 8, s));
+            const dim3 gi((unsigned)(nx * B * nd));
             for (int it = 0; it < p->num_iters; it++) {
                 for (int q = 0; q < nd; q++) {
                     const int d = dirs[q];
@@ -2166,32 +1874,13 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
                 }
                 {
                     TfProfScope ps(TFK_FB_ITER, 56.0 * plane * nd * B, s);
-                    static const int abl = getenv("TF_FBI_ABLATE") ? atoi(getenv("TF_FBI_ABLATE")) : 0;
                     ia.epoch = (unsigned)(it + 1); ia.ticket = (int *)tmp + 16 * it;
-                    if (tree) {
-                        if (abl == 1) hipLaunchKernelGGL((k_fb_iter_tree<FBI_NB, 1>), gi, bi, 0, s, ia, h, w, plane);
-                        else if (abl == 2) hipLaunchKernelGGL((k_fb_iter_tree<FBI_NB, 2>), gi, bi, 0, s, ia, h, w, plane);
-                        else hipLaunchKernelGGL((k_fb_iter_tree<FBI_NB, 0>), gi, bi, 0, s, ia, h, w, plane);
-                    } else if (abl == 1) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 1, 2, 0>), gi, bi, 0, s, ia, h, w, plane);
-                    else if (abl == 2) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 2, 2, 0>), gi, bi, 0, s, ia, h, w, plane);
-                    else if (whole_chain) {
-                        if (ia.nq == 2) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0, 1, 0>), dim3(gi.x * 2), dim3(FBI_T), 0, s, ia, h, w, plane);
-                        else if (nd == 1) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0, 1, 0>), gi, bi, 0, s, ia, h, w, plane);
-                        else hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0, 2, 0>), gi, bi, 0, s, ia, h, w, plane);
-                    } else if (ia.nq == 2) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0, 1, 1>), dim3(gi.x * 2), dim3(FBI_T), 0, s, ia, h, w, plane);
-                    else if (nd == 1) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0, 1, 1>), gi, bi, 0, s, ia, h, w, plane);
-                    else hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0, 2, 1>), gi, bi, 0, s, ia, h, w, plane);
+                    if (whole_chain) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0>), gi, dim3(FBI_T), 0, s, ia, h, w, plane);
+                    else hipLaunchKernelGGL((k_fb_iter<FBI_NB, 1>), gi, dim3(FBI_T), 0, s, ia, h, w, plane);
                 }
                 for (int q = 0; q < nd; q++) cur[dirs[q]] = 1 - cur[dirs[q]];
             }
             TF_CHECK_LAUNCH();
-            if (!tree && (seq_abl & 8)) {                               // development aid: how often did a chain have to wait?
-                int h_sp[2] = {0, 0};
-                TF_CHECK_HIP(hipMemcpyAsync(h_sp, (int *)tmp + FBI_HDR / 4 - 4, sizeof(h_sp), hipMemcpyDeviceToHost, s));
-                TF_CHECK_HIP(hipStreamSynchronize(s));
-                fprintf(stderr, "k_fb_iter %d x %d, %d pairs, %d launches: %d chains waited (of %lld), %d polls\n", h, w, B, p->num_iters, h_sp[0],
-                        (long long)B * nd * (nx - 1) * h * 5 * p->num_iters, h_sp[1]);
-            }
         } else {
             // generic window size: separate UpdateMatrices / box-filter+solve kernels, one pair at a time, in place
             const dim3 glev1((w + 63) / 64, (h + 3) / 4, 1);

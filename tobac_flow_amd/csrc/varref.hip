@@ -22,8 +22,6 @@
 // HBM layout (planar, per flow direction): D1 = float4 {Ix, Iy, Ixz, Iyz}, D2 = float4 {Ixx, Ixy, Iyy, Iz},
 // S = float4 {A11, A22, b1, b2}, A12 float, wt float, W float2 (the input flow), dW float2.
 #include "tf_common.h"
-#include <stdlib.h>
-#include <string.h>
 
 struct VrP { float alpha2, delta2, gamma2, omega, zeta2, eps2; };
 // strides between the images of a batch (tf_varref_batch; all zero-cost for one image): frames in pixels, the caller's flow
@@ -182,41 +180,25 @@ template <bool FAST> __device__ __forceinline__ float vr_over_sqrt(float a, floa
 
 __device__ __forceinline__ float2 vr_add2(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 
-__global__ void __launch_bounds__(256)
-k_vr_weights(const float2 *__restrict__ Wf, const float2 *__restrict__ dW, int H, int W, VrP P, float *__restrict__ wt)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    const int64_t j = (int64_t)y * W + x;
-    const int64_t jr = x + 1 < W ? j + 1 : j, jd = y + 1 < H ? j + W : j;
-    const float2 z = make_float2(0.f, 0.f);                            // dW == nullptr: the first iteration's dW = 0
-    const float2 w0 = Wf[j], d0 = dW ? dW[j] : z, wr = Wf[jr], dr = dW ? dW[jr] : z, wd = Wf[jd], dd = dW ? dW[jd] : z;
-    wt[j] = vr_weight(vr_add2(w0, d0), vr_add2(wr, dr), vr_add2(wd, dd), P);
-}
-
-// WEIGHTS = true: the smoothness weights are formed here instead of in a k_vr_weights pass (same expression, so the same
-// bits): every thread computes the weight of ITS pixel (written to `wt` for the SOR kernel), the left neighbour's weight
-// comes from the neighbouring lane (lane 0 computes it itself), the upper neighbour's from the wave above through LDS
-// (the first wave of the 64 x 4 block computes the row above itself): 1.27 weights per pixel instead of a pass of
-// 16 B read + 4 B written and a 4 B read here.
-template <bool WEIGHTS, bool FAST = false>
+// The smoothness weights are formed here rather than in a pass of their own (16 B read + 4 B written, and a 4 B read here):
+// every thread computes the weight of ITS pixel (written to `wt` for the SOR kernel), the left neighbour's weight comes
+// from the neighbouring lane (lane 0 computes it itself), the upper neighbour's from the wave above through LDS (the first
+// wave of the 64 x 4 block computes the row above itself): 1.27 weights per pixel, each the same expression (vr_weight).
+template <bool FAST = false>
 __global__ void __launch_bounds__(256)
 k_vr_system(const float4 *__restrict__ D1, const float4 *__restrict__ D2, const float2 *__restrict__ Wf,
-            const float2 *__restrict__ dW, const float *wt_in, int H, int W, VrP P,
-            float4 *__restrict__ S, float *__restrict__ A12o, float *wt_out, VrB bs)
+            const float2 *__restrict__ dW, int H, int W, VrP P, float4 *__restrict__ S, float *__restrict__ A12o,
+            float *__restrict__ wt, VrB bs)
 {
     __shared__ float s_w[4][64];
     {
         const int64_t b = blockIdx.z;
-        D1 += b * bs.plane; D2 += b * bs.plane; Wf += b * bs.flow; S += b * bs.plane; A12o += b * bs.plane;
+        D1 += b * bs.plane; D2 += b * bs.plane; Wf += b * bs.flow; S += b * bs.plane; A12o += b * bs.plane; wt += b * bs.plane;
         if (dW) dW += b * bs.plane;
-        if (wt_in) wt_in += b * bs.plane;
-        if (wt_out) wt_out += b * bs.plane;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + wv;
     const bool in = x < W && y < H;
-    if (!WEIGHTS && !in) return;
     const int64_t j = in ? (int64_t)y * W + x : 0;
     const float2 z2 = make_float2(0.f, 0.f);
     const bool has_r = x + 1 < W, has_l = x > 0, has_d = y + 1 < H, has_u = y > 0;
@@ -229,35 +211,28 @@ k_vr_system(const float4 *__restrict__ D1, const float4 *__restrict__ D2, const 
     const int64_t jdl = (in && has_l && has_d) ? j + W - 1 : jl, jur = (in && has_u && has_r) ? j - W + 1 : ju;
     const float4 d1 = D1[j], d2 = D2[j];
     const float2 w0 = Wf[j], wr = Wf[jr], wlf = Wf[jl], wd = Wf[jd], wuf = Wf[ju];
-    float2 d = z2, dr = z2, dd = z2, dl = z2, ddl = z2, dup = z2, dur = z2, wdl = z2, wur = z2;
-    if (dW) { d = dW[j]; if (WEIGHTS) { dr = dW[jr]; dd = dW[jd]; dl = dW[jl]; ddl = dW[jdl]; } }
-    if (WEIGHTS) {
-        wdl = Wf[jdl];
-        if (wv == 0) { wur = Wf[jur]; if (dW) { dup = dW[ju]; dur = dW[jur]; } }
+    float2 d = z2, dr = z2, dd = z2, dl = z2, ddl = z2, dup = z2, dur = z2, wur = z2;
+    if (dW) { d = dW[j]; dr = dW[jr]; dd = dW[jd]; dl = dW[jl]; ddl = dW[jdl]; }
+    const float2 wdl = Wf[jdl];
+    if (wv == 0) { wur = Wf[jur]; if (dW) { dup = dW[ju]; dur = dW[jur]; } }
+    const float2 cO = vr_add2(w0, d);
+    const float wp = vr_weight<FAST>(cO, vr_add2(wr, dr), vr_add2(wd, dd), P);      // missing neighbour = the pixel itself
+    if (in) wt[j] = wp;
+    s_w[wv][lane] = wp;
+    float wl = __shfl_up(wp, 1);
+    if (lane == 0 && in && has_l) {
+        // weight of (x - 1, y): its right neighbour is this pixel, its lower one (x - 1, y + 1) or itself
+        wl = vr_weight<FAST>(vr_add2(wlf, dl), cO, vr_add2(wdl, ddl), P);
     }
-    float wp, wl, wu;
-    if (WEIGHTS) {
-        const float2 cO = vr_add2(w0, d);
-        wp = vr_weight<FAST>(cO, vr_add2(wr, dr), vr_add2(wd, dd), P);      // missing neighbour = the pixel itself
-        if (in) wt_out[j] = wp;
-        s_w[wv][lane] = wp;
-        wl = __shfl_up(wp, 1);
-        if (lane == 0 && in && has_l) {
-            // weight of (x - 1, y): its right neighbour is this pixel, its lower one (x - 1, y + 1) or itself
-            wl = vr_weight<FAST>(vr_add2(wlf, dl), cO, vr_add2(wdl, ddl), P);
-        }
-        float wu0 = 0.f;
-        if (wv == 0 && in && has_u) {
-            // weight of (x, y - 1): its lower neighbour is this pixel, its right one (x + 1, y - 1) or itself
-            wu0 = vr_weight<FAST>(vr_add2(wuf, dup), vr_add2(wur, dur), cO, P);
-        }
-        __syncthreads();
-        wu = wv == 0 ? wu0 : s_w[wv > 0 ? wv - 1 : 0][lane];
-        if (!in) return;
-        wl = has_l ? wl : 0.f; wu = has_u ? wu : 0.f;
-    } else {
-        wp = wt_in[j]; wl = has_l ? wt_in[j - 1] : 0.f; wu = has_u ? wt_in[j - W] : 0.f;
+    float wu0 = 0.f;
+    if (wv == 0 && in && has_u) {
+        // weight of (x, y - 1): its lower neighbour is this pixel, its right one (x + 1, y - 1) or itself
+        wu0 = vr_weight<FAST>(vr_add2(wuf, dup), vr_add2(wur, dur), cO, P);
     }
+    __syncthreads();
+    float wu = wv == 0 ? wu0 : s_w[wv > 0 ? wv - 1 : 0][lane];
+    if (!in) return;
+    wl = has_l ? wl : 0.f; wu = has_u ? wu : 0.f;
     const float Ix = d1.x, Iy = d1.y, Ixz = d1.z, Iyz = d1.w, Ixx = d2.x, Ixy = d2.y, Iyy = d2.z, Iz = d2.w;
     const float du = d.x, dv = d.y;
     // ComputeDataTerm.  The fifteen quotients whose numerator is a product of two derivative values share the
@@ -343,7 +318,9 @@ k_vr_sor(const float4 *__restrict__ S, const float *__restrict__ A12, const floa
 // store W + dW, the refined flow, instead of dW -- dW_out may then be the flow array itself (this kernel never reads W
 // except at the pixel a thread is about to write).
 // Measured and not adopted: delaying the odd workgroups of the first round by half a tile's time, so that loads and sweeps
-// of different CUs overlap instead of running in lockstep: 5.63 / 5.70 / 5.74 / 5.63 ms per refinement for 0 / 5 / 10 / 20 us.
+// of different CUs overlap instead of running in lockstep: 5.63 / 5.70 / 5.74 / 5.63 ms per refinement for 0 / 5 / 10 / 20 us;
+// half-height tiles (128 x 52 regions, 78 KB of LDS) with TWO 4-wave workgroups per CU, so that one loads while the other
+// sweeps, at the price of more halo (region / tile 1.93 instead of 1.47): profiles/round6_vr_sor_notes.txt.
 // Measured alternatives (12 x 5424^2, ms per step for all 110 launches): 128 x 64 tile, thread -> pair q = t + 512 k
 // (row and pair parity vary inside a wave: per-pixel index arithmetic, activity predicates and value selects between the
 // two pixels of a pair), 256 VGPRs: 93.2; the same with 1024 threads / 7 pairs / 128 VGPRs and a small spill: 95.9.
@@ -365,33 +342,20 @@ k_vr_sor(const float4 *__restrict__ S, const float *__restrict__ A12, const floa
 #define VRT_RW (VRT_W + 2 * VRT_HALO)
 #define VRT_PW (VRT_RW / 2)
 static_assert(VRT_PW == 64, "one lane per pixel pair of a region row");
-// Tile HEIGHT and workgroup size are template parameters since round 6: <84, 512> is the kernel described
-// above -- one 8-wave workgroup per CU, whose load phase (HBM-bound) and sweep phase (VALU-bound) alternate with nothing
-// resident to overlap them; <32, 256> is the same code on half-height tiles (region 128 x 52, 78 KB of LDS, 4 waves x 13 rows:
-// the same registers per thread), TWO workgroups per CU, so that one loads while the other sweeps -- at the price of more halo
-// (region / tile = 1.93 instead of 1.47).  Measured: profiles/round6_vr_sor_notes.txt.
-template <int TH, int NT> struct VrTile {
-    static constexpr int H = TH, RH = TH + 2 * VRT_HALO, THREADS = NT, WAVES = NT / 64, K = RH / WAVES;
-    static constexpr int LDS_BYTES = 2 * RH * VRT_PW * 12;
-    static_assert(RH % WAVES == 0, "whole rows per wave");
-};
-typedef VrTile<84, 512> VrTileFull;
-typedef VrTile<32, 256> VrTileHalf;
-#define VRT_H (TILE::H)
-#define VRT_RH (TILE::RH)
-#define VRT_THREADS (TILE::THREADS)
-#define VRT_WAVES (TILE::WAVES)
-#define VRT_K (TILE::K)
+#define VRT_H 84
+#define VRT_RH (VRT_H + 2 * VRT_HALO)
+#define VRT_THREADS 512
+#define VRT_WAVES (VRT_THREADS / 64)
+#define VRT_K (VRT_RH / VRT_WAVES)
+#define VRT_LDS_BYTES (2 * VRT_RH * VRT_PW * 12)
+static_assert(VRT_RH % VRT_WAVES == 0, "whole rows per wave");
 
-template <bool FAST, typename TILE>
-__global__ void __launch_bounds__(TILE::THREADS, 2)
+template <bool FAST>
+__global__ void __launch_bounds__(VRT_THREADS, 2)
 k_vr_sor_tile(const float4 *__restrict__ S, const float *__restrict__ A12, const float *__restrict__ wt, int H, int W,
-              int n_half, float omega, const float2 *__restrict__ dW_in, const float2 *Wadd, float2 *dW_out, VrB bs, int stagger)
+              int n_half, float omega, const float2 *__restrict__ dW_in, const float2 *Wadd, float2 *dW_out, VrB bs)
 {
     extern __shared__ __align__(16) unsigned char vr_lds[];
-    if (stagger > 0 && (blockIdx.x & 1)) {                 // (experiment: odd workgroups start `stagger` x 64 clocks late)
-        for (int i = 0; i < stagger; i++) __builtin_amdgcn_s_sleep(1);
-    }
     {
         const int64_t b = blockIdx.z;
         S += b * bs.plane; A12 += b * bs.plane; wt += b * bs.plane;
@@ -551,14 +515,11 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
     if (!params) { tf_varref_default_params(&dp); params = &dp; }
     TF_REQUIRE(params->fixed_point_iterations >= 0 && params->sor_iterations >= 0, "tf_varref: bad iteration counts");
     hipStream_t s = (hipStream_t)stream;
-    // the fused SOR kernel covers up to VRT_HALO half sweeps; TF_VR_SOR_SWEEPS=1 selects the one-launch-per-half-sweep
-    // form (same results, kept as the reference for the fused one and for larger sorIterations)
-    static const bool force_sweeps = getenv("TF_VR_SOR_SWEEPS") != nullptr;
-    static const bool weights_pass_env = getenv("TF_VR_WEIGHTS_PASS") != nullptr;   // development aid: separate pass
-    const bool tiled = !force_sweeps && 2 * params->sor_iterations <= VRT_HALO;
+    // the fused SOR kernel covers up to VRT_HALO half sweeps; more sorIterations take one launch per half sweep (k_vr_sor)
+    const bool tiled = 2 * params->sor_iterations <= VRT_HALO;
     const bool tile_path = tiled && params->sor_iterations > 0;
-    if (B > 1 && (!tile_path || weights_pass_env)) {
-        // the forms without a batch dimension (per-half-sweep kernels, the separate weights pass): image by image
+    if (B > 1 && !tile_path) {
+        // the per-half-sweep kernels have no batch dimension: image by image
         for (int64_t b = 0; b < B; b++)
             if (const int rc = vr_run(I0 + b * img_stride, I1 + b * img_stride, 1, 0, H, W, params, flow + b * flow_stride, 0, flags, ws, ws_bytes, stream)) return rc;
         return TF_OK;
@@ -590,10 +551,8 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
         static TfDeviceOnce once;                  // function attributes are per device
         TfDeviceOnce::Guard guard(once);
         if (guard.first) {
-            TF_CHECK_HIP(hipFuncSetAttribute((const void *)k_vr_sor_tile<false, VrTileFull>, hipFuncAttributeMaxDynamicSharedMemorySize, VrTileFull::LDS_BYTES));
-            TF_CHECK_HIP(hipFuncSetAttribute((const void *)k_vr_sor_tile<true, VrTileFull>, hipFuncAttributeMaxDynamicSharedMemorySize, VrTileFull::LDS_BYTES));
-            TF_CHECK_HIP(hipFuncSetAttribute((const void *)k_vr_sor_tile<false, VrTileHalf>, hipFuncAttributeMaxDynamicSharedMemorySize, VrTileHalf::LDS_BYTES));
-            TF_CHECK_HIP(hipFuncSetAttribute((const void *)k_vr_sor_tile<true, VrTileHalf>, hipFuncAttributeMaxDynamicSharedMemorySize, VrTileHalf::LDS_BYTES));
+            TF_CHECK_HIP(hipFuncSetAttribute((const void *)k_vr_sor_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, VRT_LDS_BYTES));
+            TF_CHECK_HIP(hipFuncSetAttribute((const void *)k_vr_sor_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, VRT_LDS_BYTES));
             guard.done();
         }
     }
@@ -604,18 +563,11 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
     for (int it = 0; it < params->fixed_point_iterations; it++) {
         {
             // algorithmic bytes: D1 + D2 32, W 8, dW 8 read; S 16, A12 4, weight 4 written (no dW in the first iteration)
-            const bool weights_pass = weights_pass_env && !fast;
             TfProfScope ps(TFK_VR_SYSTEM, (32.0 + 8.0 + (dW_cur ? 8.0 : 0.0) + 16.0 + 4.0 + 4.0) * nb, s);
-            if (weights_pass) {
-                hipLaunchKernelGGL(k_vr_weights, g1, dim3(256), 0, s, Wf, dW_cur, iH, iW, P, wt);
-                hipLaunchKernelGGL((k_vr_system<false, false>), g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf,
-                                   dW_cur, (const float *)wt, iH, iW, P, S, A12, (float *)nullptr, bs);
-            } else if (fast)
-                hipLaunchKernelGGL((k_vr_system<true, true>), g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf,
-                                   dW_cur, (const float *)nullptr, iH, iW, P, S, A12, wt, bs);
+            if (fast)
+                hipLaunchKernelGGL(k_vr_system<true>, g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf, dW_cur, iH, iW, P, S, A12, wt, bs);
             else
-                hipLaunchKernelGGL((k_vr_system<true, false>), g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf,
-                                   dW_cur, (const float *)nullptr, iH, iW, P, S, A12, wt, bs);
+                hipLaunchKernelGGL(k_vr_system<false>, g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf, dW_cur, iH, iW, P, S, A12, wt, bs);
         }
         TF_CHECK_LAUNCH();
         if (tile_path) {
@@ -624,18 +576,14 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
             const bool last = it == params->fixed_point_iterations - 1;
             TfProfScope ps(TFK_VR_SOR, (20.0 + 4.0 + (dW_cur ? 8.0 : 0.0) + (last ? 8.0 : 0.0) + 8.0) * nb, s);
             float2 *dst = last ? (float2 *)flow : (dW_cur == dW ? dW2 : dW);
-            // TF_VR_TILE=half: half-height tiles, two 4-wave workgroups per CU (VrTileHalf); TF_VR_STAGGER=<n>: odd workgroups
-            // start n x 64 clocks late (development switches of the round-6 experiment; default: the full tile, no stagger)
-            static const bool half_env = getenv("TF_VR_TILE") && !strcmp(getenv("TF_VR_TILE"), "half");
-            static const int stagger_env = getenv("TF_VR_STAGGER") ? atoi(getenv("TF_VR_STAGGER")) : 0;
             const float2 *wadd = last ? Wf : (const float2 *)nullptr;
-#define VR_LAUNCH_TILE(FASTV, TILET)                                                                                              \
-            hipLaunchKernelGGL((k_vr_sor_tile<FASTV, TILET>), dim3((iW + VRT_W - 1) / VRT_W, (iH + TILET::H - 1) / TILET::H, Z),      \
-                               dim3(TILET::THREADS), TILET::LDS_BYTES, s, (const float4 *)S, (const float *)A12, (const float *)wt,  \
-                               iH, iW, 2 * params->sor_iterations, P.omega, dW_cur, wadd, dst, bs, stagger_env)
-            if (half_env) { if (fast_sor) VR_LAUNCH_TILE(true, VrTileHalf); else VR_LAUNCH_TILE(false, VrTileHalf); }
-            else { if (fast_sor) VR_LAUNCH_TILE(true, VrTileFull); else VR_LAUNCH_TILE(false, VrTileFull); }
-#undef VR_LAUNCH_TILE
+            const dim3 gt((iW + VRT_W - 1) / VRT_W, (iH + VRT_H - 1) / VRT_H, Z);
+            if (fast_sor)
+                hipLaunchKernelGGL(k_vr_sor_tile<true>, gt, dim3(VRT_THREADS), VRT_LDS_BYTES, s, (const float4 *)S, (const float *)A12,
+                                   (const float *)wt, iH, iW, 2 * params->sor_iterations, P.omega, dW_cur, wadd, dst, bs);
+            else
+                hipLaunchKernelGGL(k_vr_sor_tile<false>, gt, dim3(VRT_THREADS), VRT_LDS_BYTES, s, (const float4 *)S, (const float *)A12,
+                                   (const float *)wt, iH, iW, 2 * params->sor_iterations, P.omega, dW_cur, wadd, dst, bs);
             dW_cur = dst;
             flow_done = last;
         } else {
