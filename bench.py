@@ -21,6 +21,11 @@ share four frames bit for bit); the stitch then runs over all windows of all ran
 boundary and all-gathers of the pair lists (tobac_flow_amd/parallel.py: stitch_rank_windows).
 --config window --frames 12 is the round-1/2 sub-report (one 12-frame window per step).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the per-kernel figures in it come
+from events recorded inside the timed steps.  --full adds what takes runs of its own, all after the timed region: one
+stack by itself and one step in raster tie order, the flow kernels with nothing beside them, the copy kernel's practical
+HBM ceiling, the CPU baseline with its oracle check and the OpenCV parity probe.
 """
 import argparse
 import json
@@ -356,10 +361,13 @@ def main():
                          "memos of the host layer see changing input, as in a production sweep")
     ap.add_argument("--rotate-shift", type=int, default=7, help="frame offset between consecutive rotated stacks (not a multiple "
                     "of the window stride: no window of one step repeats a window of another)")
-    ap.add_argument("--no-raster-subreport", action="store_true", help="skip the one extra (untimed) step in raster tie order")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the sub-reports (one stack by itself, one step in raster tie order, the flow "
+                         "kernels uncontended), the copy kernel's practical HBM ceiling, the CPU baseline and the OpenCV parity probe")
+    ap.add_argument("--no-raster-subreport", action="store_true", help="--full: skip the one extra (untimed) step in raster tie order")
     ap.add_argument("--single-label-seeds", action="store_true",
                     help="round-2 seeds (every positive seed = 1, detect_anvils(markers=None)) instead of component-labelled ones")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the OpenCV parity probe")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--no-pipeline-stacks", dest="pipeline_stacks", action="store_false",
@@ -589,7 +597,7 @@ def main():
     del out_labels
     n_timed = len(ws_stats)
     alone_ms = None
-    if pipelined and not a.no_raster_subreport:
+    if a.full and pipelined and not a.no_raster_subreport:
         # sub-report, outside the timed region: ONE stack processed by itself (detect_stack_windows), its end with nothing beside it
         barrier()
         ts = time.perf_counter()
@@ -598,7 +606,7 @@ def main():
         alone_ms = (time.perf_counter() - ts) * 1e3
         del out_labels
     raster_ms = None
-    if a.tie_order == "reference" and not a.no_raster_subreport:
+    if a.full and a.tie_order == "reference" and not a.no_raster_subreport:
         # sub-report, outside the timed region: ONE step with equal-valued markers in raster order (on_ambiguous="ignore")
         tie_mode["order"] = "raster"
         barrier()
@@ -613,7 +621,7 @@ def main():
     # round 5 the floods run on a thread and a stream of their own beside the whole flow, so the launch durations the library's
     # HIP events record inside the timed region (`roofline.frac`) include what the floods' kernels take from the flow's.
     prof_alone = None
-    if world == 1 and full_size and not a.no_kernel_events and T >= 43:
+    if a.full and world == 1 and full_size and not a.no_kernel_events and T >= 43:
         torch.cuda.synchronize()
         _lib.profile_enable(True)
         _lib.profile_collect()
@@ -805,7 +813,7 @@ def main():
         out["stages"]["streams_overlap_ms"] = {"ms_per_step": round(sum(stage_ms.values()) - dt / a.steps * 1e3, 2),
                                                "note": "sum of the library's kernel time over both streams minus the step's wall time: > 0 = kernel time "
                                                        "hidden by running the floods beside the flow, < 0 = wall time outside the library's kernels"}
-        if roof is not None:
+        if a.full and roof is not None:
             # the practical HBM ceiling: the library's own plain copy, 16 bytes per lane per access, four loads in flight per lane
             # (tf_copy16; round 5 -- rounds 2 - 4 timed torch's copy_, which reaches 4.9 TB/s where MI355X_MICROARCH.md's
             # float4 copy reaches 6.29: a flattering denominator)
@@ -829,7 +837,7 @@ def main():
                                            "bytes); MI355X_MICROARCH.md's float4 copy: 6290 GB/s" % (4 * n_copy / 1e9))
             roof["frac_practical"] = round(roof["achieved"] / copy_gbps, 4)
             del src, dst
-        if not a.no_cpu_baseline and world == 1:             # reported baseline: rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:  # reported baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(20240601, a.vr_steps)
             out["cv2_parity"] = cv2_parity()
         print(json.dumps(out))

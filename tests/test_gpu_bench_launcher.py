@@ -15,10 +15,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _bench(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-           "--rotate", "1", "--no-raster-subreport", *extra]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+def _bench(*extra, reports=False, env_extra=None):
+    """one bench.py run as a fresh child process; reports=True keeps what --full runs after the timed region (the CPU
+    baseline, the raster sub-report), which the other calls switch off"""
+    skip = [] if reports else ["--no-cpu-baseline", "--no-raster-subreport"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C", "--steps", "1", "--warmup", "0", "--rotate", "1", *skip, *extra]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(env_extra or {}))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
@@ -120,3 +122,23 @@ def test_bench_dump_outputs_writes_the_last_steps_labels(tmp_path):
     for f in files[:2]:
         a, b = np.load(tmp_path / "handed" / f), np.load(tmp_path / "kept" / f)
         assert (a > 0).any() and np.array_equal(a, b), f
+
+
+def test_bench_full_adds_the_untimed_reports_a_plain_run_leaves_out():
+    """A plain run does only what its headline figure needs: set-up, warm-up, the timed steps, the line.  --full adds, after
+    the timed region, one stack by itself, one step in raster tie order, the copy kernel's HBM ceiling, the CPU baseline with
+    the library checked against the oracle on its sample (three frames here, TF_BENCH_CPU_FRAMES) and the OpenCV probe; the
+    timed steps are the same ones."""
+    args = ("--frames", "44", "--n-windows", "4", "--steps", "2")
+    plain = _bench(*args, reports=True)
+    full = _bench(*args, "--full", reports=True, env_extra={"TF_BENCH_CPU_FRAMES": "3"})
+    assert plain["steps_pipelined"]["on"] and full["steps_pipelined"]["on"]
+    assert plain["one_stack_by_itself_ms"] is None and "raster_order_subreport" not in plain["watershed"]
+    assert "practical_peak" not in plain["roofline"] and "cpu_baseline" not in plain and "cv2_parity" not in plain
+    assert plain["roofline"]["all_kernels"] and plain["ms_per_step"] > 0
+    assert full["one_stack_by_itself_ms"] > 0 and full["watershed"]["raster_order_subreport"]["ms_per_step"] > 0
+    assert full["roofline"]["practical_peak"] > 0 and full["roofline"]["frac_practical"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["library_vs_oracle_on_the_sample"] == {
+        "flow_bit_identical": True, "edge_field_bit_identical": True, "labels_bit_identical": True}
+    assert "status" in full["cv2_parity"]
+    assert full["config"]["objects_after_stitch_per_step"] == plain["config"]["objects_after_stitch_per_step"]
