@@ -1,4 +1,4 @@
-"""Seeded synthetic inputs shared by the parity tests."""
+"""Seeded synthetic inputs and the bit-exact comparison shared by the parity tests."""
 import numpy as np
 import scipy.ndimage as ndi
 
@@ -40,3 +40,14 @@ def seeds(rng, shape, n, with_bg=True):
         t, y, x = [rng.integers(0, s) for s in shape]
         m[t, y, x] = -1
     return m
+
+
+def _eq(a, b):
+    """bit-exact including NaN positions"""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    nan = np.isnan(a) if a.dtype.kind == "f" else np.zeros(a.shape, bool)
+    nanb = np.isnan(b) if b.dtype.kind == "f" else np.zeros(b.shape, bool)
+    assert np.array_equal(nan, nanb), f"NaN masks differ at {int((nan != nanb).sum())} px"
+    bad = (a != b) & ~nan
+    assert not bad.any(), f"{int(bad.sum())} px differ, max abs {np.nanmax(np.abs(a[bad].astype(np.float64) - b[bad]))}"

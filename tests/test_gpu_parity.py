@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import scipy.ndimage as ndi
 
-from helpers import blob_sequence, rand_field, rand_flow, seeds
+from helpers import _eq, blob_sequence, rand_field, rand_flow, seeds
 
 pytestmark = pytest.mark.gpu
 
@@ -18,17 +18,6 @@ pytestmark = pytest.mark.gpu
 def tf():
     import tobac_flow_amd.flow as flow
     return flow
-
-
-def _eq(a, b):
-    """bit-exact including NaN positions"""
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
-    nan = np.isnan(a) if a.dtype.kind == "f" else np.zeros(a.shape, bool)
-    nanb = np.isnan(b) if b.dtype.kind == "f" else np.zeros(b.shape, bool)
-    assert np.array_equal(nan, nanb), f"NaN masks differ at {int((nan != nanb).sum())} px"
-    bad = (a != b) & ~nan
-    assert not bad.any(), f"{int(bad.sum())} px differ, max abs {np.nanmax(np.abs(a[bad].astype(np.float64) - b[bad]))}"
 
 
 # ----------------------------------------------------------------------------- convolve / sobel
