@@ -199,13 +199,15 @@ extern "C" int tf_binary_morph(const uint8_t *in, int64_t T, int64_t H, int64_t 
     return TF_OK;
 }
 
-// linearise_field: clip((f - lo) / (hi - lo), 0, 1), reversed thresholds flip the ramp (float32 like numpy on float32)
+// linearise_field: clip((f - lo) / (hi - lo), 0, 1), reversed thresholds flip the ramp (float32 like numpy on float32).
+// `span` is hi - lo formed in double and rounded ONCE, as numpy does with the Python floats of the host function: the
+// difference of the two rounded thresholds is another value (0.7f - 0.1f != (float)(0.7 - 0.1)) and moved the whole ramp.
 __global__ void __launch_bounds__(256)
-k_linearise(const float *__restrict__ f, int64_t n, float lo, float hi, int flip, float *__restrict__ out)
+k_linearise(const float *__restrict__ f, int64_t n, float lo, float span, int flip, float *__restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float v = (f[i] - lo) / (hi - lo);
+    float v = (f[i] - lo) / span;
     v = (v != v) ? v : fminf(v, 1.f);          // np.minimum / np.maximum propagate NaN
     v = (v != v) ? v : fmaxf(v, 0.f);
     out[i] = flip ? 1.f - v : v;
@@ -222,12 +224,12 @@ static bool tf_vec4_ok(std::initializer_list<const void *> words, std::initializ
 }
 
 __global__ void __launch_bounds__(256)
-k_linearise4(const float *__restrict__ f, int64_t n, float lo, float hi, int flip, float *__restrict__ out)
+k_linearise4(const float *__restrict__ f, int64_t n, float lo, float span, int flip, float *__restrict__ out)
 {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
     auto one = [&](float x) {
-        float v = (x - lo) / (hi - lo);
+        float v = (x - lo) / span;
         v = (v != v) ? v : fminf(v, 1.f);
         v = (v != v) ? v : fmaxf(v, 0.f);
         return flip ? 1.f - v : v;
@@ -248,10 +250,10 @@ extern "C" int tf_linearise(const float *field, int64_t n, double lower, double 
     if (lower > upper) { const double t = lower; lower = upper; upper = t; flip = 1; }
     if (tf_vec4_ok({field, out}, {}))
         hipLaunchKernelGGL(k_linearise4, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, field, n,
-                           (float)lower, (float)upper, flip, out);
+                           (float)lower, (float)(upper - lower), flip, out);
     else
-    hipLaunchKernelGGL(k_linearise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, field, n,
-                       (float)lower, (float)upper, flip, out);
+        hipLaunchKernelGGL(k_linearise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, field, n,
+                           (float)lower, (float)(upper - lower), flip, out);
     TF_CHECK_LAUNCH();
     return TF_OK;
 }
