@@ -7,8 +7,6 @@
 // All are one-pass HBM-bound stencils / reductions on uint8 / int32 volumes.
 #include "tf_common.h"
 #include <initializer_list>
-#include <string.h>
-#include <stdlib.h>
 
 struct MorphTaps { int n; int8_t dt[27], dy[27], dx[27]; };
 
@@ -94,21 +92,16 @@ __global__ void __launch_bounds__(256)
 k_binary_morph16(const uint4 *__restrict__ in, int64_t T, int H, int W16, MorphRows rw, int op, int border,
                  uint4 *__restrict__ out)
 {
-    // Round 6: a 1-D grid whose workgroup -> (tile, t) mapping is XCD-aware.  Workgroup L runs on XCD L % 8 (round-robin
+    // A 1-D grid whose workgroup -> (tile, t) mapping is XCD-aware.  Workgroup L runs on XCD L % 8 (round-robin
     // dispatch); within an XCD consecutive workgroups take consecutive time steps t of ONE (x, y) tile, so the up to three
-    // planes a tap row reads (t - 1, t, t + 1) are requested by workgroups that share an L2 and run back to back.  With the
-    // (x, y, t) grid of rounds 2 - 5 a plane was read again a whole plane's worth of workgroups later -- from the fabric:
-    // 2.18 x the algorithmic bytes by FETCH_SIZE for the 3 x 3 x 3 structure.
+    // planes a tap row reads (t - 1, t, t + 1) are requested by workgroups that share an L2 and run back to back.  With an
+    // (x, y, t) grid a plane is read again a whole plane's worth of workgroups later -- from the fabric: 2.18 x the
+    // algorithmic bytes by FETCH_SIZE for the 3 x 3 x 3 structure.
     // A tile is 1024 x 8 pixels: every thread forms TWO output rows (y, y + 4), so that the two halo rows of a tile are read
     // per eight output rows instead of per four (1.25 x instead of 1.5 x the rows; the rows the two halves share come from L1).
     const int tiles_x = (W16 + 63) / 64, tiles_y = (H + 7) / 8;
     const int64_t n_tiles = (int64_t)tiles_x * tiles_y, L = blockIdx.x;
-    int64_t slot = L >> 3, tile = (slot / T) * 8 + (L & 7), t = slot % T;
-    if (border & 2) {                                 // (A/B switch TF_MORPH_GRID=plane: the (x, y, t) order of rounds 2 - 5)
-        const int64_t padded = (n_tiles + 7) / 8 * 8;
-        tile = L % padded; t = L / padded;
-        border &= 1;
-    }
+    const int64_t slot = L >> 3, tile = (slot / T) * 8 + (L & 7), t = slot % T;
     if (tile >= n_tiles) return;
     const int x16 = (int)(tile % tiles_x) * 64 + threadIdx.x;
     if (x16 >= W16) return;
@@ -189,8 +182,7 @@ extern "C" int tf_binary_morph(const uint8_t *in, int64_t T, int64_t H, int64_t 
         // ping-pong so that the last iteration writes `out`
         uint8_t *dst = ((iterations - 1 - it) % 2 == 0) ? out : tmp;
         TfProfScope ps(TFK_MORPH, 2.0 * (double)T * H * W, s);
-        static const bool plane_grid = getenv("TF_MORPH_GRID") && !strcmp(getenv("TF_MORPH_GRID"), "plane");
-        if (quads) hipLaunchKernelGGL(k_binary_morph16, grid16, block, 0, s, (const uint4 *)src, T, (int)H, (int)(W / 16), rw, op, (border_value ? 1 : 0) | (plane_grid ? 2 : 0), (uint4 *)dst);   // (grid16: 1-D, XCD-aware mapping inside)
+        if (quads) hipLaunchKernelGGL(k_binary_morph16, grid16, block, 0, s, (const uint4 *)src, T, (int)H, (int)(W / 16), rw, op, border_value, (uint4 *)dst);   // (grid16: 1-D, XCD-aware mapping inside)
         else if (words) hipLaunchKernelGGL(k_binary_morph4, grid4, block, 0, s, (const uint32_t *)src, T, (int)H, (int)(W / 4), rw, op, border_value, (uint32_t *)dst);
         else hipLaunchKernelGGL(k_binary_morph, grid, block, 0, s, src, T, (int)H, (int)W, tp, op, border_value, dst);
         src = dst;
@@ -618,8 +610,6 @@ extern "C" int tf_label(const uint8_t *in, int64_t T, int64_t H, int64_t W, cons
     dim3 block(64, 4), grid((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4), (unsigned)T);
     bool runs = false;                                              // the structure holds the horizontal tap (0, 0, +1)
     for (int i = 0; i < tp.n; i++) runs = runs || (tp.dt[i] == 0 && tp.dy[i] == 0 && tp.dx[i] == 1);
-    static const bool no_runs_env = getenv("TF_CCL_NO_RUNS") != nullptr;                 // development switch: the plain form (same labels)
-    if (no_runs_env) runs = false;
     if (runs) hipLaunchKernelGGL(k_ccl_init_runs, grid, block, 0, s, in, T, (int)H, (int)W, parent);
     else if (tf_vec4_ok({parent}, {in})) hipLaunchKernelGGL(k_ccl_init4, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, s, in, n, parent);
     else hipLaunchKernelGGL(k_ccl_init, dim3(nb), dim3(256), 0, s, in, n, parent);

@@ -91,11 +91,6 @@ __device__ __forceinline__ unsigned ws_ordkey(float v) {
 __device__ __forceinline__ u64 ws_load(const u64 *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// Ordering by data dependency.  The in-queue flag of a pixel must be cleared BEFORE its key is read (otherwise a
-// decrease that lands between the read and the clear is never propagated).  Both are relaxed agent-scope accesses to
-// different addresses, which the memory system may perform out of order; so the key's address takes the exchange's
-// return value (0 or 1) as a term the compiler cannot fold: ws_after(x) is 0 for every value the flag can hold.
-__device__ __forceinline__ int ws_after(int was) { asm volatile("" : "+v"(was)); return was >> 2; }
 __device__ __forceinline__ int ws_round_flow(float f) {
     // np.round(flow).astype(int32), watershed.py:121-141 (half to even); NaN -> 0
     return (f == f) ? __float2int_rn(f) : 0;
@@ -470,27 +465,22 @@ k_ws_init_labelset(const u64 *__restrict__ pix, const int32_t *__restrict__ mark
 }
 
 // ---- frontier queues ---------------------------------------------------------------------------
-// Two modes.  WITHOUT in-queue flags (inq == nullptr, the default): a pixel is appended whenever a relaxation STRICTLY
-// lowers its key -- no lost update by construction (the append follows the atomic that lowered the key), and a pixel
-// lowered twice in one sweep simply sits in the queue twice (the second visit finds nothing to do).  That removes
-// ~4 of the ~10 returning atomics a processed pixel costs, which is what bounds the sweeps.  The queue length then has
-// no a-priori bound: if a sweep overflows its queue the host re-seeds the phase with a full scan (every finite key is
-// pushed again; the fixpoint is the same).  WITH flags (TF_WS_DEDUPE=1, the round-1 scheme):
-// A sweep processes the queue of pixels whose key changed (qin) and appends every pixel whose key it
-// lowers to qout.  inq[n] = 1 while n sits in a queue and has not been processed since: the flag is
-// cleared BEFORE the pixel's key is read, so a later decrease always re-queues it (no lost update); a
-// pixel can appear at most twice per queue, hence the 2R capacity.  Appends are aggregated per wave
-// (one atomicAdd per 64 lanes).
-// LOCAL ROUNDS.  A sweep used to advance every front by exactly one pixel: a flood that has to cross a few hundred
-// pixels of plateau costs that many launches, each a few microseconds of work behind ~20 us of launch latency.  A
-// workgroup now keeps the pixels it has just lowered in LDS and relaxes THEM as well, for up to `rounds` further
-// rounds, before it hands what is left to the global queue: its piece of the front moves several pixels per launch.
-// Measured (12 x 5424^2, 17.6 M relevant pixels): 576 -> 96 launches per call with 8 rounds, 128 with 4 -- and the same
-// 32 ms either way.  The sweeps are NOT launch-bound: a call issues ~10 returning 64-bit atomics per processed pixel
-// (K2 and M1 minima, in-queue flags), ~2 x 10^8 per phase, and runs at the chip's rate for scattered atomics
-// (~2 x 10^10 / s, MI355X_MICROARCH.md "Global float atomics": 64 lanes in 64 rows).  Fewer launches is what is kept.
-// Chaotic relaxation of a monotone system reaches the same fixpoint in any order, and the in-queue flags work as
-// before (a staged pixel has its flag set; whoever processes it clears the flag before reading the key).
+// A sweep processes the queue of pixels whose key changed (qin) and appends to qout every pixel whose key one of its
+// relaxations STRICTLY lowers.  The append follows the atomic that lowered the key, so no update is lost; a pixel lowered
+// twice in one sweep sits in the queue twice, and its second visit finds nothing to do (it reads its own key with a
+// relaxed agent-scope load, ws_load / ws_load_i, and so sees the lowered value).  The queue length therefore has no
+// a-priori bound: appends past the capacity are dropped and counted, and the host re-seeds a phase whose queue was cut
+// off with a scan of all relevant pixels (keys only decrease, every key is still a valid upper bound, the fixpoint is
+// the same).  Appends are staged in LDS and handed over with one global atomicAdd per workgroup and buffer.
+// LOCAL ROUNDS.  Advancing every front by one pixel per launch makes a flood that has to cross a few hundred pixels of
+// plateau cost that many launches.  A workgroup keeps the pixels it has just lowered in LDS and relaxes THEM as well, for
+// up to WS_LOCAL_ROUNDS further rounds, before it hands what is left to the global queue: its piece of the front moves
+// several pixels per launch.  Measured (12 x 5424^2, 17.6 M relevant pixels): 576 -> 128 launches per call with 4 rounds,
+// 96 with 8 -- and the same time either way.  The sweeps are NOT launch-bound: a call issues ~6 returning 64-bit atomics
+// per processed pixel (K2 and M1 minima), and runs at the chip's rate for scattered atomics (~2 x 10^10 / s,
+// MI355X_MICROARCH.md "Global float atomics": 64 lanes in 64 rows).  Fewer launches is what is kept.  Chaotic relaxation
+// of a monotone system reaches the same fixpoint in any order.
+#define WS_LOCAL_ROUNDS 4
 #ifndef WS_LDS_CAP
 #define WS_LDS_CAP 4096
 #endif
@@ -519,21 +509,55 @@ __device__ __forceinline__ void ws_flush(WsStage &st, int w, int *__restrict__ q
     __syncthreads();
 }
 
+// One sweep, shared by every phase: each workgroup takes 256 entries of qin at a time (qin == nullptr: first sweep of a
+// phase = scan of all R relevant pixels, no seed queue needed), runs `entry` on them, then up to WS_LOCAL_ROUNDS local
+// rounds on what it has just lowered (LDS buffers w and w ^ 1 in turn), and flushes the rest to qout.
+// entry(st, w, act, p): relax the out-edges of p if act, staging the lowered pixels in buffer w; reached by every thread.
+template <class Entry>
+__device__ __forceinline__ void ws_sweep(int64_t R, const int *__restrict__ qin, const int *__restrict__ cnt_in,
+                                         int *__restrict__ qout, int *__restrict__ cnt_out, int qcap, Entry entry)
+{
+    __shared__ WsStage st;
+    if (threadIdx.x == 0) { st.cnt[0] = 0; st.cnt[1] = 0; }
+    __syncthreads();
+    const int64_t n_in = qin ? (int64_t)min(*cnt_in, qcap) : R;
+    const int64_t n_pad = (n_in + 255) & ~255ll;
+    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n_pad; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool act = i < n_in;
+        int w = 0;
+        entry(st, w, act, act ? (qin ? qin[i] : (int)i) : 0);
+        for (int r = 0; r < WS_LOCAL_ROUNDS; r++) {            // local rounds: relax what this workgroup has just lowered
+            __syncthreads();
+            const int n = min(st.cnt[w], WS_LDS_CAP);
+            if (n == 0) break;                                 // (uniform: read after the barrier)
+            for (int j0 = 0; j0 < n; j0 += 256) {
+                const int j = j0 + threadIdx.x;
+                const bool a2 = j < n;
+                entry(st, w ^ 1, a2, a2 ? st.buf[w][j] : 0);
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) st.cnt[w] = 0;
+            w ^= 1;
+        }
+        ws_flush(st, w, qout, cnt_out, qcap);
+    }
+}
+
 // ---- phase A: K2 and M1 ------------------------------------------------------------------------
-// Memory-level parallelism.  A queue entry used to walk its out-edges one at a time: neighbour id -> its value
-// and keys -> atomics, about twenty DEPENDENT round trips per entry, and a large sweep ran at the latency of that
-// chain (0.45 ns per entry = a few hundred GB/s).  The edges of one pixel are independent, so they are now handled
-// WS_NB at a time in three waves of independent accesses: all neighbour ids (issued together with the in-queue
-// exchange), then all neighbour values / keys, then all atomics.  Same operations, same decisions on the values the
-// atomics return; the plain reads were already only pre-filters (keys only decrease, a stale value is larger).
+// Memory-level parallelism.  Walking the out-edges of a queue entry one at a time (neighbour id -> its value and keys
+// -> atomics) is about twenty DEPENDENT round trips per entry, and a large sweep then runs at the latency of that chain
+// (0.45 ns per entry = a few hundred GB/s).  The edges of one pixel are independent, so they are handled WS_NB at a
+// time in three waves of independent accesses: all neighbour ids (issued together with the load of the pixel's own key),
+// then all neighbour values / keys, then all atomics.  The plain reads are only pre-filters (keys only decrease, a
+// stale value is larger); the decisions are made on the values the atomics return.
 #define WS_NB 8
 
 // one queue entry of phase A: pop p, relax its out-edges WS_NB at a time, stage the pixels whose key it lowered
-// NN = 6 (round 5): the six face neighbours as a compile-time count -- one trip of SIX slots instead of eight with two dead
-// ones (a dead slot still cost its registers and two loads of element 0 per entry): k_ws_sweep_a 80 -> 64 VGPRs; NN = 0:
-// any neighbour count, eight slots per trip
+// NN = 6: the six face neighbours as a compile-time count -- one trip of SIX slots instead of eight with two dead ones (a
+// dead slot still costs its registers and two loads of element 0 per entry); NN = 0: any neighbour count, eight slots per trip
 template <int NN>
-__device__ __forceinline__ void ws_entry_a(const WsC &c, WsStage &st, int w, bool act, int p, int *__restrict__ inq,
+__device__ __forceinline__ void ws_entry_a(const WsC &c, WsStage &st, int w, bool act, int p,
                                            int *__restrict__ qout, int *__restrict__ cnt_out, int qcap)
 {
     constexpr int NB = NN ? NN : WS_NB;
@@ -544,12 +568,7 @@ __device__ __forceinline__ void ws_entry_a(const WsC &c, WsStage &st, int w, boo
         int n[NB];
 #pragma unroll
         for (int j = 0; j < NB; j++) n[j] = (act && s0 + j < n_nbr) ? np[s0 + j] : -1;
-        if (s0 == 0 && act) {
-            // relaxed L2 atomics only: the key is loaded after the exchange has returned (the flag is cleared BEFORE
-            // the key is read, so a later decrease re-queues the pixel); the id loads above are already in flight
-            const int dep = inq ? ws_after(atomicExch(&inq[p], 0)) : 0;
-            kp = ws_load(&WS_K2(c, p) + 2 * dep);
-        }
+        if (s0 == 0 && act) kp = ws_load(&WS_K2(c, p));            // (the id loads above are already in flight)
         const u64 lp = kp >> 32;
         u64 vn[NB], m1[NB], k2[NB];
 #pragma unroll
@@ -570,49 +589,19 @@ __device__ __forceinline__ void ws_entry_a(const WsC &c, WsStage &st, int w, boo
                 if (cand[j] < k2[j]) old[j] = atomicMin(&WS_K2(c, n[j]), cand[j]);
             }
         }
-        int was_q[NB];                                              // raw returns: consumed only after all are issued
 #pragma unroll
-        for (int j = 0; j < NB; j++) {
-            was_q[j] = 1;
-            if (n[j] >= 0 && cand[j] < old[j]) was_q[j] = inq ? atomicExch(&inq[n[j]], 1) : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; j++) ws_stage(st, w, was_q[j] == 0, n[j], qout, cnt_out, qcap);
+        for (int j = 0; j < NB; j++)                               // raw returns: consumed only after all are issued
+            ws_stage(st, w, n[j] >= 0 && cand[j] < old[j], n[j], qout, cnt_out, qcap);
     }
 }
 
 template <int NN>
 __global__ void __launch_bounds__(256)
 k_ws_sweep_a(WsC c, const int *__restrict__ qin, const int *__restrict__ cnt_in, int *__restrict__ qout,
-             int *__restrict__ cnt_out, int *__restrict__ inq, int qcap, int rounds)
+             int *__restrict__ cnt_out, int qcap)
 {
-    __shared__ WsStage st;
-    if (threadIdx.x == 0) { st.cnt[0] = 0; st.cnt[1] = 0; }
-    __syncthreads();
-    // qin == nullptr: first sweep of the phase = scan of all relevant pixels (no seed queue needed)
-    const int64_t n_in = qin ? (int64_t)min(*cnt_in, qcap) : c.R;
-    const int64_t n_pad = (n_in + 255) & ~255ll;
-    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n_pad; i0 += (int64_t)gridDim.x * 256) {
-        const int64_t i = i0 + threadIdx.x;
-        const bool act = i < n_in;
-        const int p = act ? (qin ? qin[i] : (int)i) : 0;
-        int w = 0;
-        ws_entry_a<NN>(c, st, w, act, p, inq, qout, cnt_out, qcap);
-        for (int r = 0; r < rounds; r++) {                     // local rounds: relax what this workgroup has just lowered
-            __syncthreads();
-            const int n = min(st.cnt[w], WS_LDS_CAP);
-            if (n == 0) break;                                 // (uniform: read after the barrier)
-            for (int j0 = 0; j0 < n; j0 += 256) {
-                const int j = j0 + threadIdx.x;
-                const bool a2 = j < n;
-                ws_entry_a<NN>(c, st, w ^ 1, a2, a2 ? st.buf[w][j] : 0, inq, qout, cnt_out, qcap);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) st.cnt[w] = 0;
-            w ^= 1;
-        }
-        ws_flush(st, w, qout, cnt_out, qcap);
-    }
+    ws_sweep(c.R, qin, cnt_in, qout, cnt_out, qcap,
+             [&](WsStage &st, int w, bool act, int p) { ws_entry_a<NN>(c, st, w, act, p, qout, cnt_out, qcap); });
 }
 
 // After phase A the keys K2 and M1 are final, and with them which edges p -> n are candidate edges (K2[p] == M1[n]: p is
@@ -662,7 +651,7 @@ __device__ __forceinline__ int ws_load_i(const int *p) {
 
 template <int NN>
 __device__ __forceinline__ void ws_entry_chain(const WsC &c, int k, int depth, u64 *__restrict__ dst, WsStage &st, int w,
-                                               bool act0, int p, int *__restrict__ inq,
+                                               bool act0, int p,
                                                int *__restrict__ qout, int *__restrict__ cnt_out, int qcap)
 {
     constexpr int NB = NN ? NN : WS_NB;
@@ -674,13 +663,10 @@ __device__ __forceinline__ void ws_entry_chain(const WsC &c, int k, int depth, u
     u64 cp[WS_MAX_DEPTH];                        // C_j[p], j < k: final since their own phases, read once per entry
     for (int s0 = 0; s0 < n_nbr; s0 += NB) {
         if (s0 == 0 && act0) {
-            // the in-queue flag is cleared BEFORE p's own keys are read (the loads take the exchange's
-            // return value as an address term), so a later decrease re-queues p: no lost update
-            const int dep = inq ? ws_after(atomicExch(&inq[p], 0)) : 0;
             em = c.emask[p];                     // final since phase A (0 for a pixel phase A never reached)
             kp = WS_K2(c, p);
-            own = ws_load(&dst[p] + dep);
-            if (root) { own_lo = ws_load_i(&c.Llo[p] + dep); own_hi = ws_load_i(&c.Lhi[p] + dep); }
+            own = ws_load(&dst[p]);
+            if (root) { own_lo = ws_load_i(&c.Llo[p]); own_hi = ws_load_i(&c.Lhi[p]); }
             for (int j = 1; j < k; j++) cp[j] = c.C[j][p];
         }
         // candidate edges only: one or two of the six at connectivity 1
@@ -718,50 +704,22 @@ __device__ __forceinline__ void ws_entry_chain(const WsC &c, int k, int depth, u
                 }
             }
         }
-        int was_q[NB];
 #pragma unroll
         for (int j = 0; j < NB; j++) {
-            was_q[j] = 1;
             const bool improved = offered[j] < old[j] || (root && (own_lo < olo[j] || own_hi > ohi[j]));
-            if (improved) was_q[j] = inq ? atomicExch(&inq[n[j]], 1) : 0;
+            ws_stage(st, w, improved, n[j], qout, cnt_out, qcap);
         }
-#pragma unroll
-        for (int j = 0; j < NB; j++) ws_stage(st, w, was_q[j] == 0, n[j], qout, cnt_out, qcap);
     }
 }
 
 template <int NN>
 __global__ void __launch_bounds__(256)
 k_ws_sweep_chain(WsC c, int k, int depth, const int *__restrict__ qin, const int *__restrict__ cnt_in,
-                 int *__restrict__ qout, int *__restrict__ cnt_out, int *__restrict__ inq, int qcap, int rounds)
+                 int *__restrict__ qout, int *__restrict__ cnt_out, int qcap)
 {
-    __shared__ WsStage st;
-    if (threadIdx.x == 0) { st.cnt[0] = 0; st.cnt[1] = 0; }
-    __syncthreads();
-    const int64_t n_in = qin ? (int64_t)min(*cnt_in, qcap) : c.R;
-    const int64_t n_pad = (n_in + 255) & ~255ll;
     u64 *dst = k == depth ? c.Rt : c.C[k];
-    for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n_pad; i0 += (int64_t)gridDim.x * 256) {
-        const int64_t i = i0 + threadIdx.x;
-        const bool act0 = i < n_in;
-        const int p = act0 ? (qin ? qin[i] : (int)i) : 0;
-        int w = 0;
-        ws_entry_chain<NN>(c, k, depth, dst, st, w, act0, p, inq, qout, cnt_out, qcap);
-        for (int r = 0; r < rounds; r++) {
-            __syncthreads();
-            const int n = min(st.cnt[w], WS_LDS_CAP);
-            if (n == 0) break;
-            for (int j0 = 0; j0 < n; j0 += 256) {
-                const int j = j0 + threadIdx.x;
-                const bool a2 = j < n;
-                ws_entry_chain<NN>(c, k, depth, dst, st, w ^ 1, a2, a2 ? st.buf[w][j] : 0, inq, qout, cnt_out, qcap);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) st.cnt[w] = 0;
-            w ^= 1;
-        }
-        ws_flush(st, w, qout, cnt_out, qcap);
-    }
+    ws_sweep(c.R, qin, cnt_in, qout, cnt_out, qcap,
+             [&](WsStage &st, int w, bool act, int p) { ws_entry_chain<NN>(c, k, depth, dst, st, w, act, p, qout, cnt_out, qcap); });
 }
 
 // ---- exactness check after a root phase at depth d ------------------------------------------------------------
@@ -1199,7 +1157,7 @@ static size_t ws_compact_bytes(int64_t R, int n_nbr, int depth) {
     // pix + val + nbr + keys + queues
     return tf_align_up((size_t)R * 8, 256) + tf_align_up((size_t)R * 4, 256) + tf_align_up((size_t)R * 4 * n_nbr, 256)
          + (size_t)(depth + 2) * tf_align_up((size_t)R * 8, 256)          // K2, M1, C_1..C_{d-1}, Rt
-         + 2 * tf_align_up((size_t)R * 8 + 256, 256) + tf_align_up((size_t)R * 4, 256)           // two queues (2R ints), inq
+         + 2 * tf_align_up((size_t)R * 8 + 256, 256)                                             // two queues (2R ints)
          + 5 * tf_align_up((size_t)R * 4, 256) + tf_align_up((size_t)R * 8, 256) + 4096;         // Llo, Lhi, org, rank, sub-graph ids; edge masks
 }
 
@@ -1211,7 +1169,7 @@ extern "C" size_t tf_watershed_workspace_bytes(int64_t T, int64_t H, int64_t W, 
     return ws_full_bytes(N, ws_virtual_voxels(T, H, W)) + ws_compact_bytes(max_relevant, n_nbr, chain_depth);
 }
 
-struct WsQueues { int *q[2]; int *cnt; int *inq; int qcap; int *h_cnt; int64_t *processed; };
+struct WsQueues { int *q[2]; int *cnt; int qcap; int *h_cnt; int64_t *processed; };
 
 // Run one relaxation phase to its fixpoint.  phase_k = 0: K2/M1; otherwise chain level k (k == depth: root).
 // alg_bytes: the algorithmic bytes the timing facility books on this phase's first batch of sweeps.  The flood's figure is
@@ -1223,13 +1181,7 @@ static int ws_run_phase(const WsC &c, int phase_k, int depth, const WsQueues &Q,
 {
     const unsigned nbR = (unsigned)((c.R + 255) / 256);
     const unsigned nb = nbR < 2048u ? nbR : 2048u;
-    // development switches (same labels either way): TF_WS_LOCAL_ROUNDS=<n> (0 = one front step per launch),
-    // TF_WS_DEDUPE=1 (in-queue flags: every pixel at most once per queue, the round-1 scheme)
-    static const int rounds = getenv("TF_WS_LOCAL_ROUNDS") ? atoi(getenv("TF_WS_LOCAL_ROUNDS")) : 4;
-    static const bool dedupe = getenv("TF_WS_DEDUPE") != nullptr;
-    int *inq = dedupe ? Q.inq : nullptr;
     TF_CHECK_HIP(hipMemsetAsync(Q.cnt, 0, (WS_BATCH + 1) * sizeof(int), s));
-    if (dedupe) TF_CHECK_HIP(hipMemsetAsync(Q.inq, 0, (size_t)c.R * sizeof(int), s));
     int64_t sweeps = 0;
     int parity = 0;
     bool first = true;                // the next launch scans every relevant pixel instead of reading a queue
@@ -1245,11 +1197,11 @@ static int ws_run_phase(const WsC &c, int phase_k, int depth, const WsQueues &Q,
                 const int *qin = first ? nullptr : Q.q[parity];
                 const unsigned blocks = first ? nbR : grid_hint;
                 if (phase_k == 0) {
-                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_a<6>, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, inq, Q.qcap, rounds);
-                    else hipLaunchKernelGGL(k_ws_sweep_a<0>, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, inq, Q.qcap, rounds);
+                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_a<6>, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
+                    else hipLaunchKernelGGL(k_ws_sweep_a<0>, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
                 } else {
-                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_chain<6>, dim3(blocks), dim3(256), 0, s, c, phase_k, depth, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, inq, Q.qcap, rounds);
-                    else hipLaunchKernelGGL(k_ws_sweep_chain<0>, dim3(blocks), dim3(256), 0, s, c, phase_k, depth, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, inq, Q.qcap, rounds);
+                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_chain<6>, dim3(blocks), dim3(256), 0, s, c, phase_k, depth, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
+                    else hipLaunchKernelGGL(k_ws_sweep_chain<0>, dim3(blocks), dim3(256), 0, s, c, phase_k, depth, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
                 }
                 parity ^= 1;
                 first = false;
@@ -1261,14 +1213,7 @@ static int ws_run_phase(const WsC &c, int phase_k, int depth, const WsQueues &Q,
         bool done = false, overflow = false;
         // slot b holds the size of the queue consumed by sweep b (slot 0 of a batch that starts with a full scan is
         // unused)
-        static const bool trace = getenv("TF_WS_TRACE") != nullptr;      // development aid: frontier size per sweep
-        if (trace) {
-            fprintf(stderr, "ws_trace phase %d sweeps %lld:", phase_k, (long long)sweeps);
-            for (int b = 0; b <= WS_BATCH; b++) fprintf(stderr, " %d", Q.h_cnt[b]);
-            fprintf(stderr, "\n");
-        }
         for (int b = (scan_batch ? 1 : 0); b <= WS_BATCH; b++) overflow = overflow || Q.h_cnt[b] > Q.qcap;
-        if (overflow && dedupe) { tf_set_error("tf_watershed: frontier queue overflow"); return TF_EHIP; }
         for (int b = (scan_batch ? 1 : 0); b <= WS_BATCH && !overflow; b++) {
             if (Q.h_cnt[b] == 0) { done = true; break; }
             if (b < WS_BATCH) *Q.processed += Q.h_cnt[b];
@@ -1409,7 +1354,7 @@ static void ws_job_free(tf_ws_job *j)
     delete j;
 }
 
-// device -> pinned host, waits
+// device -> pinned host; the caller synchronises the stream
 static int ws_to_host(void *dst, const void *src, size_t bytes, hipStream_t s)
 {
     if (bytes == 0) return TF_OK;
@@ -1427,7 +1372,6 @@ static int ws_job_export(tf_ws_job *j)
     const int64_t R = j->R, N = j->N;
     const int nn = j->n_nbr;
     const unsigned nbr_blocks = (unsigned)((R + 255) / 256);
-    static const bool ref_debug = ws_env("TF_WS_REF_DEBUG");           // development aid: where the detour's time goes
     // A/B and test aid (read per call: the tests toggle it): TF_WS_REFERENCE_DENSE=1 the dense form whatever the seed counts, =2 the plain form
     const char *dense_env = getenv("TF_WS_REFERENCE_DENSE");
     const bool force_dense = dense_env != nullptr;
@@ -1455,7 +1399,7 @@ static int ws_job_export(tf_ws_job *j)
     TF_CHECK_HIP(hipMemcpyAsync(&h_last[1], base_small + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
     TF_CHECK_HIP(hipMemcpyAsync(&h_lastc[0], n_seed + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
     TF_CHECK_HIP(hipMemcpyAsync(&h_lastc[1], n_small + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    // the sub-graph: Q = poppable pixels + their out-neighbours (flags in the idle scan array, ids in the idle in-queue flags)
+    // the sub-graph: Q = poppable pixels + their out-neighbours (flags in the idle scan array, ids in subid)
     uint8_t *in_q = (uint8_t *)j->scan;
     int *subid = j->subid;
     TF_CHECK_HIP(hipMemsetAsync(in_q, 0, (size_t)R, s));
@@ -1476,9 +1420,6 @@ static int ws_job_export(tf_ws_job *j)
         char *tie_base = (char *)j->scan + tf_align_up((size_t)R, 256);
         const size_t tie_room = (size_t)j->NV * 4 > tf_align_up((size_t)R, 256) ? (size_t)j->NV * 4 - tf_align_up((size_t)R, 256) : 0;
         const size_t tie_need = tf_align_up((size_t)S * 8, 256) + 5 * tf_align_up((size_t)S * 4, 256) + 256;
-        if (ref_debug)
-            fprintf(stderr, "reference order: closed form? seed below the tie value %d, floodable pixel below it %d, S %lld, R %lld, room %zu of %zu\n",
-                    h_any[0], h_any[1], (long long)S, (long long)R, tie_room, tie_need);
         if (!force_host && !force_dense && !h_any[0] && !h_any[1] && S > 0 && S <= R && S < 0x3fffffffll && tie_need <= tie_room) {
             long long *stg_k = (long long *)c.Rt; unsigned *stg_val = (unsigned *)c.Llo; int *stg_id = c.Lhi;
             hipLaunchKernelGGL(k_ws_small_list, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, h_vmax,
@@ -1487,7 +1428,6 @@ static int ws_job_export(tf_ws_job *j)
             long long k_max = 0;
             TF_CHECK_HIP(hipMemcpyAsync(&k_max, stg_k + S - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
             TF_CHECK_HIP(hipStreamSynchronize(s));
-            if (ref_debug && k_max >= j->M - S) fprintf(stderr, "reference order: closed form refused: small seed at heap position %lld of %lld\n", k_max, (long long)j->M);
             if (k_max < j->M - S) {                                     // no small seed among the last S positions: every replacement item is large
                 TfArena ta(tie_base, tie_room);
                 WsTie t;
@@ -1525,9 +1465,6 @@ static int ws_job_export(tf_ws_job *j)
                         j->need_replay = false;
                         j->popped = S; j->n_ranked = (int)S;
                         j->ms_export = ws_now_ms() - t_enter;
-                        if (ref_debug)
-                            fprintf(stderr, "reference order: %lld seeds, %lld at the tie value (key %u) and nothing below it: pop ranks on the device "
-                                    "(tree of %d levels), %.1f ms\n", (long long)j->M, (long long)S, h_vmax, n_lev, j->ms_export);
                         return TF_OK;
                     }
                 }
@@ -1541,7 +1478,6 @@ static int ws_job_export(tf_ws_job *j)
     j->nQ = nQ;
     // the small seeds are staged in Rt / Llo / Lhi (idle until the root phase is repeated): R entries each
     j->sparse = !force_dense && j->S <= R;
-    const double t_numbered = ws_now_ms();
     j->hb_val = ws_host_take((size_t)nQ * sizeof(unsigned), true);
     j->hb_nbr = ws_host_take((size_t)nQ * nn * sizeof(int), true);
     j->hb_rank = ws_host_take((size_t)nQ * sizeof(int), true);
@@ -1641,12 +1577,6 @@ static int ws_job_export(tf_ws_job *j)
     }
     j->need_replay = true;
     j->ms_export = ws_now_ms() - t_enter;
-    if (ref_debug)
-        fprintf(stderr, "reference order: %lld seeds, %lld at or below the tie value (key %u), %lld relevant pixels, sub-graph %lld%s, %s form; "
-                "tie value + numbering %.1f ms, export %.1f ms\n", (long long)j->M, (long long)j->S, h_vmax, (long long)R, (long long)nQ,
-                j->identity ? " (whole compact set)" : "", j->sparse ? "sparse" : (j->coded ? "dense (2 bits per seed + exceptions)" : "dense"), t_numbered - t_enter, ws_now_ms() - t_numbered);
-    if (ref_debug && !j->sparse && j->coded)
-        fprintf(stderr, "reference order: modal ballast entry %016llx, %lld exceptions\n", (unsigned long long)j->code_d, (long long)j->n_exc);
     return TF_OK;
 }
 
@@ -1865,7 +1795,7 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
         c.emask = emask;
         WsQueues &Q = j->Q;
         Q.qcap = (int)(2 * R < 0x7fffff00ll ? 2 * R : 0x7fffff00ll);
-        Q.q[0] = ar.take<int>(2 * R + 64); Q.q[1] = ar.take<int>(2 * R + 64); Q.inq = ar.take<int>(R);
+        Q.q[0] = ar.take<int>(2 * R + 64); Q.q[1] = ar.take<int>(2 * R + 64);
         j->subid = ar.take<int>(R);
         Q.cnt = d_flags; Q.h_cnt = j->h_cnt; Q.processed = &st[7];
         if (!ar.ok()) { tf_set_error("tf_watershed: workspace too small"); return TF_ENOMEM; }
@@ -1891,7 +1821,6 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
                 return TF_EINVAL;
             }
         }
-        const unsigned nbr_blocks = (unsigned)((R + 255) / 256);
         // a front advances at least one pixel per sweep, so a phase needs at most "longest flood path" sweeps: bounded by
         // T + H + W times a detour factor on a (T, H, W) grid; the raveled form knows no shape, there the only safe bound
         // is the number of relevant pixels itself (a snake-shaped mask floods one pixel per sweep)
@@ -1909,7 +1838,6 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
             const int rc_x = ws_job_export(j);
             if (rc_x) return rc_x;
         }
-        (void)nbr_blocks;
         j->sweeps_pending = true;
         if (flags & TF_WS_DEFER_SWEEPS) return TF_OK;                               // phase A and the chain levels: tf_watershed_sweeps / finish
         return ws_job_sweeps(j);
@@ -1924,10 +1852,9 @@ static int ws_job_replay(tf_ws_job *j)
     if (!j->need_replay || j->replay_done) return j->replay_rc;
     const double t0 = ws_now_ms();
     int n_ranked = 0;
-    double phase[2] = {0.0, 0.0};
     if (j->sparse)
         j->popped = ws_reference_ranks_sparse(j->M, j->S, (const long long *)j->hb_sk.p, (const unsigned *)j->hb_sval.p, (const int *)j->hb_sid.p,
-                                              j->nQ, (const unsigned *)j->hb_val.p, (const int *)j->hb_nbr.p, j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked, phase);
+                                              j->nQ, (const unsigned *)j->hb_val.p, (const int *)j->hb_nbr.p, j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked);
     else {
         const WsSeedCodes codes{(const uint32_t *)j->hb_sval.p, (const uint32_t *)j->hb_sval.p + (j->coded ? j->code_words : 0), j->code_d, (const u64 *)j->hb_sid.p};
         if (j->plain) {
@@ -1936,15 +1863,12 @@ static int ws_job_replay(tf_ws_job *j)
                                                  (const int *)j->hb_nbr.p, j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked);
         } else
             j->popped = ws_reference_ranks_dense(j->M, (u64 *)j->hb_sk.p, j->nQ, (const unsigned *)j->hb_val.p, (const int *)j->hb_nbr.p,
-                                                 j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked, phase, j->coded ? &codes : nullptr);
+                                                 j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked, j->coded ? &codes : nullptr);
     }
     j->n_ranked = n_ranked;
     j->replay_done = true;
     j->ms_replay = ws_now_ms() - t0;
     if (j->popped < 0) { tf_set_error("tf_watershed: out of host memory for the reference-order replay"); j->replay_rc = TF_ENOMEM; }
-    static const bool ref_debug = ws_env("TF_WS_REF_DEBUG");
-    if (ref_debug) fprintf(stderr, "reference order: %s%s replay %.1f ms (%lld pops, %d markers ranked; heap build %.1f ms, pops %.1f ms)\n", j->speculative ? "speculative " : "",
-                           j->sparse ? "sparse" : (j->plain ? "plain" : "dense"), j->ms_replay, (long long)j->popped, n_ranked, phase[0], phase[1]);
     return j->replay_rc;
 }
 
@@ -1970,7 +1894,6 @@ static int ws_job_finish(tf_ws_job *j, int32_t *labels, uint8_t *amb_out)
     const WsC &c = j->c;
     const int64_t R = j->R, N = j->N;
     const unsigned nb1 = (unsigned)((N + 255) / 256);
-    static const bool ref_debug = ws_env("TF_WS_REF_DEBUG");
     bool ranked = j->ranked;                                             // root keys are (pop rank << 32) | compact id
     if (R > 0 && j->sweeps_pending) {                                    // TF_WS_DEFER_SWEEPS and nobody has called tf_watershed_sweeps
         const int rc_s = ws_job_sweeps(j);
@@ -2033,7 +1956,6 @@ static int ws_job_finish(tf_ws_job *j, int32_t *labels, uint8_t *amb_out)
                 // the host replay (ws_reference_ranks*) gives the reference's order, and the root phase is repeated with the
                 // pop rank in place of the raster index.  Chain levels, origins and label sets do not depend on that order,
                 // only the choice among tying candidates does.
-                if (ref_debug && ranked) fprintf(stderr, "reference order: the guessed tie value (key %u) was too low (true key %u): export again\n", j->vmax, h_vmax);
                 ws_host_give(j->hb_val); ws_host_give(j->hb_nbr); ws_host_give(j->hb_rank);
                 ws_host_give(j->hb_sk); ws_host_give(j->hb_sval); ws_host_give(j->hb_sid);
                 j->need_replay = false; j->replay_done = false; j->speculative = false; j->replay_rc = TF_OK;

@@ -21,7 +21,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <utility>
 #include <vector>
 
@@ -176,11 +175,8 @@ struct WsPosMap {                                                       // open 
 };
 
 static int64_t ws_reference_ranks_sparse(int64_t M, int64_t S, const long long *sk, const unsigned *sval, const int *sid, int64_t nQ,
-                                         const unsigned *val, const int *nbr, int n_nbr, unsigned vmax, int *rank, int *n_ranked_out,
-                                         double *phase_ms = nullptr)
+                                         const unsigned *val, const int *nbr, int n_nbr, unsigned vmax, int *rank, int *n_ranked_out)
 {
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double t_start = now_ms();
     // an item = (key, id) with key = (v << 32) | age: `smaller` (:161-164) is the order of the keys.  LARGE = the all-ones
     // key: larger than every small item (value keys stop at that of +inf, NaN fields are refused), equal to itself -- a
     // sift never swaps two of them, which is all the replay needs to know about the large items.
@@ -263,7 +259,6 @@ static int64_t ws_reference_ranks_sparse(int64_t M, int64_t S, const long long *
         }
         store(child, e);
     };
-    const double t_alloc = now_ms();
     // (round 5: the bitmap words of a seed's position, of its parent and of its grandparent -- the cold bottom of its chain; the
     // levels above are shared with its neighbours and stay cached -- are requested a few seeds ahead: the build was paced by
     // those misses, two 56 MB bitmaps per 16 x 5424^2 window)
@@ -279,8 +274,6 @@ static int64_t ws_reference_ranks_sparse(int64_t M, int64_t S, const long long *
         push_small((int64_t)sk[j], Item{(u64)sval[j] << 32, sid[j], 0});     // seed k enters at position k, age 0
     }
     hint_on = false;
-    if (phase_ms) phase_ms[0] = now_ms() - t_start;
-    if (getenv("WSR_DEBUG")) fprintf(stderr, "sparse: scratch %.1f ms, %lld pushes %.1f ms, table of items with an id / another value: %zu entries\n", t_alloc - t_start, (long long)S, now_ms() - t_alloc, deep.n);
     int64_t items = M;
     for (int64_t i = 0; i < nQ; i++) rank[i] = -1;
     int64_t age = 1, popped = 0;
@@ -358,7 +351,6 @@ static int64_t ws_reference_ranks_sparse(int64_t M, int64_t S, const long long *
             items += 1;
         }
     }
-    if (phase_ms) phase_ms[1] = now_ms() - t_start - phase_ms[0];
     *n_ranked_out = n_ranked;
     free(occ); free(expl); free(state);
     return oom ? -1 : popped;
@@ -397,15 +389,12 @@ static void wsr_expand(int64_t M, const WsSeedCodes &c, wsr_u64 *h) {
 
 // `codes` != nullptr: h[0 .. M) is written here, from the codes, as the build goes (no pass of its own)
 static int64_t ws_reference_ranks_dense(int64_t M, wsr_u64 *h, int64_t nQ, const unsigned *val, const int *nbr, int n_nbr,
-                                        unsigned vmax, int *rank, int *n_ranked_out, double *phase_ms = nullptr,
-                                        const WsSeedCodes *codes = nullptr)
+                                        unsigned vmax, int *rank, int *n_ranked_out, const WsSeedCodes *codes = nullptr)
 {
     typedef wsr_u64 u64;
     uint8_t *state = (uint8_t *)calloc((size_t)(nQ > 0 ? nQ : 1), 1);                          // 1: already pushed
     int *pushed_id = (int *)malloc((size_t)(nQ + 2) * sizeof(int));                           // id of the pixel pushed with age a
     if (!state || !pushed_id) { free(state); free(pushed_id); return -1; }
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double t_start = now_ms();
     // build: _watershed.pyx:120-152 for arrival k = 1 .. M - 1 (position k holds seed k already)
     int64_t j_exc = 0;
     if (codes && M > 0) h[0] = wsr_next_entry(*codes, 0, j_exc);
@@ -425,7 +414,6 @@ static int64_t ws_reference_ranks_dense(int64_t M, wsr_u64 *h, int64_t nQ, const
         }
         h[child] = e;
     }
-    const double t_built = now_ms();
     for (int64_t i = 0; i < nQ; i++) rank[i] = -1;
     int64_t items = M, age = 1, popped = 0;
     int n_ranked = 0;
@@ -534,7 +522,6 @@ static int64_t ws_reference_ranks_dense(int64_t M, wsr_u64 *h, int64_t nQ, const
             else { h[items] = WSR_LARGE; items += 1; }
         }
     }
-    if (phase_ms) { phase_ms[0] = t_built - t_start; phase_ms[1] = now_ms() - t_built; }
     *n_ranked_out = n_ranked;
     free(state); free(pushed_id);
     return popped;
