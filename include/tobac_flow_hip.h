@@ -257,6 +257,45 @@ int tf_convolve(const void *data, int data_type, int64_t T, int64_t H, int64_t W
                 int interp, double fill, int func, void *out, int out_type,
                 int64_t t0, int64_t t1, void *stream);
 
+/* ---- a8-a10 by name: the step-level functions of tobac_flow/convolve.py -----------------------------
+ * The arithmetic of tf_convolve's STACK form in the reference's general shape: separate frames, an image that need
+ * not have the flow's shape, an explicit grid, any list of offsets, a (3, m, n) structure.  All three run on the
+ * caller's stream, allocate no device memory and do not synchronise.  Offsets are host arrays; a list of any length
+ * is served (the kernels take them 32 at a time).  Element types: images TF_F32 or TF_I32 (TF_I32 requires
+ * TF_INTERP_NEAREST), out_type TF_F32, TF_F64 or TF_I32 (the sample is cast on store).  Every shape extent < 2^15.
+ *
+ * tf_warp_offsets: tobac_flow/convolve.py:8-86 warp_flow.
+ *   img      (h, w)
+ *   flow     (H, W, 2) float; (H, W) may differ from (h, w)
+ *   grid     (H, W, 2) int32 (x, y) on the device, or NULL for the pixel index (convolve.py:59-63)
+ *   offsets  (K, 2) host floats (x, y)
+ *   out      (K, H, W): out[k] = cv2.remap(img, map_k, interp, BORDER_CONSTANT, fill) with, per component,
+ *            map_k = (float)((double)(flow + offsets[k]) + (double)grid), the sum in brackets in float32 */
+int tf_warp_offsets(const void *img, int img_type, int64_t h, int64_t w, const float *flow, const int32_t *grid,
+                    int64_t H, int64_t W, const float *offsets_host, int64_t K, int interp, double fill,
+                    void *out, int out_type, void *stream);
+
+/* tf_gather_offsets: tobac_flow/convolve.py:89-144 convolve_same_step.
+ *   img      (h, w)
+ *   grid     (H, W, 2) int32 (x, y) on the device, or NULL for the pixel index of an (H, W) raster
+ *   offsets  (K, 2) host int32 (x, y)
+ *   out      (K, H, W): out[k] = img[grid.y + offsets[k].y, grid.x + offsets[k].x], `fill` where that is outside img */
+int tf_gather_offsets(const void *img, int img_type, int64_t h, int64_t w, const int32_t *grid, int64_t H, int64_t W,
+                      const int32_t *offsets_host, int64_t K, double fill, void *out, int out_type, void *stream);
+
+/* tf_convolve_step: tobac_flow/convolve.py:147-245 convolve_step.
+ *   prev, same, next  three separate (H, W) frames of data_type (prev / next may be NULL when plane 0 / 2 of the
+ *                     structure is empty, and so may bwd / fwd)
+ *   fwd, bwd          (H, W, 2) float: flow from this step to the next / to the previous one
+ *   grid              (H, W, 2) int32 or NULL, as above
+ *   structure         3 * m * n host bytes, (3, m, n) C order, non-zero = tap present; the offset of entry (row, col) is
+ *                     (x, y) = (col - m / 2, row - n / 2), the reference's centre (convolve.py:203) as it applies it
+ *   out               (n_struct, H, W): taps of plane 0 warped from prev through bwd, then the same-step taps of plane 1,
+ *                     then the taps of plane 2 warped from next through fwd; within a plane in C (np.where) order */
+int tf_convolve_step(const void *prev, const void *same, const void *next, int data_type, int64_t H, int64_t W,
+                     const float *fwd, const float *bwd, const int32_t *grid, const uint8_t *structure_host,
+                     int64_t m, int64_t n, int interp, double fill, void *out, int out_type, void *stream);
+
 /* ---- a17 piece: combined edge field --------------------------------------------------------------
  * the elementwise tail of tobac_flow/detection.py:620-642 get_combined_edge_field:
  * edges[edges > 0] += 1; edges -= field; edges[isnan(field)] = inf, in float64 like the reference;

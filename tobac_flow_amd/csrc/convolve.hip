@@ -17,6 +17,7 @@
 __constant__ float c_tf_lanczos[32][8];
 #include "remap_dev.h"
 #include <type_traits>
+#include <vector>
 #include <stdlib.h>
 #include <math.h>
 #include <float.h>
@@ -457,6 +458,198 @@ extern "C" int tf_convolve(const void *data, int data_type, int64_t T, int64_t H
     if (out_type == TF_F64)
         return launch_convolve<double>(data, T, (int)H, (int)W, fwd, bwd, tp, interp, fill, func, out, out_type, t0, t1, s);
     return launch_convolve<float>(data, T, (int)H, (int)W, fwd, bwd, tp, interp, fill, func, out, out_type, t0, t1, s);
+}
+
+// ---- step-level API: convolve.py:8-86 warp_flow, :89-144 convolve_same_step, :147-245 convolve_step ----------
+// The same arithmetic as k_convolve's STACK branch in the reference's general form: the image is an array of its own
+// (h, w) that need not have the flow's shape (H, W), the grid may be given (full-frame coordinates of a crop), the
+// taps are an arbitrary (K, 2) list.  One thread per output pixel reads its flow vector and grid entry ONCE and loops
+// over the taps; every sample is tf_remap / tf_remap_nearest as it stands, so no result moves by a bit.  The taps
+// travel as a kernel argument, TF_STEP_TAP_CAP at a time; a longer list takes further launches into the following
+// planes of the output.
+#define TF_STEP_TAP_CAP 32
+struct WarpTaps { int n; float ox[TF_STEP_TAP_CAP], oy[TF_STEP_TAP_CAP]; };
+struct GatherTaps { int n; int ox[TF_STEP_TAP_CAP], oy[TF_STEP_TAP_CAP]; };
+
+// tf_loc with a float offset (convolve.py:56-63: float32 flow + float32 offset, then the in-place += of an int64 grid,
+// which numpy evaluates in double and rounds back to float32)
+__device__ __forceinline__ float tf_loc_f(float flow, float off, int grid) {
+    float l = flow + off;
+    return (float)((double)l + (double)grid);
+}
+
+template <int METHOD, typename In>
+__global__ void __launch_bounds__(256)
+k_warp_offsets(const In *__restrict__ img, int h, int w, const float *__restrict__ flow, const int32_t *__restrict__ grid,
+               int H, int W, WarpTaps tp, double fill, void *__restrict__ out, int out_type, int64_t plane0)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const int64_t plane = (int64_t)H * W, pix = (int64_t)y * W + x;
+    const In fillv = (In)fill;
+    const float2 f = ((const float2 *)flow)[pix];
+    int gx = x, gy = y;
+    if (grid) { const int2 g = ((const int2 *)grid)[pix]; gx = g.x; gy = g.y; }
+    for (int k = 0; k < tp.n; k++) {
+        const float mx = tf_loc_f(f.x, tp.ox[k], gx), my = tf_loc_f(f.y, tp.oy[k], gy);
+        In v;
+        if constexpr (std::is_same<In, int32_t>::value) v = tf_remap_nearest<int32_t>(img, h, w, mx, my, fillv);
+        else v = tf_remap<METHOD>(img, h, w, mx, my, fillv);
+        store_out<In>(out, out_type, (plane0 + k) * plane + pix, v);
+    }
+}
+
+// same step: integer gather at grid + offset, out of the image -> fill
+template <typename In>
+__global__ void __launch_bounds__(256)
+k_gather_offsets(const In *__restrict__ img, int h, int w, const int32_t *__restrict__ grid, int H, int W,
+                 GatherTaps tp, double fill, void *__restrict__ out, int out_type, int64_t plane0)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const int64_t plane = (int64_t)H * W, pix = (int64_t)y * W + x;
+    const In fillv = (In)fill;
+    int gx = x, gy = y;
+    if (grid) { const int2 g = ((const int2 *)grid)[pix]; gx = g.x; gy = g.y; }
+    for (int k = 0; k < tp.n; k++) {
+        const int64_t xx = (int64_t)gx + tp.ox[k], yy = (int64_t)gy + tp.oy[k];
+        const In v = (xx < 0 || yy < 0 || xx >= w || yy >= h) ? fillv : img[yy * w + xx];
+        store_out<In>(out, out_type, (plane0 + k) * plane + pix, v);
+    }
+}
+
+template <typename In>
+static int launch_warp_offsets(const In *img, int h, int w, const float *flow, const int32_t *grid, int H, int W,
+                               const float *offsets, int64_t K, int interp, double fill, void *out, int out_type,
+                               int64_t plane0, hipStream_t s)
+{
+    TfProfScope ps(TFK_CONVOLVE, (4.0 + 8.0 + (grid ? 8.0 : 0.0) + (out_type == TF_F64 ? 8.0 : 4.0) * (double)K) * (double)H * W, s);
+    dim3 block(64, 4, 1), grid_dim((W + 63) / 64, (H + 3) / 4, 1);
+    for (int64_t k0 = 0; k0 < K; k0 += TF_STEP_TAP_CAP) {
+        WarpTaps tp;
+        tp.n = (int)(K - k0 < TF_STEP_TAP_CAP ? K - k0 : TF_STEP_TAP_CAP);
+        for (int k = 0; k < TF_STEP_TAP_CAP; k++) {
+            tp.ox[k] = k < tp.n ? offsets[2 * (k0 + k)] : 0.f;
+            tp.oy[k] = k < tp.n ? offsets[2 * (k0 + k) + 1] : 0.f;
+        }
+        if constexpr (std::is_same<In, int32_t>::value) {
+            hipLaunchKernelGGL((k_warp_offsets<TF_INTERP_NEAREST, In>), grid_dim, block, 0, s, img, h, w, flow, grid, H, W, tp, fill, out, out_type, plane0 + k0);
+        } else {
+            switch (interp) {
+            case TF_INTERP_NEAREST:
+                hipLaunchKernelGGL((k_warp_offsets<TF_INTERP_NEAREST, In>), grid_dim, block, 0, s, img, h, w, flow, grid, H, W, tp, fill, out, out_type, plane0 + k0); break;
+            case TF_INTERP_LINEAR:
+                hipLaunchKernelGGL((k_warp_offsets<TF_INTERP_LINEAR, In>), grid_dim, block, 0, s, img, h, w, flow, grid, H, W, tp, fill, out, out_type, plane0 + k0); break;
+            case TF_INTERP_LANCZOS:
+                hipLaunchKernelGGL((k_warp_offsets<TF_INTERP_LANCZOS, In>), grid_dim, block, 0, s, img, h, w, flow, grid, H, W, tp, fill, out, out_type, plane0 + k0); break;
+            default:
+                hipLaunchKernelGGL((k_warp_offsets<TF_INTERP_CUBIC, In>), grid_dim, block, 0, s, img, h, w, flow, grid, H, W, tp, fill, out, out_type, plane0 + k0); break;
+            }
+        }
+        TF_CHECK_LAUNCH();
+    }
+    return TF_OK;
+}
+
+template <typename In>
+static int launch_gather_offsets(const In *img, int h, int w, const int32_t *grid, int H, int W, const int32_t *offsets,
+                                 int64_t K, double fill, void *out, int out_type, int64_t plane0, hipStream_t s)
+{
+    TfProfScope ps(TFK_CONVOLVE, ((grid ? 8.0 : 0.0) + (4.0 + (out_type == TF_F64 ? 8.0 : 4.0)) * (double)K) * (double)H * W, s);
+    dim3 block(64, 4, 1), grid_dim((W + 63) / 64, (H + 3) / 4, 1);
+    for (int64_t k0 = 0; k0 < K; k0 += TF_STEP_TAP_CAP) {
+        GatherTaps tp;
+        tp.n = (int)(K - k0 < TF_STEP_TAP_CAP ? K - k0 : TF_STEP_TAP_CAP);
+        for (int k = 0; k < TF_STEP_TAP_CAP; k++) {
+            tp.ox[k] = k < tp.n ? offsets[2 * (k0 + k)] : 0;
+            tp.oy[k] = k < tp.n ? offsets[2 * (k0 + k) + 1] : 0;
+        }
+        hipLaunchKernelGGL((k_gather_offsets<In>), grid_dim, block, 0, s, img, h, w, grid, H, W, tp, fill, out, out_type, plane0 + k0);
+        TF_CHECK_LAUNCH();
+    }
+    return TF_OK;
+}
+
+static int warp_offsets(const void *img, int img_type, int h, int w, const float *flow, const int32_t *grid, int H, int W,
+                        const float *offsets, int64_t K, int interp, double fill, void *out, int out_type,
+                        int64_t plane0, hipStream_t s)
+{
+    if (img_type == TF_I32)
+        return launch_warp_offsets<int32_t>((const int32_t *)img, h, w, flow, grid, H, W, offsets, K, interp, fill, out, out_type, plane0, s);
+    return launch_warp_offsets<float>((const float *)img, h, w, flow, grid, H, W, offsets, K, interp, fill, out, out_type, plane0, s);
+}
+
+static int gather_offsets(const void *img, int img_type, int h, int w, const int32_t *grid, int H, int W,
+                          const int32_t *offsets, int64_t K, double fill, void *out, int out_type, int64_t plane0, hipStream_t s)
+{
+    if (img_type == TF_I32)
+        return launch_gather_offsets<int32_t>((const int32_t *)img, h, w, grid, H, W, offsets, K, fill, out, out_type, plane0, s);
+    return launch_gather_offsets<float>((const float *)img, h, w, grid, H, W, offsets, K, fill, out, out_type, plane0, s);
+}
+
+#define TF_STEP_SHAPE_OK(a, b) ((a) > 0 && (b) > 0 && (a) < (1 << 15) && (b) < (1 << 15))
+
+extern "C" int tf_warp_offsets(const void *img, int img_type, int64_t h, int64_t w, const float *flow, const int32_t *grid,
+                               int64_t H, int64_t W, const float *offsets_host, int64_t K, int interp, double fill,
+                               void *out, int out_type, void *stream)
+{
+    TF_REQUIRE(img && flow && offsets_host && out, "tf_warp_offsets: null pointer");
+    TF_REQUIRE(TF_STEP_SHAPE_OK(h, w) && TF_STEP_SHAPE_OK(H, W), "tf_warp_offsets: bad shape");
+    TF_REQUIRE(K > 0, "tf_warp_offsets: empty offset list");
+    TF_REQUIRE(interp >= TF_INTERP_NEAREST && interp <= TF_INTERP_LANCZOS, "tf_warp_offsets: bad interp");
+    TF_REQUIRE(img_type == TF_F32 || img_type == TF_I32, "tf_warp_offsets: img_type must be f32 or i32");
+    TF_REQUIRE(out_type >= TF_F32 && out_type <= TF_I32, "tf_warp_offsets: bad out_type");
+    TF_REQUIRE(img_type != TF_I32 || interp == TF_INTERP_NEAREST, "tf_warp_offsets: int32 data needs nearest");
+    if (interp == TF_INTERP_LANCZOS) { const int rc = ensure_lanczos_table(); if (rc) return rc; }
+    return warp_offsets(img, img_type, (int)h, (int)w, flow, grid, (int)H, (int)W, offsets_host, K, interp, fill, out, out_type, 0,
+                        (hipStream_t)stream);
+}
+
+extern "C" int tf_gather_offsets(const void *img, int img_type, int64_t h, int64_t w, const int32_t *grid, int64_t H, int64_t W,
+                                 const int32_t *offsets_host, int64_t K, double fill, void *out, int out_type, void *stream)
+{
+    TF_REQUIRE(img && offsets_host && out, "tf_gather_offsets: null pointer");
+    TF_REQUIRE(TF_STEP_SHAPE_OK(h, w) && TF_STEP_SHAPE_OK(H, W), "tf_gather_offsets: bad shape");
+    TF_REQUIRE(K > 0, "tf_gather_offsets: empty offset list");
+    TF_REQUIRE(img_type == TF_F32 || img_type == TF_I32, "tf_gather_offsets: img_type must be f32 or i32");
+    TF_REQUIRE(out_type >= TF_F32 && out_type <= TF_I32, "tf_gather_offsets: bad out_type");
+    return gather_offsets(img, img_type, (int)h, (int)w, grid, (int)H, (int)W, offsets_host, K, fill, out, out_type, 0, (hipStream_t)stream);
+}
+
+extern "C" int tf_convolve_step(const void *prev, const void *same, const void *next, int data_type, int64_t H, int64_t W,
+                                const float *fwd, const float *bwd, const int32_t *grid, const uint8_t *structure_host,
+                                int64_t m, int64_t n, int interp, double fill, void *out, int out_type, void *stream)
+{
+    TF_REQUIRE(structure_host && out, "tf_convolve_step: null pointer");
+    TF_REQUIRE(TF_STEP_SHAPE_OK(H, W), "tf_convolve_step: bad shape");
+    TF_REQUIRE(TF_STEP_SHAPE_OK(m, n), "tf_convolve_step: bad structure shape");
+    TF_REQUIRE(interp >= TF_INTERP_NEAREST && interp <= TF_INTERP_LANCZOS, "tf_convolve_step: bad interp");
+    TF_REQUIRE(data_type == TF_F32 || data_type == TF_I32, "tf_convolve_step: data_type must be f32 or i32");
+    TF_REQUIRE(out_type >= TF_F32 && out_type <= TF_I32, "tf_convolve_step: bad out_type");
+    TF_REQUIRE(data_type != TF_I32 || interp == TF_INTERP_NEAREST, "tf_convolve_step: int32 data needs nearest");
+    // convolve.py:203-234: offsets = np.where(structure[k])[..., ::-1] - [m // 2, n // 2], i.e. the centre of the ROW axis is
+    // taken from the column index and the other way round (no difference for m == n)
+    const int cx = (int)(m / 2), cy = (int)(n / 2);
+    std::vector<float> fo[3];
+    std::vector<int32_t> io;
+    for (int p = 0; p < 3; p++)
+        for (int64_t r = 0; r < m; r++)
+            for (int64_t c = 0; c < n; c++)
+                if (structure_host[(p * m + r) * n + c]) {
+                    if (p == 1) { io.push_back((int32_t)c - cx); io.push_back((int32_t)r - cy); }
+                    else { fo[p].push_back((float)((int)c - cx)); fo[p].push_back((float)((int)r - cy)); }
+                }
+    const int64_t nb = (int64_t)fo[0].size() / 2, ns = (int64_t)io.size() / 2, nf = (int64_t)fo[2].size() / 2;
+    TF_REQUIRE(nb + ns + nf > 0, "tf_convolve_step: empty structure");
+    TF_REQUIRE((!nb || (prev && bwd)) && (!ns || same) && (!nf || (next && fwd)), "tf_convolve_step: null pointer");
+    if (interp == TF_INTERP_LANCZOS && nb + nf) { const int rc = ensure_lanczos_table(); if (rc) return rc; }
+    hipStream_t s = (hipStream_t)stream;
+    const int h = (int)H, w = (int)W;
+    int rc = TF_OK;
+    if (nb) rc = warp_offsets(prev, data_type, h, w, bwd, grid, h, w, fo[0].data(), nb, interp, fill, out, out_type, 0, s);
+    if (!rc && ns) rc = gather_offsets(same, data_type, h, w, grid, h, w, io.data(), ns, fill, out, out_type, nb, s);
+    if (!rc && nf) rc = warp_offsets(next, data_type, h, w, fwd, grid, h, w, fo[2].data(), nf, interp, fill, out, out_type, nb + ns, s);
+    return rc;
 }
 
 // ---- single-image warp and forward/backward smoothing -----------------------------------------
