@@ -597,6 +597,39 @@ int tf_window_overlap_pairs(const int32_t *left, const int32_t *right, int64_t n
 size_t tf_label_stats_workspace_bytes(int64_t n_labels);
 int tf_label_stats(const int32_t *labels, const float *field, const float *weights, int64_t n, int64_t n_labels,
                    double *out, void *ws, size_t ws_bytes, void *stream);
+/* tf_label_props: tobac_flow/dataset.py:705-1595 (`calculate_label_properties`) -- everything that function derives from
+ *   ONE int32 (T, H, W) label volume, in one read of it: per label id 0 .. n_labels a record of 8 doubles (64 B) on the
+ *   device, acc[id * 8 + k]:
+ *     k = 0  number of voxels, stored as an int64 (np.bincount)
+ *     k = 1  sum of area[y, x] over the voxels whose area is not NaN (labeled_comprehension(area, np.nansum))
+ *     k = 2  sum of area[y, x], NaN propagating (the denominator of np.average(..., weights=area))
+ *     k = 3 .. 6  sum of area * x[x], area * y[y], area * lat[y, x], area * lon[y, x], NaN propagating
+ *     k = 7  two int32: the smallest and the largest t_rank[t] of the label's frames (0x7fffffff / -1 where it has none)
+ *   area, lat, lon: (H, W) doubles; x: (W,), y: (H,) doubles; t_rank: (T,) int32 >= 0 -- the operands as they are, never
+ *   broadcast to the volume; besides the labels nothing of T * H * W elements is read or allocated.  A NULL operand
+ *   switches its sums off (they stay 0; NULL area switches k = 1 .. 6 off, NULL t_rank k = 7).  Ids outside
+ *   [1, n_labels] are skipped, so record 0 stays empty.  Shape contract as tf_label_extent (T < 65536); 64-bit indexing.
+ *   The sums are double atomics, one set per run of equal labels inside a lane's 16 voxels of a row: as with
+ *   tf_label_stats the last bits of a sum depend on arrival order and can differ from run to run (N terms: N * 2^-53
+ *   relative for terms of one sign); counts and the two ranks are exact. */
+int tf_label_props(const int32_t *labels, int64_t T, int64_t H, int64_t W, int64_t n_labels,
+                   const double *area, const double *x, const double *y, const double *lat, const double *lon,
+                   const int32_t *t_rank, double *acc, void *stream);
+/* tf_unique_along_t / tf_unique_per_frame: tobac_flow/utils/stats_utils.py:23-30 (`n_unique_along_axis`, which equals the
+ *   number of DISTINCT NON-ZERO values along the axis) together with np.count_nonzero, as tobac_flow/analysis.py:245-290
+ *   (`get_label_stats`) uses them.  Both are exact.
+ *   along t: per pixel of an int32 (T, H, W) volume, unique[H * W] and nonzero[H * W] (int32).  Any int32 values.  The
+ *     per-pixel set of values met so far has room for T entries; it lives in LDS for T <= 640 (*lanes_host = pixels per
+ *     workgroup, 256 / 128 / 64) and otherwise in the workspace (T * H * W int32, *lanes_host = 0);
+ *     tf_unique_along_t_workspace_bytes returns 0 when none is needed.
+ *   per frame: per frame of an int32 (T, hw) volume, unique[T] (int32) = distinct ids in [1, n_labels] and nonzero[T]
+ *     (int64) = voxels != 0.  The workspace holds one int32 per id. */
+size_t tf_unique_along_t_workspace_bytes(int64_t T, int64_t H, int64_t W);
+int tf_unique_along_t(const int32_t *vol, int64_t T, int64_t H, int64_t W, int32_t *unique, int32_t *nonzero,
+                      int *lanes_host, void *ws, size_t ws_bytes, void *stream);
+size_t tf_unique_per_frame_workspace_bytes(int64_t n_labels);
+int tf_unique_per_frame(const int32_t *vol, int64_t T, int64_t hw, int64_t n_labels, int32_t *unique, int64_t *nonzero,
+                        void *ws, size_t ws_bytes, void *stream);
 size_t tf_slice_labels_workspace_bytes(int64_t T, int64_t id_capacity);
 int tf_slice_labels(const int32_t *labels, int64_t T, int64_t hw, int32_t *out, int64_t *n_step_labels_host,
                     void *ws, size_t ws_bytes, void *stream);

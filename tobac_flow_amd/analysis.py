@@ -1,7 +1,8 @@
 """Label filters used by the detection recipes (host glue; mirrors the first three groups of
 /root/reference/tobac_flow/analysis.py:15-201) and the per-label statistics of analysis.py:204-245 / 293-376 as
-segmented reductions on the GPU (tf_label_stats).  The coverage / unique-count maps of analysis.py:248-290 and the
-xarray packaging (names, long_name, units attributes) are out of scope: xarray is not in this image."""
+segmented reductions on the GPU (tf_label_stats), and the coverage / unique-count maps of analysis.py:245-290
+(get_label_stats: tf_unique_along_t, tf_unique_per_frame).  The xarray packaging (long_name, units attributes) is out of
+scope: xarray is not in this image."""
 import numpy as np
 from scipy import ndimage as ndi
 
@@ -127,3 +128,38 @@ def weighted_statistics_on_labels(labels, da, weights, name=None, dim=None, dtyp
     """Weighted mean, weighted standard deviation, and the max / min over the positively weighted values of `da` for every
     label 1 .. max, NaN values ignored, NaN for labels without weight (reference: analysis.py:293-376)."""
     return _label_stats(labels, da, weights, dtype)
+
+
+def get_label_stats(da, ds, name=None):
+    """Coverage and unique-count maps of a (t, y, x) label volume, added to `ds` (reference: analysis.py:245-290):
+    `{name}_fraction` (y, x) float32 = count_nonzero(da, 0) / T, `{name}_unique_count` (y, x) int32 = distinct non-zero
+    labels along t, `{name}_temporal_fraction` (t,) float32 = count_nonzero(da, (1, 2)) / (Y * X) and
+    `{name}_temporal_unique_count` (t,) int32 = distinct non-zero labels per frame.  `da` is the name of a variable of
+    `ds`, or an array / device tensor together with `name=` (there is no DataArray.name here).  Four reads of the volume
+    on the GPU: its smallest and largest value (the per-frame kernel is sized by the largest id), then one counting pass
+    per direction; both counts are exact."""
+    from tobac_flow_amd import _lib
+    from tobac_flow_amd import label as _label
+    from tobac_flow_amd.utils.stats_utils import _sorted_form, _stamps_fit
+    if isinstance(da, str):
+        name = da if name is None else name
+        da = ds[da]
+    if name is None:
+        raise ValueError("get_label_stats: an array needs name= (there is no DataArray.name here)")
+    if len(da.shape) != 3:
+        raise ValueError("get_label_stats: the labels must be a (t, y, x) volume")
+    T, Y, X = (int(n) for n in da.shape)
+    tensor = _lib.is_tensor(da)
+    integer = (not da.dtype.is_floating_point and not da.dtype.is_complex) if tensor else np.asarray(da).dtype.kind in "iu"
+    lo, hi = (int(da.min()), int(da.max())) if integer and T * Y * X else (0, 0)
+    if integer and T * Y * X and T < 65536 and _stamps_fit(lo, hi, T * Y * X):
+        unique, count, _ = _label.unique_along_t(da)
+        t_unique, t_count = _label.unique_per_frame(da, hi)
+    else:                                                          # not a label volume: counted on the host
+        host = _lib.to_host(da) if tensor else np.asarray(da)
+        unique, count = _sorted_form(host, 0), np.count_nonzero(host, 0)
+        t_unique, t_count = _sorted_form(host.reshape([T, -1]), 1), np.count_nonzero(host, (1, 2))
+    ds.add(f"{name}_fraction", count / T, ("y", "x"), np.float32)
+    ds.add(f"{name}_unique_count", unique, ("y", "x"), np.int32)
+    ds.add(f"{name}_temporal_fraction", t_count / (X * Y), ("t",), np.float32)
+    ds.add(f"{name}_temporal_unique_count", t_unique, ("t",), np.int32)

@@ -1,4 +1,4 @@
-"""The label contract of the detection output files, at array level (mirrors /root/reference/tobac_flow/dataset.py:189-702).
+"""The label contract of the detection output files, at array level (mirrors /root/reference/tobac_flow/dataset.py:189-1595).
 
 After detection the drop-in scripts (scripts/dcc_detect_goes.py:316-330) derive, from the three label volumes
 `core_label`, `thick_anvil_label`, `thin_anvil_label`, the variables every later stage (linking.py, analysis.py) reads:
@@ -226,5 +226,156 @@ def flag_nan_adjacent_labels(dataset, da):
         dataset.add(kind + "_nan_flag", _flags(dataset.coords[dim], ids), (dim,), bool)
 
 
+def _group_heads(order, parent_sorted, parents):
+    """position (in the step arrays) of the first entry of every parent's group in `order`; ValueError for a parent
+    without a group, as the reference's argmax / nanmin of an empty selection raises"""
+    parents = np.asarray(parents)
+    head = np.ones(order.size, bool)
+    head[1:] = parent_sorted[1:] != parent_sorted[:-1]
+    group_parent, group_first = parent_sorted[head], order[head]
+    pos = np.searchsorted(group_parent, parents)
+    ok = pos < group_parent.size
+    ok[ok] = group_parent[pos[ok]] == parents[ok]
+    if not np.all(ok):
+        raise ValueError(f"attempt to reduce over an empty sequence: label {int(parents[~ok][0])} has no step")
+    return group_first[pos]
+
+
+def _first_max_step(step_ids, step_parent, step_area, parents):
+    """For every id in `parents`: the position in the step arrays of its step of maximal area, chosen as
+    `step[parent == i][np.argmax(area[parent == i])]` chooses on an ascending step coordinate (dataset.py:771-778): a NaN
+    area wins, the one with the smallest step id first; otherwise the smallest step id among the maxima."""
+    step_ids, step_parent = np.asarray(step_ids), np.asarray(step_parent)
+    area = np.asarray(step_area, np.float64)
+    nan = np.isnan(area)
+    order = np.lexsort((step_ids, -np.where(nan, 0.0, area), ~nan, step_parent))
+    return _group_heads(order, step_parent[order], parents)
+
+
+def _first_step(step_ids, step_parent, parents):
+    """For every id in `parents`: the position of its step with the smallest step id (dataset.py:1334-1339)."""
+    step_ids, step_parent = np.asarray(step_ids), np.asarray(step_parent)
+    order = np.lexsort((step_ids, step_parent))
+    return _group_heads(order, step_parent[order], parents)
+
+
+def _props_inputs(dataset):
+    """the operands of calculate_label_properties, checked before anything touches the device"""
+    def need(container, name):
+        if name not in container:
+            raise KeyError(name)
+        return container[name]
+
+    area = np.asarray(need(dataset, "area"))
+    lat, lon = np.asarray(need(dataset, "lat")), np.asarray(need(dataset, "lon"))
+    x, y, t = (np.asarray(need(dataset.coords, c)) for c in ("x", "y", "t"))
+    for kind, dim in _KINDS:
+        need(dataset, kind + "_label")
+        need(dataset, kind + "_step_label")
+        need(dataset.coords, dim)
+        need(dataset.coords, kind + "_step")
+    need(dataset, "core_step_core_index")
+    if lat.ndim == 1 and lon.ndim == 1:
+        lon, lat = np.meshgrid(lon, lat)                          # dataset.py:1256-1259
+    elif not (lat.ndim == 2 and lon.ndim == 2):
+        raise ValueError(f"lat and lon must both be 2-D or both 1-D (got {lat.ndim}-D and {lon.ndim}-D)")
+    shape = (y.size, x.size)
+    for name, a in (("area", area), ("lat", lat), ("lon", lon)):
+        if a.shape != shape:
+            raise ValueError(f"{name} has shape {a.shape}, expected (y, x) = {shape}")
+    t = t.astype("datetime64[ns]")
+    if np.any(np.isnat(t)):
+        raise ValueError("calculate_label_properties: the t coordinate holds NaT")
+    return area, lat, lon, x, y, t
+
+
+def calculate_label_properties(dataset):
+    """Pixel counts, areas, start / end times, lifetimes and area-weighted locations of the cores, anvils and their steps
+    (reference: dataset.py:705-1595; the variables it has commented out stay out).  Names, dimensions and dtypes are the
+    reference's.  Each of the six label volumes is read ONCE by tf_label_props, with `area`, `lat`, `lon` as (y, x) planes
+    and `x`, `y`, `t` as vectors -- the reference's np.repeat stacks are never built; the per-core choices among the steps
+    (`core_max_area*`, `core_start_*`) are small host reductions over the step arrays.  Counts and times are exact; areas
+    and locations are double sums (the reference sums in the operands' own precision) cast to float32.
+    `t` need not be sorted.  A coordinate id that does not occur in its volume gets count 0, area NaN, times NaT and
+    location NaN; a region whose areas sum to exactly 0 raises ZeroDivisionError as np.average does."""
+    area, lat, lon, x, y, t = _props_inputs(dataset)
+    t_sorted, t_rank = np.unique(t, return_inverse=True)
+    nat = np.datetime64("NaT", "ns")
+    tt = _lib.torch()
+    # the operands go to the device once, not once per volume
+    area, lat, lon, x, y = (_lib.to_dev(np.ascontiguousarray(a, np.float64), tt.float64, share=True) for a in (area, lat, lon, x, y))
+    t_rank = _lib.to_dev(np.ascontiguousarray(t_rank.reshape(-1), np.int32), tt.int32)
+
+    def props(volume, ids, locations):
+        ids = np.asarray(ids)
+        n = int(ids.max()) if ids.size else 0
+        loc = dict(x=x, y=y, lat=lat, lon=lon) if locations else {}
+        return _label.label_props(dataset[volume], n, area=area, t_rank=t_rank, **loc)[ids]
+
+    def times(rec, which):
+        present = rec["count"] > 0
+        out = np.full(rec.size, nat)
+        out[present] = t_sorted[rec[which][present]]
+        return out
+
+    def areas(rec):
+        return np.where(rec["count"] > 0, rec["area_nansum"], np.nan).astype(np.float32)
+
+    def location(rec, key):
+        present = rec["count"] > 0
+        if np.any(present & (rec["w"] == 0)):
+            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+        out = np.full(rec.size, np.nan)
+        out[present] = rec[key][present] / rec["w"][present]
+        return out.astype(np.float32)
+
+    step, parent = {}, {}
+    for kind, dim in _KINDS:
+        parent[kind] = props(kind + "_label", dataset.coords[dim], False)
+        step[kind] = props(kind + "_step_label", dataset.coords[kind + "_step"], True)
+
+    def add_steps(kind, what):
+        rec, d = step[kind], (kind + "_step",)
+        if what == "area":
+            dataset.add(kind + "_step_pixel_count", rec["count"], d, np.int32)
+            dataset.add(kind + "_step_area", areas(rec), d, np.float32)
+        elif what == "t":
+            dataset.add(kind + "_step_t", times(rec, "tmin"), d, "datetime64[ns]")
+        else:
+            for c in ("x", "y", "lat", "lon"):
+                dataset.add(f"{kind}_step_{c}", location(rec, "w" + c), d, np.float32)
+
+    def add_times(kind, dim):
+        rec = parent[kind]
+        start, end = times(rec, "tmin"), times(rec, "tmax")
+        dataset.add(kind + "_start_t", start, (dim,), "datetime64[ns]")
+        dataset.add(kind + "_end_t", end, (dim,), "datetime64[ns]")
+        dataset.add(kind + "_lifetime", end - start, (dim,), "timedelta64[ns]")
+
+    # the reference's order of creation: core, thick anvil, thin anvil (areas, then times), then the locations
+    core = np.asarray(dataset.coords["core"])
+    dataset.add("core_pixel_count", parent["core"]["count"], ("core",), np.int32)
+    dataset.add("core_total_area", areas(parent["core"]), ("core",), np.float32)
+    add_steps("core", "area")
+    widest = _first_max_step(dataset.coords["core_step"], _host(dataset["core_step_core_index"]), dataset["core_step_area"], core)
+    dataset.add("core_max_area", dataset["core_step_area"][widest], ("core",), np.float32)
+    add_times("core", "core")
+    add_steps("core", "t")
+    dataset.add("core_max_area_t", dataset["core_step_t"][widest], ("core",), "datetime64[ns]")
+    for kind in ("thick_anvil", "thin_anvil"):
+        if kind == "thick_anvil":
+            dataset.add("thick_anvil_total_area", areas(parent[kind]), ("anvil",), np.float32)
+        add_steps(kind, "area")
+        add_times(kind, "anvil")
+        add_steps(kind, "t")
+    add_steps("core", "loc")
+    first = _first_step(dataset.coords["core_step"], _host(dataset["core_step_core_index"]), core)
+    for c in ("x", "y", "lat", "lon"):
+        dataset.add(f"core_start_{c}", dataset[f"core_step_{c}"][first], ("core",), np.float32)
+    add_steps("thick_anvil", "loc")
+    add_steps("thin_anvil", "loc")
+
+
 __all__ = ("LabelDataset", "add_step_labels", "add_label_coords", "find_max_overlap", "link_cores_and_anvils",
-           "link_step_labels", "find_edge_labels", "flag_edge_labels", "flag_nan_adjacent_labels")
+           "link_step_labels", "find_edge_labels", "flag_edge_labels", "flag_nan_adjacent_labels",
+           "calculate_label_properties")

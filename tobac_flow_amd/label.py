@@ -227,5 +227,82 @@ def slice_labels_dev(labels):
     return out, int(n_ids.value)
 
 
+_PROPS_RECORD = np.dtype([("count", np.int64), ("area_nansum", np.float64), ("w", np.float64), ("wx", np.float64),
+                          ("wy", np.float64), ("wlat", np.float64), ("wlon", np.float64), ("tmin", np.int32), ("tmax", np.int32)])
+
+
+def label_props(labels, n_labels, area=None, x=None, y=None, lat=None, lon=None, t_rank=None):
+    """tf_label_props on an int32 (T, H, W) label volume (numpy or device tensor): a host record array of n_labels + 1
+    entries with the fields count, area_nansum, w, wx, wy, wlat, wlon, tmin, tmax (entry 0, the background, stays empty).
+    area, lat, lon: (H, W); x: (W,); y: (H,); t_rank: (T,) ints >= 0 -- host arrays or device tensors, passed as they are;
+    None switches the sums that need it off."""
+    t = _lib.torch()
+    lab = _lib.to_dev(labels, t.int32, share=True).contiguous()
+    if lab.dim() != 3:
+        raise ValueError("label_props: labels must be a (t, y, x) volume")
+    T, H, W = (int(n) for n in lab.shape)
+    n_labels = int(n_labels)
+    if lab.numel() == 0 or n_labels < 0:
+        raise ValueError("label_props: empty volume or negative n_labels")
+    keep = []                                                     # the operands stay alive until the result is on the host
+
+    def operand(a, shape, dtype, name):
+        if a is None:
+            return ctypes.c_void_p(0)
+        if not _lib.is_tensor(a):
+            a = np.ascontiguousarray(a, dtype)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"label_props: {name} has shape {tuple(a.shape)}, expected {shape}")
+        keep.append(_lib.to_dev(a, getattr(t, np.dtype(dtype).name), share=True))
+        return _lib.ptr(keep[-1])
+
+    args = [operand(area, (H, W), np.float64, "area"), operand(x, (W,), np.float64, "x"), operand(y, (H,), np.float64, "y"),
+            operand(lat, (H, W), np.float64, "lat"), operand(lon, (H, W), np.float64, "lon"),
+            operand(t_rank, (T,), np.int32, "t_rank")]
+    acc = _lib.empty((n_labels + 1, 8), t.float64)
+    _lib.check(_lib.lib().tf_label_props(_lib.ptr(lab), T, H, W, n_labels, *args, _lib.ptr(acc), _lib.stream_ptr()),
+               "tf_label_props")
+    return acc.cpu().numpy().view(_PROPS_RECORD).reshape(n_labels + 1)
+
+
+def unique_along_t(volume):
+    """Per pixel of an int32 (T, H, W) volume the number of distinct non-zero values along t and the number of non-zero
+    ones (tf_unique_along_t): host int32 (H, W) arrays, and the pixels per workgroup of the LDS form that ran (0: the
+    per-pixel sets lived in HBM scratch, T > 640)."""
+    t = _lib.torch()
+    L = _lib.lib()
+    vol = _lib.to_dev(volume, t.int32, share=True).contiguous()
+    T, H, W = (int(n) for n in vol.shape)
+    if vol.numel() == 0:
+        raise ValueError("unique_along_t: empty volume")
+    uniq, nz = _lib.empty((H, W), t.int32), _lib.empty((H, W), t.int32)
+    need = L.tf_unique_along_t_workspace_bytes(T, H, W)
+    ws = _lib.workspace(need, "unique_along_t") if need else None
+    lanes = ctypes.c_int(-1)
+    _lib.check(L.tf_unique_along_t(_lib.ptr(vol), T, H, W, _lib.ptr(uniq), _lib.ptr(nz), ctypes.byref(lanes),
+                                   _lib.ptr(ws) if ws is not None else ctypes.c_void_p(0), ws.numel() if ws is not None else 0,
+                                   _lib.stream_ptr()), "tf_unique_along_t")
+    return uniq.cpu().numpy(), nz.cpu().numpy(), int(lanes.value)
+
+
+def unique_per_frame(volume, n_labels=None):
+    """Per frame of an int32 (T, ...) volume the number of distinct ids in [1, n_labels] (default: the largest value) and
+    the number of non-zero voxels (tf_unique_per_frame): host arrays int32 (T,) and int64 (T,)."""
+    t = _lib.torch()
+    L = _lib.lib()
+    vol = _lib.to_dev(volume, t.int32, share=True).contiguous()
+    T = int(vol.shape[0])
+    if vol.numel() == 0:
+        raise ValueError("unique_per_frame: empty volume")
+    if n_labels is None:
+        n_labels = max(int(vol.max()), 0)
+    uniq, nz = _lib.empty((T,), t.int32), _lib.empty((T,), t.int64)
+    ws = _lib.workspace(L.tf_unique_per_frame_workspace_bytes(int(n_labels)), "unique_per_frame")
+    _lib.check(L.tf_unique_per_frame(_lib.ptr(vol), T, vol.numel() // T, int(n_labels), _lib.ptr(uniq), _lib.ptr(nz),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "tf_unique_per_frame")
+    return uniq.cpu().numpy(), nz.cpu().numpy()
+
+
 __all__ = ("flow_label", "find_neighbour_labels", "flow_link_overlap", "flow_label_dev", "link_overlap_dev",
-           "pair_counts", "label_sizes", "slice_labels_dev", "make_step_labels_dev")
+           "pair_counts", "label_sizes", "slice_labels_dev", "make_step_labels_dev", "label_props", "unique_along_t",
+           "unique_per_frame")
