@@ -630,6 +630,40 @@ int tf_unique_along_t(const int32_t *vol, int64_t T, int64_t H, int64_t W, int32
 size_t tf_unique_per_frame_workspace_bytes(int64_t n_labels);
 int tf_unique_per_frame(const int32_t *vol, int64_t T, int64_t hw, int64_t n_labels, int32_t *unique, int64_t *nonzero,
                         void *ws, size_t ws_bytes, void *stream);
+/* tf_label_wstats: tobac_flow/utils/stats_utils.py:33-154 (`weighted_average_and_std`, `weighted_stats`,
+ *   `weighted_average_uncertainty`, `weighted_uncertainties`, `weighted_stats_and_uncertainties`) applied to every label by
+ *   tobac_flow/utils/label_utils.py:58-140 (`apply_func_to_labels`), as tobac_flow/postprocess.py:102-242
+ *   (`weighted_label_stats`, `add_weighted_stats_to_dataset`) calls them.  labels: int32 (T, hw); field, errors (or NULL)
+ *   and weights: all float32 (dtype TF_F32) or all float64 (TF_F64), nothing is cast down; weights are (T, hw), or with
+ *   weights_plane != 0 ONE (hw,) plane shared by every frame (the scripts' np.repeat(area[None], T, 0), never
+ *   materialised).  Per label id 1 .. n_labels, over F = its voxels with a finite field value,
+ *   out[(id - 1) * 10 + k] as doubles on the device:
+ *     k = 0  n = |F|                         k = 1  sum of w over F (NaN if one of them is NaN)
+ *     k = 2  mean = sum w x / sum w          k = 3  std = sqrt(sum w (x - mean)^2 / sum w / c), c = 1 - sum w^2 / (sum w)^2,
+ *                                                   NaN where c < 0 or 0 / 0 (one weighted voxel), inf where a / 0
+ *     k = 4  min of x over F                 k = 5  max of x over F   (weight-0 voxels included)
+ *     k = 6  sqrt(sum w^2 e^2) / sum w       k = 7  sqrt((std / sqrt(n))^2 + [6]^2)
+ *     k = 8  e at the voxel of the minimum   k = 9  e at the voxel of the maximum
+ *   k = 2 .. 9 are NaN unless n > 0 and sum w > 0; k = 6 .. 9 are NaN when errors == NULL.  Where the extreme occurs more
+ *   than once the voxel with the smallest raveled index is taken (the reference's unstable argsort leaves it undefined);
+ *   -0.0 and +0.0 compare equal.  Two reads of labels, field and weights (the errors once, only under labelled voxels) and
+ *   a finish per label; sums are double atomics, one set per run of equal labels a lane meets, so their last bits depend
+ *   on arrival order (N terms of one sign: N * 2^-53 relative); n, min, max and the two selected errors are exact.  Ids
+ *   outside [1, n_labels] are background.  64-bit indexing throughout.  The workspace holds 128 B per label. */
+size_t tf_label_wstats_workspace_bytes(int64_t n_labels);
+int tf_label_wstats(const int32_t *labels, const void *field, const void *errors, const void *weights, int dtype,
+                    int64_t T, int64_t hw, int weights_plane, int64_t n_labels, double *out, void *ws, size_t ws_bytes,
+                    void *stream);
+/* tf_label_proportions: tobac_flow/utils/stats_utils.py:157-168 (`get_weighted_proportions`) per label
+ *   (tobac_flow/postprocess.py:245-310).  labels, flags: int32 (T, hw); weights: float32, volume or plane as above;
+ *   flag_values_host: n_flags <= 64 DISTINCT int32 values in host memory.  out[(id - 1) * n_flags + k] = (sum of the
+ *   label's non-NaN weights where flag == value k) / (sum of all its non-NaN weights), NaN for every k unless that total
+ *   is > 0; a flag that is not listed counts towards the total only.  One read of the volume and a finish; one or two
+ *   double atomics per run of equal (label, flag) pairs.  The workspace holds 1 + n_flags doubles per label. */
+size_t tf_label_proportions_workspace_bytes(int64_t n_labels, int n_flags);
+int tf_label_proportions(const int32_t *labels, const int32_t *flags, const float *weights, int64_t T, int64_t hw,
+                         int weights_plane, int64_t n_labels, const int32_t *flag_values_host, int n_flags, double *out,
+                         void *ws, size_t ws_bytes, void *stream);
 size_t tf_slice_labels_workspace_bytes(int64_t T, int64_t id_capacity);
 int tf_slice_labels(const int32_t *labels, int64_t T, int64_t hw, int32_t *out, int64_t *n_step_labels_host,
                     void *ws, size_t ws_bytes, void *stream);

@@ -128,6 +128,10 @@ _PROTOS = {
     "tf_unique_along_t": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _c.c_size_t, _P]),
     "tf_unique_per_frame_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
     "tf_unique_per_frame": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_label_wstats_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
+    "tf_label_wstats": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _P, _c.c_size_t, _P]),
+    "tf_label_proportions_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int]),
+    "tf_label_proportions": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
     "tf_slice_labels": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_pair_counts": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_sizes": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P]),

@@ -10,7 +10,9 @@ from tobac_flow_amd.utils.label_utils import (apply_func_to_labels, find_overlap
                                               relabel_objects, remap_labels, slice_labels)
 from tobac_flow_amd.utils.normalisation_utils import (inverse_log_norm, linear_norm, linearise_field, local_linear_norm,
                                                       log_norm, select_normalisation_method, to_8bit, uniform_norm, z_norm)
-from tobac_flow_amd.utils.stats_utils import mse, n_unique_along_axis
+from tobac_flow_amd.utils.stats_utils import (get_weighted_proportions, mse, n_unique_along_axis, weighted_average_and_std,
+                                              weighted_average_uncertainty, weighted_stats,
+                                              weighted_stats_and_uncertainties, weighted_uncertainties)
 
 __all__ = (
     "get_datetime_from_coord", "get_time_diff_from_coord", "time_diff",
@@ -19,5 +21,6 @@ __all__ = (
     "labeled_comprehension", "make_step_labels", "relabel_objects", "remap_labels", "slice_labels",
     "inverse_log_norm", "linear_norm", "linearise_field", "local_linear_norm", "log_norm",
     "select_normalisation_method", "to_8bit", "uniform_norm", "z_norm",
-    "mse", "n_unique_along_axis",
+    "mse", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
+    "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions",
 )

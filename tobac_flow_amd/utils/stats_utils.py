@@ -1,4 +1,8 @@
-"""The statistics helpers the drop-in scripts reach (reference: utils/stats_utils.py:23-30 and :366-367)."""
+"""The statistics helpers the drop-in scripts reach (reference: utils/stats_utils.py:23-30, :33-168 and :366-367).
+
+The weighted_* functions and get_weighted_proportions are the per-region host forms: one region's values in, scalars
+out.  tobac_flow_amd.postprocess evaluates them for all labels at once on the GPU (tf_label_wstats,
+tf_label_proportions) and falls back to these for inputs the kernels do not take."""
 import numpy as np
 
 
@@ -67,4 +71,79 @@ def n_unique_along_axis(a, axis: int = 0):
     return uniq.reshape(out_shape)
 
 
-__all__ = ("mse", "n_unique_along_axis")
+def _finite_part(data, *others, ignore_nan=True):
+    """the arrays restricted to where `data` is finite (np.isfinite: NaN and both infinities go)"""
+    arrays = [np.asarray(a) for a in (data,) + others]
+    if not ignore_nan:
+        return arrays
+    keep = np.isfinite(arrays[0])
+    return [a[keep] for a in arrays]
+
+
+def weighted_average_and_std(data, weights, unbiased: bool = True):
+    """mean = sum w x / sum w and the standard deviation about it, sqrt(sum w (x - mean)^2 / sum w / c) with Bessel's
+    correction for reliability weights c = 1 - sum w^2 / (sum w)^2; NaN where c < 0 (reference: stats_utils.py:33-50,
+    whose `unbiased=False` leaves std unset; here it gives the uncorrected value)."""
+    data, weights = np.asarray(data), np.asarray(weights)
+    total = np.sum(weights)
+    mean = np.sum(weights * data) / total
+    var = np.sum(weights * (data - mean) ** 2) / total
+    if not unbiased:
+        return mean, np.sqrt(var)
+    c = 1 - np.sum(weights ** 2) / total ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        std = np.sqrt(var / c) if c >= 0 else np.nan
+    return mean, std
+
+
+def weighted_stats(data, weights, ignore_nan: bool = True, default=np.nan):
+    """(mean, std, min, max) of one region over its finite values; `default` four times unless there is a finite value
+    and their weights sum to > 0 (a NaN weight makes the sum NaN).  min and max include weight-0 values (reference:
+    stats_utils.py:53-73)."""
+    data, weights = _finite_part(data, weights, ignore_nan=ignore_nan)
+    if data.size == 0 or not np.sum(weights) > 0:
+        return default, default, default, default
+    mean, std = weighted_average_and_std(data, weights)
+    return mean, std, np.min(data), np.max(data)
+
+
+def weighted_average_uncertainty(errors, weights):
+    """propagated uncertainty of a weighted mean, sqrt(sum w^2 e^2) / sum w (reference: stats_utils.py:76-86)"""
+    errors, weights = np.asarray(errors), np.asarray(weights)
+    if errors.size == 0 or not np.sum(weights) > 0:
+        return np.nan
+    return np.sqrt(np.sum(weights ** 2 * errors ** 2)) / np.sum(weights)
+
+
+def weighted_uncertainties(data, errors, weights, std, ignore_nan: bool = True):
+    """(uncertainty of the mean, sqrt((std / sqrt(n))^2 + uncertainty^2), error at the minimum, error at the maximum) of
+    one region; the first occurrence of an extreme is taken (reference: stats_utils.py:89-117)."""
+    data, errors, weights = _finite_part(data, errors, weights, ignore_nan=ignore_nan)
+    if data.size == 0 or not np.sum(weights) > 0:
+        return np.nan, np.nan, np.nan, np.nan
+    uncertainty = weighted_average_uncertainty(errors, weights)
+    combined = np.sqrt((std / np.sqrt(data.size)) ** 2 + uncertainty ** 2)
+    return uncertainty, combined, errors[np.argmin(data)], errors[np.argmax(data)]
+
+
+def weighted_stats_and_uncertainties(data, errors, weights, ignore_nan: bool = True):
+    """weighted_stats followed by weighted_uncertainties: eight values (reference: stats_utils.py:120-154)"""
+    stats = weighted_stats(data, weights, ignore_nan=ignore_nan)
+    return stats + weighted_uncertainties(data, errors, weights, stats[1], ignore_nan=ignore_nan)
+
+
+def get_weighted_proportions(data, weights, flag_values):
+    """per flag value, the share of the region's (non-NaN) weight that lies on it; NaN throughout unless the weights sum
+    to > 0.  A flag that is not listed counts towards the total only (reference: stats_utils.py:157-168)."""
+    data, weights = np.asarray(data).ravel(), np.asarray(weights, float).ravel()
+    flag_values = np.asarray(list(flag_values))
+    total = np.nansum(weights)
+    if not total > 0:
+        return np.full(flag_values.size, np.nan)
+    counted = np.where(np.isnan(weights), 0.0, weights)
+    with np.errstate(invalid="ignore"):
+        return np.array([np.nansum(np.where(data == f, counted, 0.0)) for f in flag_values]) / total
+
+
+__all__ = ("mse", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
+           "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions")
