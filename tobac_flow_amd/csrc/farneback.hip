@@ -1838,7 +1838,10 @@ static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_
             // The chain in two parts one row group apart (HP form; same flows) is the faster form alone on the GPU (level-0
             // launch of 21 pairs: 18.0 against 19.7 ms), but its 39 KB of LDS per workgroup fill the CU (4 x 39 = 156 of
             // 160 KB): in the pipelined benchmark the floods of the finished windows run beside the flow in what the one-lane
-            // form leaves free (4 x 27 KB), and with the two-part form they displace iteration workgroups instead -- the kernel
+            // form leaves free -- LDS: 160 KB - 4 x 27 KB; registers: 512 - 2 x 224 = 64 per lane and SIMD, which the
+            // connectivity-1 sweep kernels are built to fit (watershed.hip, tests/test_kernel_resources_cpu.py); a kernel that
+            // needs more than 64 cannot start on a SIMD before an iteration workgroup has left its CU -- and with the
+            // two-part form they displace iteration workgroups instead -- the kernel
             // then reads 1 985 against 1 860 ms per config-F step, the step is the same (4.75 s either way, back to back on one
             // box).  So it is chosen PER CALL (tf_farneback_params.chain_form): the host layer asks for the two-part form when
             // nothing is going to run beside this call's flow; a process-wide switch, as in round 4, let one thread's plain

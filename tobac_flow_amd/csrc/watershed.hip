@@ -13,7 +13,7 @@
 // lexicographically smallest chain.  Every component of the chain is the fixpoint of a MONOTONE
 // min-relaxation over the directed neighbour graph (flow-displaced in t), so it is computed with
 // chaotic 64-bit atomicMin sweeps, one phase per chain level:
-//   phase A   K2 and M1(n) = min K2 over in-neighbours
+//   phase A   K2; then, in one pass over the final keys, M1(n) = min K2 over in-neighbours
 //   phase k   C_k(n) = k-th chain element (k = 1 .. depth-1), candidates must match levels < k
 //   phase R   root marker index among fully matching candidates; label(n) = markers[R(n)]
 // Ties between equal-valued MARKERS (age 0 in the reference, heap-internal order there) are
@@ -45,8 +45,8 @@ typedef unsigned long long u64;
 #define WS_MAX_NBR 26
 #define WS_MAX_DEPTH TF_WS_MAX_DEPTH
 #define WS_BATCH 32
-#define WS_K2(c, i) ((c).KM[2 * (int64_t)(i)])
-#define WS_M1(c, i) ((c).KM[2 * (int64_t)(i) + 1])
+#define WS_K2(c, i) ((c).K2[(int64_t)(i)])
+#define WS_M1(c, i) ((c).M1[(int64_t)(i)])
 
 struct WsGeom {
     int64_t T; int H, W; int64_t plane;
@@ -77,7 +77,7 @@ static int64_t ws_virtual_voxels(int64_t T, int64_t H, int64_t W) {
 struct WsC {               // compact arrays
     int64_t R; int n_nbr;
     const u64 *pix; const unsigned *val; const int *nbr;
-    u64 *KM;               // K2 and M1 of a pixel side by side ({K2, M1}[R], 16-byte aligned): phase A reads both with one load
+    u64 *K2, *M1;          // two arrays: the phase A sweeps read and lower K2 only, M1 is scattered once from the final K2 (k_ws_sweep_m1)
     u64 *C[WS_MAX_DEPTH], *Rt;
     int *Llo, *Lhi;        // smallest / largest label among the roots of all fully matching candidates (root phase)
     const u64 *emask;      // per pixel p, bit i: out-edge i is a CANDIDATE edge (K2[p] == M1[nbr i]); bit 32 + i: nbr i is an entry
@@ -312,7 +312,7 @@ template <int NN>
 __global__ void __launch_bounds__(256)
 k_ws_compact(const float *__restrict__ field, const float *__restrict__ fwd, const float *__restrict__ bwd,
              const int *__restrict__ cid, WsGeom g, u64 *__restrict__ pix, unsigned *__restrict__ val,
-             int *__restrict__ nbr, u64 *__restrict__ KM, int *__restrict__ nan_flag)
+             int *__restrict__ nbr, u64 *__restrict__ K2, u64 *__restrict__ M1, int *__restrict__ nan_flag)
 {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     const int64_t t = blockIdx.z;
@@ -347,7 +347,8 @@ k_ws_compact(const float *__restrict__ field, const float *__restrict__ fwd, con
             nbr[id * g.n_nbr + i] = cn;
         }
     }
-    *(ulonglong2 *)&KM[2 * id] = make_ulonglong2(marker ? ((u64)v << 32) : WS_INF, WS_INF);
+    K2[id] = marker ? ((u64)v << 32) : WS_INF;
+    M1[id] = WS_INF;
 }
 
 // ---- the reference's own raveled form (tf_watershed_raveled) -------------------------------------------------------
@@ -403,7 +404,7 @@ k_wsr_relevant(const uint8_t *__restrict__ cls, WsRavel g, uint8_t *__restrict__
 
 __global__ void __launch_bounds__(256)
 k_wsr_compact(const float *__restrict__ image, const int *__restrict__ cid, WsRavel g, u64 *__restrict__ pix,
-              unsigned *__restrict__ val, int *__restrict__ nbr, u64 *__restrict__ KM, int *__restrict__ nan_flag)
+              unsigned *__restrict__ val, int *__restrict__ nbr, u64 *__restrict__ K2, u64 *__restrict__ M1, int *__restrict__ nan_flag)
 {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= g.n) return;
@@ -423,7 +424,8 @@ k_wsr_compact(const float *__restrict__ image, const int *__restrict__ cid, WsRa
         if (n >= 0) { cn = cid[n]; if (cn < 0) cn = -1; }
         nbr[id * g.n_nbr + i] = cn;
     }
-    *(ulonglong2 *)&KM[2 * id] = make_ulonglong2(marker ? ((u64)v << 32) : WS_INF, WS_INF);
+    K2[id] = marker ? ((u64)v << 32) : WS_INF;
+    M1[id] = WS_INF;
 }
 
 // in place: output[i] = label of its root seed for every flooded pixel (seeds and everything else untouched)
@@ -480,9 +482,12 @@ k_ws_init_labelset(const u64 *__restrict__ pix, const int32_t *__restrict__ mark
 // per processed pixel (K2 and M1 minima), and runs at the chip's rate for scattered atomics (~2 x 10^10 / s,
 // MI355X_MICROARCH.md "Global float atomics": 64 lanes in 64 rows).  Fewer launches is what is kept.  Chaotic relaxation
 // of a monotone system reaches the same fixpoint in any order.
+// WS_LDS_CAP entries per staging buffer.  2048 (16 KB per workgroup): three sweep workgroups fit on a CU beside four
+// workgroups of the one-lane iteration kernel, one with 4096; config F, the two in turn: 3 952 against 3 994 ms per step
+// (profiles/sweeps_in_64.txt).  What does not fit a buffer goes straight to the global queue (ws_stage).
 #define WS_LOCAL_ROUNDS 4
 #ifndef WS_LDS_CAP
-#define WS_LDS_CAP 4096
+#define WS_LDS_CAP 2048
 #endif
 struct WsStage { int cnt[2]; int base; int buf[2][WS_LDS_CAP]; };
 
@@ -544,14 +549,23 @@ __device__ __forceinline__ void ws_sweep(int64_t R, const int *__restrict__ qin,
     }
 }
 
-// ---- phase A: K2 and M1 ------------------------------------------------------------------------
-// Memory-level parallelism.  Walking the out-edges of a queue entry one at a time (neighbour id -> its value and keys
-// -> atomics) is about twenty DEPENDENT round trips per entry, and a large sweep then runs at the latency of that chain
+// ---- phase A: K2; then M1 in one pass -------------------------------------------------------------
+// Memory-level parallelism.  Walking the out-edges of a queue entry one at a time (neighbour id -> its value and key
+// -> atomic) is about twenty DEPENDENT round trips per entry, and a large sweep then runs at the latency of that chain
 // (0.45 ns per entry = a few hundred GB/s).  The edges of one pixel are independent, so they are handled WS_NB at a
 // time in three waves of independent accesses: all neighbour ids (issued together with the load of the pixel's own key),
 // then all neighbour values / keys, then all atomics.  The plain reads are only pre-filters (keys only decrease, a
 // stale value is larger); the decisions are made on the values the atomics return.
+// REGISTERS.  The connectivity-1 sweeps are meant to run in the 64 registers per lane that two resident k_fb_iter waves
+// leave free on a SIMD ("What runs beside the iteration kernel"): neighbour values stay 32-bit, the
+// candidate key is recomputed from (value, own key) when the atomic has returned instead of being held across it, and M1
+// is not touched here at all (k_ws_sweep_m1 below).
 #define WS_NB 8
+
+// the key p offers its out-neighbour of value vn: a higher level starts generation 1, the same level the next generation
+__device__ __forceinline__ u64 ws_cand_a(unsigned vn, unsigned lp, u64 kp) {
+    return vn > lp ? (((u64)vn << 32) | 1ull) : (vn == lp ? kp + 1ull : kp);
+}
 
 // one queue entry of phase A: pop p, relax its out-edges WS_NB at a time, stage the pixels whose key it lowered
 // NN = 6: the six face neighbours as a compile-time count -- one trip of SIX slots instead of eight with two dead ones (a
@@ -569,39 +583,73 @@ __device__ __forceinline__ void ws_entry_a(const WsC &c, WsStage &st, int w, boo
 #pragma unroll
         for (int j = 0; j < NB; j++) n[j] = (act && s0 + j < n_nbr) ? np[s0 + j] : -1;
         if (s0 == 0 && act) kp = ws_load(&WS_K2(c, p));            // (the id loads above are already in flight)
-        const u64 lp = kp >> 32;
-        u64 vn[NB], m1[NB], k2[NB];
+        const unsigned lp = (unsigned)(kp >> 32);
+        unsigned vn[NB];
+        u64 k2[NB];                                                    // the neighbour's key, then the atomic's return
 #pragma unroll
         for (int j = 0; j < NB; j++) {
             const int q = n[j] >= 0 ? n[j] : 0;
             vn[j] = c.val[q];
-            const ulonglong2 km = *(const ulonglong2 *)&WS_K2(c, q);
-            k2[j] = km.x; m1[j] = km.y;
+            k2[j] = WS_K2(c, q);
         }
-        u64 cand[NB], old[NB];
 #pragma unroll
         for (int j = 0; j < NB; j++) {
-            cand[j] = vn[j] > lp ? ((vn[j] << 32) | 1ull) : (vn[j] == lp ? kp + 1ull : kp);
-            old[j] = 0ull;                                             // "no improvement"
-            if (n[j] >= 0) {
-                // keys only decrease, so a (possibly stale, i.e. larger) plain read is a safe pre-filter
-                if (kp < m1[j]) atomicMin(&WS_M1(c, n[j]), kp);
-                if (cand[j] < k2[j]) old[j] = atomicMin(&WS_K2(c, n[j]), cand[j]);
-            }
+            // keys only decrease, so a (possibly stale, i.e. larger) plain read is a safe pre-filter
+            const u64 cand = ws_cand_a(vn[j], lp, kp);
+            const bool go = n[j] >= 0 && cand < k2[j];
+            k2[j] = 0ull;                                              // "no improvement"
+            if (go) k2[j] = atomicMin(&WS_K2(c, n[j]), cand);
         }
 #pragma unroll
         for (int j = 0; j < NB; j++)                               // raw returns: consumed only after all are issued
-            ws_stage(st, w, n[j] >= 0 && cand[j] < old[j], n[j], qout, cnt_out, qcap);
+            ws_stage(st, w, n[j] >= 0 && ws_cand_a(vn[j], lp, kp) < k2[j], n[j], qout, cnt_out, qcap);
     }
 }
 
-template <int NN>
+// any neighbour count (eight slots per trip; not part of the 64-register budget)
 __global__ void __launch_bounds__(256)
 k_ws_sweep_a(WsC c, const int *__restrict__ qin, const int *__restrict__ cnt_in, int *__restrict__ qout,
              int *__restrict__ cnt_out, int qcap)
 {
     ws_sweep(c.R, qin, cnt_in, qout, cnt_out, qcap,
-             [&](WsStage &st, int w, bool act, int p) { ws_entry_a<NN>(c, st, w, act, p, qout, cnt_out, qcap); });
+             [&](WsStage &st, int w, bool act, int p) { ws_entry_a<0>(c, st, w, act, p, qout, cnt_out, qcap); });
+}
+// connectivity 1: 64 registers, declared (see k_ws_sweep_chain6 below)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(64)))
+k_ws_sweep_a6(WsC c, const int *__restrict__ qin, const int *__restrict__ cnt_in, int *__restrict__ qout,
+              int *__restrict__ cnt_out, int qcap)
+{
+    ws_sweep(c.R, qin, cnt_in, qout, cnt_out, qcap,
+             [&](WsStage &st, int w, bool act, int p) { ws_entry_a<6>(c, st, w, act, p, qout, cnt_out, qcap); });
+}
+
+// M1(n) = min of the FINAL K2 over the reached in-neighbours of n.  The sweeps used to offer p's current key to the M1 of
+// all its out-neighbours at every visit of p (one more 64-bit atomic per edge and visit, and M1 read beside K2); only the
+// last visit of p matters -- every reached p is visited after its last lowering -- so one scatter pass over the final keys
+// gives the same minima: plain-read pre-filter, one non-returning atomic per edge that still lowers.  A pixel phase A never
+// reached offers nothing; a pixel with no reached in-neighbour keeps M1 = infinity.
+template <int NN>
+__global__ void __launch_bounds__(256)
+k_ws_sweep_m1(WsC c)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= c.R) return;
+    const u64 kp = WS_K2(c, p);
+    if (kp == WS_INF) return;
+    constexpr int NB = NN ? NN : WS_NB;
+    const int n_nbr = NN ? NN : c.n_nbr;
+    const int *np = c.nbr + p * n_nbr;
+    for (int s0 = 0; s0 < n_nbr; s0 += NB) {
+        int n[NB];
+        u64 m1[NB];
+#pragma unroll
+        for (int j = 0; j < NB; j++) n[j] = s0 + j < n_nbr ? np[s0 + j] : -1;
+#pragma unroll
+        for (int j = 0; j < NB; j++) m1[j] = WS_M1(c, n[j] >= 0 ? n[j] : 0);
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+            if (n[j] >= 0 && kp < m1[j]) atomicMin(&WS_M1(c, n[j]), kp);
+    }
 }
 
 // After phase A the keys K2 and M1 are final, and with them which edges p -> n are candidate edges (K2[p] == M1[n]: p is
@@ -625,8 +673,7 @@ k_ws_edge_masks(WsC c, u64 *__restrict__ emask)
 #pragma unroll
             for (int j = 0; j < WS_NB; j++) {
                 const int q = n[j] >= 0 ? n[j] : 0;
-                const ulonglong2 km = *(const ulonglong2 *)&WS_K2(c, q);
-                kn[j] = km.x; m1[j] = km.y; vn[j] = c.val[q];
+                kn[j] = WS_K2(c, q); m1[j] = WS_M1(c, q); vn[j] = c.val[q];
             }
 #pragma unroll
             for (int j = 0; j < WS_NB; j++)
@@ -649,77 +696,120 @@ __device__ __forceinline__ int ws_load_i(const int *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int NN>
-__device__ __forceinline__ void ws_entry_chain(const WsC &c, int k, int depth, u64 *__restrict__ dst, WsStage &st, int w,
+// K = the level k as a compile-time value (1 .. 3: the depths the library starts with), 0 = k at run time (deeper chains);
+// ROOT = this is the root phase (k == depth).  With K fixed, C_1[p] .. C_{K-1}[p] are K - 1 named registers and the match
+// loop is unrolled; a chain level carries none of the root phase's label-set state.  Nothing is held across the atomics
+// but their returns: what was offered is recomputed from (entry bit, kp, cp, own) afterwards.
+template <int NN, int K, bool ROOT>
+__device__ __forceinline__ void ws_entry_chain(const WsC &c, int k_rt, u64 *__restrict__ dst, const u64 *__restrict__ below, WsStage &st, int w,
                                                bool act0, int p,
                                                int *__restrict__ qout, int *__restrict__ cnt_out, int qcap)
 {
     constexpr int NB = NN ? NN : WS_NB;
     const int n_nbr = NN ? NN : c.n_nbr;
+    const int k = K ? K : k_rt;
     const int *np = c.nbr + (int64_t)p * n_nbr;
-    const bool root = k == depth;
     u64 kp = WS_INF, own = WS_INF, em = 0ull;
     int own_lo = 0x7fffffff, own_hi = (int)0x80000000;   // label set of p (root phase only)
-    u64 cp[WS_MAX_DEPTH];                        // C_j[p], j < k: final since their own phases, read once per entry
+    // C_j[p], j < k: final since their own phases.  K fixed: read once per entry into K - 1 named registers.  k at run
+    // time (chains deeper than the library starts with): only C_{k-1}[p] is held, the match loop reads the others again
+    // (cache hits) rather than index a register array with a run-time value
+    u64 cp[K ? K : 1];
+    u64 ek = WS_INF;                             // what an entry is offered at level k: K2[p] (k = 1) or C_{k-1}[p]
+    // what p offers n along edge slot i at level l < k, to be matched with C_l[n] ...
+    auto offer = [&](int i, int l) -> u64 {
+        const bool entry = ((em >> (32 + i)) & 1ull) != 0ull;
+        if constexpr (K != 0) return entry ? (l == 1 ? kp : cp[l - 1]) : cp[l];
+        else return entry ? (l == 1 ? kp : c.C[l - 1][p]) : c.C[l][p];
+    };
+    // ... and at level k itself, to be written (the root phase copies the root along every edge)
+    auto offer_k = [&](int i) -> u64 {
+        const bool entry = ((em >> (32 + i)) & 1ull) != 0ull;
+        return (ROOT || !entry) ? own : ek;
+    };
     for (int s0 = 0; s0 < n_nbr; s0 += NB) {
         if (s0 == 0 && act0) {
             em = c.emask[p];                     // final since phase A (0 for a pixel phase A never reached)
             kp = WS_K2(c, p);
             own = ws_load(&dst[p]);
-            if (root) { own_lo = ws_load_i(&c.Llo[p]); own_hi = ws_load_i(&c.Lhi[p]); }
-            for (int j = 1; j < k; j++) cp[j] = c.C[j][p];
+            if constexpr (ROOT) { own_lo = ws_load_i(&c.Llo[p]); own_hi = ws_load_i(&c.Lhi[p]); }
+            if constexpr (K != 0) {
+#pragma unroll
+                for (int j = 1; j < K; j++) cp[j] = c.C[j][p];
+            }
+            if constexpr (!ROOT) {
+                if constexpr (K == 1) ek = kp;
+                else if constexpr (K != 0) ek = cp[K - 1];
+                else ek = k == 1 ? kp : below[p];
+            }
         }
         // candidate edges only: one or two of the six at connectivity 1
         int n[NB];
 #pragma unroll
         for (int j = 0; j < NB; j++) n[j] = (s0 + j < n_nbr && ((em >> (s0 + j)) & 1ull)) ? np[s0 + j] : -1;
-        u64 dn[NB];
-        int lon[NB], hin[NB];
+        u64 dn[NB];                              // dst[n], then the raw return of its atomic
+        int lon[ROOT ? NB : 1], hin[ROOT ? NB : 1];   // label set of n, then the raw returns of its relaxations
 #pragma unroll
         for (int j = 0; j < NB; j++) {
-            dn[j] = WS_INF; lon[j] = 0; hin[j] = 0;
-            if (n[j] >= 0) { dn[j] = dst[n[j]]; if (root) { lon[j] = c.Llo[n[j]]; hin[j] = c.Lhi[n[j]]; } }
+            dn[j] = WS_INF;
+            if constexpr (ROOT) { lon[j] = 0; hin[j] = 0; }
+            if (n[j] >= 0) { dn[j] = dst[n[j]]; if constexpr (ROOT) { lon[j] = c.Llo[n[j]]; hin[j] = c.Lhi[n[j]]; } }
         }
-        u64 offered[NB], old[NB];
-        int olo[NB], ohi[NB];              // raw atomic returns of the label-set relaxations
 #pragma unroll
         for (int j = 0; j < NB; j++) {
-            offered[j] = WS_INF; old[j] = 0ull; olo[j] = (int)0x80000000; ohi[j] = 0x7fffffff;
+            const u64 seen = dn[j];
+            dn[j] = 0ull;                        // "no improvement"
+            int seen_lo = 0, seen_hi = 0;
+            if constexpr (ROOT) { seen_lo = lon[j]; seen_hi = hin[j]; lon[j] = (int)0x80000000; hin[j] = 0x7fffffff; }
             if (n[j] >= 0) {
-                const bool entry = ((em >> (32 + s0 + j)) & 1ull) != 0ull;
                 bool match = true;
-                for (int l = 1; l < k && match; l++) {
-                    const u64 offered_l = entry ? (l == 1 ? kp : cp[l - 1]) : cp[l];
-                    match = offered_l == c.C[l][n[j]];
+                if constexpr (K != 0) {
+#pragma unroll
+                    for (int l = 1; l < K; l++) if (match) match = offer(s0 + j, l) == c.C[l][n[j]];
+                } else {
+                    for (int l = 1; l < k && match; l++) match = offer(s0 + j, l) == c.C[l][n[j]];
                 }
                 if (match) {
-                    if (root) offered[j] = own;                                       // root: copied along every edge
-                    else offered[j] = entry ? (k == 1 ? kp : cp[k - 1]) : own;
-                    if (offered[j] != WS_INF && offered[j] < dn[j]) old[j] = atomicMin(&dst[n[j]], offered[j]);
-                    if (root) {
+                    const u64 offered = offer_k(s0 + j);
+                    if (offered != WS_INF && offered < seen) dn[j] = atomicMin(&dst[n[j]], offered);
+                    if constexpr (ROOT) {
                         // label set of n = union over its fully matching candidates (monotone min / max relaxations)
-                        if (own_lo < lon[j]) olo[j] = atomicMin(&c.Llo[n[j]], own_lo);
-                        if (own_hi > hin[j]) ohi[j] = atomicMax(&c.Lhi[n[j]], own_hi);
+                        if (own_lo < seen_lo) lon[j] = atomicMin(&c.Llo[n[j]], own_lo);
+                        if (own_hi > seen_hi) hin[j] = atomicMax(&c.Lhi[n[j]], own_hi);
                     }
                 }
             }
         }
 #pragma unroll
         for (int j = 0; j < NB; j++) {
-            const bool improved = offered[j] < old[j] || (root && (own_lo < olo[j] || own_hi > ohi[j]));
+            // dn = 0 where no atomic was issued (no candidate edge, no match, nothing to offer): never "improved"
+            bool improved = offer_k(s0 + j) < dn[j];
+            if constexpr (ROOT) improved = improved || own_lo < lon[j] || own_hi > hin[j];
             ws_stage(st, w, improved, n[j], qout, cnt_out, qcap);
         }
     }
 }
 
-template <int NN>
+// any neighbour count, k at run time
+template <bool ROOT>
 __global__ void __launch_bounds__(256)
-k_ws_sweep_chain(WsC c, int k, int depth, const int *__restrict__ qin, const int *__restrict__ cnt_in,
+k_ws_sweep_chain(WsC c, int k, u64 *__restrict__ dst, const u64 *__restrict__ below, const int *__restrict__ qin, const int *__restrict__ cnt_in,
                  int *__restrict__ qout, int *__restrict__ cnt_out, int qcap)
 {
-    u64 *dst = k == depth ? c.Rt : c.C[k];
     ws_sweep(c.R, qin, cnt_in, qout, cnt_out, qcap,
-             [&](WsStage &st, int w, bool act, int p) { ws_entry_chain<NN>(c, k, depth, dst, st, w, act, p, qout, cnt_out, qcap); });
+             [&](WsStage &st, int w, bool act, int p) { ws_entry_chain<0, 0, ROOT>(c, k, dst, below, st, w, act, p, qout, cnt_out, qcap); });
+}
+// connectivity 1.  These run beside two resident k_fb_iter waves per SIMD, in the 64 registers those leave free, so 64 is
+// DECLARED: the compiler sizes a kernel for the occupancy its LDS allows on a CU of its own, which is well below eight waves
+// per SIMD, and spends the registers that leaves (the K = 3 root form came out at 66).  The forms fit without a spill; tests/test_kernel_resources_cpu.py
+// holds the build to that (registers, zero scratch, LDS).
+template <int K, bool ROOT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(64)))
+k_ws_sweep_chain6(WsC c, int k, u64 *__restrict__ dst, const u64 *__restrict__ below, const int *__restrict__ qin, const int *__restrict__ cnt_in,
+                  int *__restrict__ qout, int *__restrict__ cnt_out, int qcap)
+{
+    ws_sweep(c.R, qin, cnt_in, qout, cnt_out, qcap,
+             [&](WsStage &st, int w, bool act, int p) { ws_entry_chain<6, K, ROOT>(c, k, dst, below, st, w, act, p, qout, cnt_out, qcap); });
 }
 
 // ---- exactness check after a root phase at depth d ------------------------------------------------------------
@@ -1171,6 +1261,24 @@ extern "C" size_t tf_watershed_workspace_bytes(int64_t T, int64_t H, int64_t W, 
 
 struct WsQueues { int *q[2]; int *cnt; int qcap; int *h_cnt; int64_t *processed; };
 
+// one chain-level (ROOT = false) or root-phase (ROOT = true) sweep at level k.  Connectivity 1 has the levels the library
+// starts with (1 .. 3) as compile-time forms; deeper chains, and every other neighbour count, take the run-time k.
+template <int NN, bool ROOT>
+static void ws_launch_chain(unsigned blocks, hipStream_t s, const WsC &c, int k, const int *qin, const int *cnt_in,
+                            int *qout, int *cnt_out, int qcap)
+{
+    u64 *dst = ROOT ? c.Rt : c.C[k];             // what the phase relaxes: the root keys, or chain level k
+    const u64 *below = (!ROOT && k > 1) ? c.C[k - 1] : nullptr;   // C_{k-1}: what an entry is offered at level k (run-time k only)
+    if constexpr (NN == 6) {
+        if (k == 1) hipLaunchKernelGGL((k_ws_sweep_chain6<1, ROOT>), dim3(blocks), dim3(256), 0, s, c, k, dst, below, qin, cnt_in, qout, cnt_out, qcap);
+        else if (k == 2) hipLaunchKernelGGL((k_ws_sweep_chain6<2, ROOT>), dim3(blocks), dim3(256), 0, s, c, k, dst, below, qin, cnt_in, qout, cnt_out, qcap);
+        else if (k == 3) hipLaunchKernelGGL((k_ws_sweep_chain6<3, ROOT>), dim3(blocks), dim3(256), 0, s, c, k, dst, below, qin, cnt_in, qout, cnt_out, qcap);
+        else hipLaunchKernelGGL((k_ws_sweep_chain6<0, ROOT>), dim3(blocks), dim3(256), 0, s, c, k, dst, below, qin, cnt_in, qout, cnt_out, qcap);
+    } else {
+        hipLaunchKernelGGL((k_ws_sweep_chain<ROOT>), dim3(blocks), dim3(256), 0, s, c, k, dst, below, qin, cnt_in, qout, cnt_out, qcap);
+    }
+}
+
 // Run one relaxation phase to its fixpoint.  phase_k = 0: K2/M1; otherwise chain level k (k == depth: root).
 // alg_bytes: the algorithmic bytes the timing facility books on this phase's first batch of sweeps.  The flood's figure is
 // SURVEY section 8(d)'s: 29 B per voxel for ONE ideal sweep over the volume (field 4 + markers 4 + labels 4 + mask 1 + flows
@@ -1196,12 +1304,16 @@ static int ws_run_phase(const WsC &c, int phase_k, int depth, const WsQueues &Q,
             for (int b = 0; b < WS_BATCH; b++) {
                 const int *qin = first ? nullptr : Q.q[parity];
                 const unsigned blocks = first ? nbR : grid_hint;
+                int *qout = Q.q[parity ^ 1];
                 if (phase_k == 0) {
-                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_a<6>, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
-                    else hipLaunchKernelGGL(k_ws_sweep_a<0>, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
+                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_a6, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, qout, Q.cnt + b + 1, Q.qcap);
+                    else hipLaunchKernelGGL(k_ws_sweep_a, dim3(blocks), dim3(256), 0, s, c, qin, Q.cnt + b, qout, Q.cnt + b + 1, Q.qcap);
+                } else if (phase_k == depth) {
+                    if (c.n_nbr == 6) ws_launch_chain<6, true>(blocks, s, c, phase_k, qin, Q.cnt + b, qout, Q.cnt + b + 1, Q.qcap);
+                    else ws_launch_chain<0, true>(blocks, s, c, phase_k, qin, Q.cnt + b, qout, Q.cnt + b + 1, Q.qcap);
                 } else {
-                    if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_chain<6>, dim3(blocks), dim3(256), 0, s, c, phase_k, depth, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
-                    else hipLaunchKernelGGL(k_ws_sweep_chain<0>, dim3(blocks), dim3(256), 0, s, c, phase_k, depth, qin, Q.cnt + b, Q.q[parity ^ 1], Q.cnt + b + 1, Q.qcap);
+                    if (c.n_nbr == 6) ws_launch_chain<6, false>(blocks, s, c, phase_k, qin, Q.cnt + b, qout, Q.cnt + b + 1, Q.qcap);
+                    else ws_launch_chain<0, false>(blocks, s, c, phase_k, qin, Q.cnt + b, qout, Q.cnt + b + 1, Q.qcap);
                 }
                 parity ^= 1;
                 first = false;
@@ -1636,6 +1748,11 @@ static int ws_job_sweeps(tf_ws_job *j)
     int rc = ws_run_phase(c, 0, j->depth_max, j->Q, s, j->max_sweeps, &st[0], 29.0 * (double)j->N);
     if (rc) return rc;
     {
+        TfProfScope ps(TFK_WS_RELAX, 0.0, s);                                      // M1 from the final K2: work the sweeps used to do
+        if (c.n_nbr == 6) hipLaunchKernelGGL(k_ws_sweep_m1<6>, dim3(nbr_blocks), dim3(256), 0, s, c);
+        else hipLaunchKernelGGL(k_ws_sweep_m1<0>, dim3(nbr_blocks), dim3(256), 0, s, c);
+    }
+    {
         TfProfScope ps(TFK_WS_SETUP, 0.0, s);
         hipLaunchKernelGGL(k_ws_edge_masks, dim3(nbr_blocks), dim3(256), 0, s, c, (u64 *)c.emask);
     }
@@ -1786,7 +1903,7 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
     if (R > 0) {
         u64 *pix = ar.take<u64>(R); unsigned *val = ar.take<unsigned>(R); int *nbr = ar.take<int>(R * n_nbr);
         c.pix = pix; c.val = val; c.nbr = nbr;
-        c.KM = ar.take<u64>(2 * R);
+        c.K2 = ar.take<u64>(R); c.M1 = ar.take<u64>(R);
         for (int k = 1; k < depth_max; k++) c.C[k] = ar.take<u64>(R);
         c.Rt = ar.take<u64>(R);
         c.Llo = ar.take<int>(R); c.Lhi = ar.take<int>(R); j->org = ar.take<int>(R);
@@ -1803,11 +1920,11 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
         TF_CHECK_HIP(hipMemsetAsync(d_nan, 0, sizeof(int), s));
         {
             TfProfScope ps(TFK_WS_SETUP, 0.0, s);
-            if (rv) hipLaunchKernelGGL(k_wsr_compact, dim3(nb1), dim3(256), 0, s, field, (const int *)cid, *rv, pix, val, nbr, c.KM, d_nan);
-            else if (n_nbr == 6) hipLaunchKernelGGL(k_ws_compact<6>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.KM, d_nan);
-            else if (n_nbr == 18) hipLaunchKernelGGL(k_ws_compact<18>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.KM, d_nan);
-            else if (n_nbr == 26) hipLaunchKernelGGL(k_ws_compact<26>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.KM, d_nan);
-            else hipLaunchKernelGGL(k_ws_compact<0>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.KM, d_nan);
+            if (rv) hipLaunchKernelGGL(k_wsr_compact, dim3(nb1), dim3(256), 0, s, field, (const int *)cid, *rv, pix, val, nbr, c.K2, c.M1, d_nan);
+            else if (n_nbr == 6) hipLaunchKernelGGL(k_ws_compact<6>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
+            else if (n_nbr == 18) hipLaunchKernelGGL(k_ws_compact<18>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
+            else if (n_nbr == 26) hipLaunchKernelGGL(k_ws_compact<26>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
+            else hipLaunchKernelGGL(k_ws_compact<0>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
         }
         TF_CHECK_LAUNCH();
         {   // the reference's `smaller()` (_watershed.pyx:161-164) is not an order on NaN: its heap then pops in an order
