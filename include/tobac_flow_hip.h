@@ -47,6 +47,7 @@ extern "C" {
 #define TF_F32 0
 #define TF_F64 1
 #define TF_I32 2
+#define TF_U8 3          /* tf_edt2d_frames, tf_label_nanmin only (bool arrays have these bytes) */
 
 /* reductions over the gathered (n_struct, H, W) stack, i.e. the `func` argument of
  * tobac_flow/convolve.py:248-348 for the callables the reference itself passes */
@@ -667,6 +668,39 @@ int tf_label_proportions(const int32_t *labels, const int32_t *flags, const floa
 size_t tf_slice_labels_workspace_bytes(int64_t T, int64_t id_capacity);
 int tf_slice_labels(const int32_t *labels, int64_t T, int64_t hw, int32_t *out, int64_t *n_step_labels_host,
                     void *ws, size_t ws_bytes, void *stream);
+
+/* ---- GLM validation: tobac_flow/validation.py (scripts/dcc_validation.py:145-250) ------------------------------------
+ * tf_edt2d_frames: scipy.ndimage.distance_transform_edt(frame == 0) for every frame of a (T, H, W) volume (validation.py:
+ *   24-36, 52-104), exact and in integers.  A voxel is a FEATURE when its value is != 0 (NaN is one, as NaN == 0 is false
+ *   in NumPy).  vol: TF_U8 (bool), TF_I32, TF_F32 or TF_F64.  d2[t][y][x] = int32 squared distance to the nearest feature
+ *   of frame t; nearest[t][y][x] (may be NULL) = y' * W + x' of such a feature.  A frame without a feature gets INT32_MAX
+ *   and -1.  (H - 1)^2 + (W - 1)^2 < 2^31 is required.  Distances are unique; where several features are equally near
+ *   the one with the smallest |x' - x| is reported, of two at the same |x' - x| the left one, within a column the upper
+ *   one -- the order of the scan, the same in every run (SciPy's choice follows its Voronoi sweep and is not reproduced).
+ *   A column pass (one lane per column, down and up) and a row pass (one workgroup per row, the row's column distances in
+ *   LDS, a scan outward from every pixel that stops at dx^2 >= best).  Frames are processed in chunks: the workspace
+ *   holds one int32 per voxel of a chunk (two where W > 16384, beyond the LDS form) and stays <= 1 GiB unless one frame
+ *   needs more.
+ * tf_edt_cylinder: validation.py:52-104 get_marker_distance_cylinder from the two arrays above.  dist[t][p] (double) =
+ *   sqrt of the smallest d2[k][p] over k = max(t - time_margin, 0) .. min(t + time_margin, T - 1), +inf where all of them
+ *   are INT32_MAX; src[t][p] (int64, may be NULL; needs nearest) = k * hw + nearest[k][p] for the EARLIEST k that holds the
+ *   minimum (np.nanargmin), -1 where there is none.  The double square root is correctly rounded (= np.sqrt).
+ * tf_label_nanmin: np.nanmin of a field over every label (label_utils.py:58-140 apply_func_to_labels with func=np.nanmin,
+ *   validation.py:13-21, 144-152).  labels: int32 (n,); field: TF_U8, TF_F32 or TF_F64 (n,); ids: n_ids int64 label ids on
+ *   the device.  out_min[k] (double) = the minimum over the voxels of ids[k] that are not NaN, NaN where it has none;
+ *   out_count[k] (int64) = the number of those voxels, -1 where the label has no voxel at all or the id lies outside
+ *   [1, n_labels] (the caller's `default`).  One read of labels and field: 64-bit atomicMin on an order-preserving key,
+ *   one per run of equal labels a lane meets, the runs its lanes still hold at the end combined across the wave where they
+ *   agree on the label; minimum and integer count do not depend on arrival order.  -0.0 and +0.0 compare equal
+ *   (+0.0 is returned).  The workspace holds 16 B per label. */
+size_t tf_edt2d_frames_workspace_bytes(int64_t T, int64_t H, int64_t W);
+int tf_edt2d_frames(const void *vol, int dtype, int64_t T, int64_t H, int64_t W, int32_t *d2, int32_t *nearest, void *ws,
+                    size_t ws_bytes, void *stream);
+int tf_edt_cylinder(const int32_t *d2, const int32_t *nearest, int64_t T, int64_t hw, int64_t time_margin, double *dist,
+                    int64_t *src, void *stream);
+size_t tf_label_nanmin_workspace_bytes(int64_t n_labels);
+int tf_label_nanmin(const int32_t *labels, const void *field, int dtype, int64_t n, int64_t n_labels, const int64_t *ids,
+                    int64_t n_ids, double *out_min, int64_t *out_count, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- measurement aid (bench.py's roofline figure) ---------------------------------------------
  * tf_profile_enable(1): every kernel launch of the library is bracketed by HIP events on its own

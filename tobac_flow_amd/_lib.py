@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("TF_LIB_PATH") or os.path.join(_HERE, "csrc", "libtobac_flow_hip.so")
 
 INTERP = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos": 3}
-TF_F32, TF_F64, TF_I32 = 0, 1, 2
+TF_F32, TF_F64, TF_I32, TF_U8 = 0, 1, 2, 3
 FUNC_STACK, FUNC_SOBEL, FUNC_SOBEL_UPHILL, FUNC_SOBEL_DOWNHILL, FUNC_NANMEAN, FUNC_DIFF, FUNC_ANY, FUNC_NANMAX = range(8)
 
 
@@ -132,6 +132,11 @@ _PROTOS = {
     "tf_label_wstats": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_proportions_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int]),
     "tf_label_proportions": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
+    "tf_edt2d_frames_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64]),
+    "tf_edt2d_frames": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_edt_cylinder": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P]),
+    "tf_label_nanmin_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
+    "tf_label_nanmin": (_c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_slice_labels": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_pair_counts": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_sizes": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P]),

@@ -47,6 +47,11 @@ __host__ __device__ inline void ws_vload(const float *p, float v[WS_VEC])
     const float4 q = *(const float4 *)p;
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
 }
+__host__ __device__ inline void ws_vload(const uint8_t *p, uint8_t v[WS_VEC])      // tf_label_nanmin's bool field: one 4-byte load
+{
+    const uchar4 q = *(const uchar4 *)p;
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
 __host__ __device__ inline void ws_vload(const double *p, double v[WS_VEC])
 {
     const double2 a = ((const double2 *)p)[0], b = ((const double2 *)p)[1];

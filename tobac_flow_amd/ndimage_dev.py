@@ -314,3 +314,101 @@ def within_distance(points, shape, radius, device):
     cells = t.from_numpy(cells[ok]).to(device)
     out[cells[:, 0], cells[:, 1]] = True
     return out
+
+
+def _edt_dtype(x):
+    t = _lib.torch()
+    return {t.uint8: _lib.TF_U8, t.bool: _lib.TF_U8, t.int32: _lib.TF_I32, t.float32: _lib.TF_F32, t.float64: _lib.TF_F64}.get(x.dtype)
+
+
+def edt_squared_frames(features, return_nearest=False):
+    """tf_edt2d_frames of a (T, H, W) device tensor whose non-zero voxels (NaN included) are the features: (d2, nearest),
+    the int32 squared distance of every voxel to the nearest feature of its frame and (with return_nearest, else None) the
+    int32 raveled index y' * W + x' of such a feature; INT32_MAX and -1 throughout a frame without features.  Of several
+    equally near features the one with the smallest |x' - x| is reported, then the left one, then the upper one."""
+    t = _lib.torch()
+    L = _lib.lib()
+    if features.dim() != 3 or 0 in features.shape:
+        raise ValueError("a non-empty (T, H, W) volume is required")
+    x = features if _edt_dtype(features) is not None else (features != 0)      # other integer widths: only != 0 matters
+    x = x.contiguous()
+    if x.dtype == t.bool:
+        x = x.view(t.uint8)
+    T, H, W = x.shape
+    d2 = t.empty((T, H, W), dtype=t.int32, device=x.device)
+    nearest = t.empty((T, H, W), dtype=t.int32, device=x.device) if return_nearest else None
+    nbytes = L.tf_edt2d_frames_workspace_bytes(T, H, W)
+    ws = _lib.workspace(nbytes, "edt") if nbytes else None                      # 0: a shape the entry point rejects with its reason
+    _lib.check(L.tf_edt2d_frames(_lib.ptr(x), _edt_dtype(x), T, H, W, _lib.ptr(d2), _lib.ptr(nearest), _lib.ptr(ws),
+                                 ws.numel() if ws is not None else 0, _lib.stream_ptr()), "tf_edt2d_frames")
+    return d2, nearest
+
+
+def edt_cylinder(d2, nearest, time_margin):
+    """tf_edt_cylinder: (float64 distances, int64 source voxels or None) -- per voxel the square root of the smallest d2
+    over the frames t - time_margin .. t + time_margin (inf where none has a feature) and, when `nearest` is given, the
+    raveled index into the volume of the nearest feature of the earliest frame that holds the minimum (-1 where none)."""
+    t = _lib.torch()
+    T, H, W = d2.shape
+    dist = t.empty((T, H, W), dtype=t.float64, device=d2.device)
+    src = t.empty((T, H, W), dtype=t.int64, device=d2.device) if nearest is not None else None
+    _lib.check(_lib.lib().tf_edt_cylinder(_lib.ptr(d2), _lib.ptr(nearest), T, H * W, int(time_margin), _lib.ptr(dist),
+                                          _lib.ptr(src), _lib.stream_ptr()), "tf_edt_cylinder")
+    return dist, src
+
+
+def distance_transform_edt_frames(x, return_distances=True, return_indices=False):
+    """scipy.ndimage.distance_transform_edt(x[t], return_distances=..., return_indices=...) for every frame t of a
+    (T, H, W) device tensor: the float64 distance of every voxel to the nearest voxel of its frame where x == 0, and the
+    (2, T, H, W) int32 row and column indices of that voxel.  Distances equal SciPy's bit for bit (an integer squared
+    distance and one correctly rounded square root).  Where several zero voxels are equally near, the one with the
+    smallest column distance is returned, then the left one, then the upper one; SciPy's choice among them follows its
+    own sweep and may differ.  A frame with NO zero voxel returns inf and -1 (SciPy's result for such a frame is
+    meaningless, and the reference guards against it with np.any).  Returns what SciPy returns: the distances, the
+    indices, or the tuple of both."""
+    if not (return_distances or return_indices):
+        raise RuntimeError("at least one of return_distances/return_indices must be True")
+    t = _lib.torch()
+    d2, nearest = edt_squared_frames(x == 0, return_nearest=return_indices)
+    out = []
+    if return_distances:
+        out.append(edt_cylinder(d2, None, 0)[0])
+    if return_indices:
+        W = x.shape[2]
+        rows = t.div(nearest, W, rounding_mode="floor")
+        out.append(t.stack([rows, t.where(nearest < 0, nearest, nearest - rows * W)]))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def label_nanmin(labels, field, ids):
+    """tf_label_nanmin: (float64 minima, int64 counts) for the label ids `ids` (a 1-D int64 numpy array, every id >= 1):
+    np.nanmin of `field` (bool, uint8, float32 or float64 device tensor; other types are widened to float64) over the
+    voxels of each label of the int32 device tensor `labels`; NaN where the label has no non-NaN voxel; the count of
+    non-NaN voxels, -1 where the label has no voxel at all."""
+    t = _lib.torch()
+    L = _lib.lib()
+    if tuple(labels.shape) != tuple(field.shape):
+        raise ValueError(f"labels {tuple(labels.shape)} and field {tuple(field.shape)} do not have the same shape")
+    ids = np.ascontiguousarray(ids, np.int64)
+    n_ids = ids.size
+    mins = t.full((n_ids,), float("nan"), dtype=t.float64, device=labels.device)
+    counts = t.full((n_ids,), -1, dtype=t.int64, device=labels.device)
+    if n_ids == 0 or labels.numel() == 0:
+        return mins, counts
+    lab = labels.to(t.int32).contiguous()
+    f = field.contiguous()
+    if f.dtype == t.bool:
+        f = f.view(t.uint8)
+    elif f.dtype not in (t.uint8, t.float32, t.float64):
+        f = f.to(t.float64)
+    dtype = {t.uint8: _lib.TF_U8, t.float32: _lib.TF_F32, t.float64: _lib.TF_F64}[f.dtype]
+    top = int(ids.max())
+    n_labels = top if top <= lab.numel() else min(top, int(lab.max()))         # ids beyond the largest label have no voxel
+    if n_labels < 1:
+        return mins, counts
+    ids_t = t.from_numpy(ids).to(labels.device)
+    ws = _lib.workspace(L.tf_label_nanmin_workspace_bytes(n_labels), "label_nanmin")
+    _lib.check(L.tf_label_nanmin(_lib.ptr(lab), _lib.ptr(f), dtype, lab.numel(), n_labels, _lib.ptr(ids_t), n_ids,
+                                 _lib.ptr(mins), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "tf_label_nanmin")
+    return mins, counts

@@ -22,6 +22,7 @@
 struct int4 { int32_t x, y, z, w; };
 struct float4 { float x, y, z, w; };
 struct double2 { double x, y; };
+struct uchar4 { uint8_t x, y, z, w; };
 template <typename T> static T atomicAdd(T *p, T v) { T o = *p; *p = o + v; return o; }
 static unsigned long long atomicMin(unsigned long long *p, unsigned long long v) { unsigned long long o = *p; *p = std::min(o, v); return o; }
 static unsigned long long atomicMax(unsigned long long *p, unsigned long long v) { unsigned long long o = *p; *p = std::max(o, v); return o; }
