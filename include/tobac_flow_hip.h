@@ -74,6 +74,42 @@ size_t tf_to8bit_workspace_bytes(int64_t H, int64_t W);
 int tf_to8bit_pair(const float *frame0, const float *frame1, int64_t H, int64_t W,
                    uint8_t *out0, uint8_t *out1, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- a3b: to_8bit(<normalisation method>(data[i:i+2], **kwargs), 0, 1) -----------------------
+ * the other joint normalisations that tobac_flow/flow.py:411-414 selects by name
+ * (tobac_flow/utils/normalisation_utils.py:59-116), for float32 frames under numpy 2's promotion rules.
+ *   linear        vmin / vmax optional (neither given: the same bytes as tf_to8bit_pair)
+ *   log           vmax optional; vmin is ignored, as in the reference (the data minimum is reused)
+ *   inverse_log   vmin optional; vmax is ignored
+ *   z_score       max_std
+ *   uniform       quantiles in 1 .. TF_NORM_MAX_QUANTILES; the pair must be finite (a NaN makes numpy's edges NaN): the
+ *                 call does not test that -- the caller does (normalise_pair_dev / calculate_flow)
+ *   local_linear  size >= 1; W <= TF_NORM_MAX_ROW (a row is filtered in LDS)
+ * vmin, vmax and max_std are Python numbers as numpy 2 sees them ("weak": rounded to float32 where they meet the data,
+ * double among themselves) unless TF_NORM_F32_SCALARS says that the caller held float32 scalars.  linear with bounds,
+ * uniform and local_linear on NaN-free pairs give the reference's bytes; log, inverse_log, z_score and local_linear
+ * with NaNs evaluate log and the moments in float64 and round, which can move a byte by 1.
+ * Bad arguments: TF_EINVAL; ws_bytes < tf_norm8_workspace_bytes(H, W, method, params): TF_ENOMEM. */
+typedef enum {
+    TF_NORM_LINEAR = 0, TF_NORM_LOG = 1, TF_NORM_INVERSE_LOG = 2, TF_NORM_Z_SCORE = 3, TF_NORM_UNIFORM = 4,
+    TF_NORM_LOCAL_LINEAR = 5
+} TfNormMethod;
+#define TF_NORM_HAS_VMIN 1
+#define TF_NORM_HAS_VMAX 2
+#define TF_NORM_F32_SCALARS 4
+#define TF_NORM_MAX_QUANTILES 1024
+#define TF_NORM_MAX_ROW 8192
+typedef struct {
+    double vmin, vmax;      /* used when the matching TF_NORM_HAS_* flag is set */
+    double max_std;         /* 3   */
+    int64_t quantiles;      /* 256 */
+    int64_t size;           /* 100 */
+    int flags;
+} TfNormParams;
+void tf_norm8_default_params(TfNormParams *params);
+size_t tf_norm8_workspace_bytes(int64_t H, int64_t W, int method, const TfNormParams *params);
+int tf_norm8_pair(const float *frame0, const float *frame1, int64_t H, int64_t W, int method, const TfNormParams *params,
+                  uint8_t *out0, uint8_t *out1, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- a5: dense Farnebaeck flow for one frame pair, BOTH directions ---------------------------
  * replaces cv2.optflow.createOptFlow_Farneback().calc(prev, next, None) and
  * .calc(next, prev, None) as issued by tobac_flow/flow.py:511,516 (model factory

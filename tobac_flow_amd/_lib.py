@@ -28,6 +28,13 @@ class FarnebackParams(ctypes.Structure):
                 ("chain_form", ctypes.c_int), ("status_slot", ctypes.c_int)]
 
 
+class NormParams(ctypes.Structure):
+    _fields_ = [("vmin", ctypes.c_double), ("vmax", ctypes.c_double), ("max_std", ctypes.c_double),
+                ("quantiles", ctypes.c_int64), ("size", ctypes.c_int64), ("flags", ctypes.c_int)]
+
+
+NORM_METHODS = {"linear": 0, "log": 1, "inverse_log": 2, "z_score": 3, "uniform": 4, "local_linear": 5}
+NORM_HAS_VMIN, NORM_HAS_VMAX, NORM_F32_SCALARS = 1, 2, 4
 FB_CHAIN_DEFAULT, FB_CHAIN_ONE_LANE, FB_CHAIN_TWO_PART = 0, 1, 2
 TF_ESTARVED = -6
 
@@ -42,6 +49,9 @@ _PROTOS = {
     "tf_device_count": (_c.c_int, []),
     "tf_to8bit_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
     "tf_to8bit_pair": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_norm8_default_params": (None, [_c.POINTER(NormParams)]),
+    "tf_norm8_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(NormParams)]),
+    "tf_norm8_pair": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(NormParams), _P, _P, _P, _c.c_size_t, _P]),
     "tf_farneback_default_params": (None, [_c.POINTER(FarnebackParams)]),
     "tf_farneback_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.POINTER(FarnebackParams)]),
     "tf_farneback_pair": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.POINTER(FarnebackParams), _P, _P, _P,

@@ -25,7 +25,7 @@ from tobac_flow_amd.label import flow_label, flow_link_overlap
 from tobac_flow_amd.sobel import sobel
 from tobac_flow_amd.utils import mse, select_normalisation_method, select_of_model, to_8bit, warp_flow  # noqa: F401
 from tobac_flow_amd.utils.flow_utils import select_interp_mode
-from tobac_flow_amd.utils.normalisation_utils import linear_norm, to_8bit_pair_dev
+from tobac_flow_amd.utils.normalisation_utils import linear_norm, norm_params_dev, normalise_pair_dev, to_8bit_pair_dev
 from tobac_flow_amd.watershed import watershed
 
 
@@ -442,7 +442,7 @@ def _side_stream(main):
 
 def _calculate_flow_impl(frame_pairs, T, shape, of_model, vr_steps, smoothing_passes, interp_method,
                          norm_name, norm_method, normalisation_kwargs, on_device, max_value=float("inf"), on_batch=None,
-                         workspace_gb=None, split_parts=None, check_out=None):
+                         workspace_gb=None, split_parts=None, check_out=None, stacks=()):
     t = _lib.torch()
     L = _lib.lib()
     H, W = shape
@@ -460,6 +460,16 @@ def _calculate_flow_impl(frame_pairs, T, shape, of_model, vr_steps, smoothing_pa
     # Frame pairs are independent units: they are processed in batches of TF_FLOW_BATCH pairs per set of
     # kernel launches (tf_farneback_batch), which keeps the coarse pyramid levels busy on all CUs.
     linear = norm_name == "linear" and not normalisation_kwargs
+    # the other methods stay on the device when the caller's data was there (host containers keep the host glue byte for
+    # byte); ValueError: only the host form computes what this call asks for
+    norm_dev = False
+    if on_device and not linear:
+        try:
+            norm_params_dev(norm_name, (H, W), **normalisation_kwargs)
+            # uniform: finite stacks only (one reduction and one synchronisation per call)
+            norm_dev = norm_name != "uniform" or all(bool(t.isfinite(s).all()) for s in stacks)
+        except ValueError:
+            pass
     interp = select_interp_mode(interp_method) if smoothing_passes > 0 else 1
     # The fused iteration kernel walks whole columns (OpenCV's running column sums cannot be split over rows,
     # csrc/farneback.hip), so its parallelism is strips x directions x PAIRS and a launch costs a whole number of rounds
@@ -568,6 +578,8 @@ def _calculate_flow_impl(frame_pairs, T, shape, of_model, vr_steps, smoothing_pa
             fa, fb = frame_pairs(i0 + b)
             if linear:
                 to_8bit_pair_dev(fa, fb, out=(prev8[b], next8[b]))
+            elif norm_dev:
+                normalise_pair_dev(norm_name, fa, fb, out=(prev8[b], next8[b]), check_finite=False, **normalisation_kwargs)
             else:   # other normalisations are host glue (not on the production path)
                 pair = np.stack([fa.cpu().numpy(), fb.cpu().numpy()], 0)
                 p8 = to_8bit(norm_method(pair, **normalisation_kwargs), 0, 1)
@@ -735,7 +747,8 @@ def calculate_flow(data, model: str = "Farneback", vr_steps: int = 0, smoothing_
     T = d.shape[0]
     return _calculate_flow_impl(lambda i: (d[i], d[i + 1]), T, tuple(d.shape[1:]), of_model, vr_steps,
                                 smoothing_passes, interp_method, normalisation_method, norm_method,
-                                normalisation_kwargs, on_device, max_value, on_batch, workspace_gb, split_parts, check_out)
+                                normalisation_kwargs, on_device, max_value, on_batch, workspace_gb, split_parts, check_out,
+                                stacks=(d,))
 
 
 def calculate_flow_2(a, b, model: str = "Farneback", vr_steps: int = 0, smoothing_passes: int = 0,
@@ -754,7 +767,7 @@ def calculate_flow_2(a, b, model: str = "Farneback", vr_steps: int = 0, smoothin
     T = da.shape[0]
     return _calculate_flow_impl(lambda i: (da[i], db[i]), T, tuple(da.shape[1:]), of_model, vr_steps,
                                 smoothing_passes, "linear", normalisation_method, norm_method,
-                                normalisation_kwargs, on_device)
+                                normalisation_kwargs, on_device, stacks=(da, db))
 
 
 def calculate_flow_frame(prev_frame, next_frame, of_model, vr_steps: int = 0, smoothing_steps: int = 0,

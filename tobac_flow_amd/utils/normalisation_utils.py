@@ -2,8 +2,10 @@
 
 `to_8bit` and `linear_norm` keep the reference's numpy semantics for arbitrary arrays; inside
 `calculate_flow` the frame-pair composition to_8bit(linear_norm(pair), 0, 1) runs on the GPU
-(`to_8bit_pair_dev`, tf_to8bit_pair).
+(`to_8bit_pair_dev`, tf_to8bit_pair), and so do the other methods when the frames are device tensors
+(`normalise_pair_dev`, tf_norm8_pair).
 """
+import inspect
 from typing import Callable
 
 import numpy as np
@@ -129,6 +131,91 @@ NORMALISATION_METHODS = {
     "uniform": uniform_norm,
     "local_linear": local_linear_norm,
 }
+
+
+# ---- the same compositions on the GPU ----------------------------------------------------------------------------------
+def _norm_scalar(name, value):
+    """(value as a double, is a float32 scalar) of a bound.  numpy 2 rounds a Python number to the array's float32 and
+    computes in float32 with a float32 scalar; any other scalar type (a float64 or integer numpy scalar, an array)
+    would make it compute in another precision, which the kernels do not follow: ValueError."""
+    if isinstance(value, np.float32):
+        return float(value), True
+    if type(value) in (int, float):
+        try:
+            return float(value), False
+        except OverflowError:
+            raise ValueError(f"{name}={value!r} is beyond a double") from None
+    raise ValueError(f"{name} must be a Python number or a float32 scalar for the device form, got {type(value).__name__}")
+
+
+MAX_QUANTILES_DEV, MAX_ROW_DEV = 1024, 8192                  # TF_NORM_MAX_QUANTILES, TF_NORM_MAX_ROW
+
+
+def norm_params_dev(method, shape=None, **kwargs):
+    """(method id, parameter block) of tf_norm8_pair for the host call `select_normalisation_method(method)(pair, **kwargs)`
+    on frames of `shape`.  TypeError for a keyword that call would not take; ValueError where only the host form computes
+    what that call computes (`calculate_flow` then takes the host glue)."""
+    func = select_normalisation_method(method)
+    inspect.signature(func).bind(None, **kwargs)              # TypeError as the host call would raise it
+    p = _lib.NormParams(vmin=0, vmax=0, max_std=3, quantiles=256, size=100, flags=0)     # tf_norm8_default_params
+    f32 = []
+    for name, flag in (("vmin", _lib.NORM_HAS_VMIN), ("vmax", _lib.NORM_HAS_VMAX)):
+        if kwargs.get(name) is not None:
+            value, is32 = _norm_scalar(name, kwargs[name])
+            setattr(p, name, value)
+            p.flags |= flag
+            f32.append(is32)
+    if "max_std" in kwargs:
+        p.max_std, is32 = _norm_scalar("max_std", kwargs["max_std"])
+        f32.append(is32)
+    if any(f32):
+        p.flags |= _lib.NORM_F32_SCALARS
+    if "size" in kwargs:
+        if type(kwargs["size"]) is not int or kwargs["size"] < 1:
+            raise ValueError("size must be an int >= 1 for the device form")
+        p.size = kwargs["size"]
+    if "quantiles" in kwargs:
+        if type(kwargs["quantiles"]) is not int or not 1 <= kwargs["quantiles"] <= MAX_QUANTILES_DEV:
+            raise ValueError(f"quantiles must be an int in 1 .. {MAX_QUANTILES_DEV} for the device form")
+        p.quantiles = kwargs["quantiles"]
+    if shape is not None and method == "local_linear" and shape[1] > MAX_ROW_DEV:
+        raise ValueError(f"the device form of local_linear filters rows of at most {MAX_ROW_DEV} pixels")
+    if shape is not None and method == "uniform" and shape[0] * shape[1] < p.quantiles + 1:
+        raise ValueError("the device form of uniform needs at least 2 (quantiles + 1) values")
+    return _lib.NORM_METHODS[method], p
+
+
+def normalise_pair_dev(method, frame0, frame1, out=None, check_finite=True, **kwargs):
+    """GPU: to_8bit(select_normalisation_method(method)(stack([frame0, frame1]), **kwargs), 0, 1) for two float32
+    device tensors of one shape -> two uint8 torch tensors (`out`: a pair of (H, W) uint8 tensors written in place).
+    Exactness against the host composition: DESIGN.md, "Normalisation methods".  `uniform` covers finite pairs (with a
+    NaN numpy's quantile edges are all NaN): ValueError otherwise; check_finite=False when the caller has tested that."""
+    t = _lib.torch()
+    if method == "linear" and not kwargs:
+        return to_8bit_pair_dev(frame0, frame1, out=out)
+    for f in (frame0, frame1):
+        if not isinstance(f, t.Tensor) or f.dtype != t.float32 or f.dim() != 2 or not f.is_cuda:
+            raise ValueError("normalise_pair_dev takes two (H, W) float32 device tensors")
+    if frame0.shape != frame1.shape:
+        raise ValueError("the two frames must have one shape")
+    mid, p = norm_params_dev(method, tuple(frame0.shape), **kwargs)
+    if method == "uniform" and check_finite and not bool(t.isfinite(frame0).all() & t.isfinite(frame1).all()):
+        raise ValueError("the device form of uniform takes finite pairs")
+    frame0, frame1 = frame0.contiguous(), frame1.contiguous()
+    L = _lib.lib()
+    H, W = frame0.shape
+    o0, o1 = out if out is not None else (_lib.empty((H, W), t.uint8), _lib.empty((H, W), t.uint8))
+    for o in (o0, o1):
+        if o.dtype != t.uint8 or tuple(o.shape) != (H, W) or not o.is_contiguous():
+            raise ValueError("out must be two contiguous (H, W) uint8 tensors")
+    nbytes = L.tf_norm8_workspace_bytes(H, W, mid, p)
+    if nbytes == 0:
+        _lib.check(L.tf_norm8_pair(None, None, H, W, mid, p, None, None, None, 0, None), "tf_norm8_pair")   # says why
+    ws = _lib.workspace(nbytes, "norm8")
+    rc = L.tf_norm8_pair(_lib.ptr(frame0), _lib.ptr(frame1), H, W, mid, p, _lib.ptr(o0), _lib.ptr(o1),
+                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    _lib.check(rc, "tf_norm8_pair")
+    return o0, o1
 
 
 def select_normalisation_method(method: str) -> Callable:
