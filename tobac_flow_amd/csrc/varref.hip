@@ -6,12 +6,12 @@
 // modules/video/src/variational_refinement.cpp, restated from the published algorithm (SURVEY.md Appendix A.2;
 // PARITY UNPINNED: no OpenCV in the build image, the reference holds no vectors for this stage).
 //
-//   k_vr_prepare   I1 warped by the flow (bilinear, coordinates quantised to 1/32 px, replicated border), averaged
-//                  image, Iz, and all first / second central differences (Sobel ksize 1, replicated border) on ONE LDS
-//                  tile with a 2-pixel halo: the eight derivative planes are written once (32 B / px), nothing else
-//                  touches HBM
-//   k_vr_system    smoothness weights of the current flow W + dW (forward differences, replicated border; each
-//                  weight shared with the right / lower neighbour through a lane shuffle / LDS) and
+//   k_vr_prepare   I1 warped by the flow (bilinear, coordinates quantised to 1/32 px, replicated border), the averaged
+//                  image and Iz: one float2 plane A (8 B / px) -- the sources of every derivative
+//   k_vr_system    on an LDS tile of A, W and dW: the first / second central differences of the averaged image and of Iz
+//                  (Sobel ksize 1, replicated border: single subtractions at clamped neighbour coordinates), the
+//                  smoothness weights of the current flow W + dW (forward differences, replicated border; each weight
+//                  computed once per tile and shared with the right / lower neighbour through LDS) and
 //                  the 2x2 system of every pixel: data term (robust colour- and gradient-constancy weights) plus the
 //                  smoothness contributions of its four edges, accumulated in OpenCV's pass order (red before black,
 //                  horizontal before vertical -- the order at a pixel depends on its colour)
@@ -19,8 +19,8 @@
 // Every float expression is evaluated as written (-ffp-contract=off, correctly rounded divide / sqrt), so the result
 // is bit-identical to the oracle's C restatement (oracle/c/varref.c).
 //
-// HBM layout (planar, per flow direction): D1 = float4 {Ix, Iy, Ixz, Iyz}, D2 = float4 {Ixx, Ixy, Iyy, Iz},
-// S = float4 {A11, A22, b1, b2}, A12 float, wt float, W float2 (the input flow), dW float2.
+// HBM layout (planar, per flow direction): A = float2 {avg, Iz}, S = float4 {A11, A22, b1, b2}, A12 float, wt float,
+// W float2 (the input flow), dW float2 and its ping-pong partner: 48 B of workspace per pixel.
 #include "tf_common.h"
 
 struct VrP { float alpha2, delta2, gamma2, omega, zeta2, eps2; };
@@ -32,83 +32,49 @@ __device__ __forceinline__ int vr_clampi(int v, int hi) { return v < 0 ? 0 : (v 
 
 #define VR_TW 64
 #define VR_TH 16
-#define VR_LW (VR_TW + 4)
-#define VR_LH (VR_TH + 4)
 
 __global__ void __launch_bounds__(256)
 k_vr_prepare(const uint8_t *__restrict__ I0, const uint8_t *__restrict__ I1, const float2 *__restrict__ flow,
-             int H, int W, float4 *__restrict__ D1, float4 *__restrict__ D2, VrB bs)
+             int H, int W, float2 *__restrict__ A, VrB bs)
 {
-    __shared__ float s_avg[VR_LH][VR_LW], s_iz[VR_LH][VR_LW], s_ix[VR_LH][VR_LW], s_iy[VR_LH][VR_LW];
     {   // image blockIdx.z of a batch (tf_varref_batch): the same tile code on that image's arrays
         const int64_t b = blockIdx.z;
-        I0 += b * bs.img; I1 += b * bs.img; flow += b * bs.flow; D1 += b * bs.plane; D2 += b * bs.plane;
+        I0 += b * bs.img; I1 += b * bs.img; flow += b * bs.flow; A += b * bs.plane;
     }
-    const int x0 = blockIdx.x * VR_TW - 2, y0 = blockIdx.y * VR_TH - 2;
-    // warped / averaged image and Iz on the tile + 2 halo (in-image positions only; neighbours are clamped later).
+    const int x0 = blockIdx.x * VR_TW, y0 = blockIdx.y * VR_TH;
+    // warped / averaged image and Iz of the tile's pixels; the differences are formed where they are used (k_vr_system).
     // Three stages so that a thread's loads are in flight together: flow + I0 of all its positions, then the four I1
-    // taps of all of them (their addresses need the flow), then the arithmetic and the LDS stores.
-    {
-        constexpr int NL = (VR_LW * VR_LH + 255) / 256;
-        float2 f[NL]; float i0[NL]; bool ok[NL];
+    // taps of all of them (their addresses need the flow), then the arithmetic and the stores.
+    constexpr int NL = VR_TW * VR_TH / 256;
+    float2 f[NL]; float i0[NL]; bool ok[NL]; int64_t p[NL];
 #pragma unroll
-        for (int j = 0; j < NL; j++) {
-            const int i = threadIdx.x + 256 * j, ly = i / VR_LW, lx = i - ly * VR_LW;
-            const int x = x0 + lx, y = y0 + ly;
-            ok[j] = i < VR_LW * VR_LH && x >= 0 && y >= 0 && x < W && y < H;
-            const int64_t p = ok[j] ? (int64_t)y * W + x : 0;
-            f[j] = flow[p]; i0[j] = (float)I0[p];
-        }
-        float v[NL][4], wgt[NL][4];
-#pragma unroll
-        for (int j = 0; j < NL; j++) {
-            const int i = threadIdx.x + 256 * j, ly = i / VR_LW, lx = i - ly * VR_LW;
-            const int x = x0 + lx, y = y0 + ly;
-            const float mx = (float)x + f[j].x, my = (float)y + f[j].y;
-            const int fx = tf_cvround(mx * 32.f), fy = tf_cvround(my * 32.f);
-            const int sx = tf_sat_short(fx >> 5), sy = tf_sat_short(fy >> 5);
-            const int ax = fx & 31, ay = fy & 31;
-            const float tx1 = (float)ax * (1.f / 32.f), tx0 = 1.f - tx1, ty1 = (float)ay * (1.f / 32.f), ty0 = 1.f - ty1;
-            wgt[j][0] = ty0 * tx0; wgt[j][1] = ty0 * tx1; wgt[j][2] = ty1 * tx0; wgt[j][3] = ty1 * tx1;
-            const int xa = vr_clampi(sx, W - 1), xb = vr_clampi(sx + 1, W - 1), ya = vr_clampi(sy, H - 1), yb = vr_clampi(sy + 1, H - 1);
-            v[j][0] = (float)I1[(int64_t)ya * W + xa]; v[j][1] = (float)I1[(int64_t)ya * W + xb];
-            v[j][2] = (float)I1[(int64_t)yb * W + xa]; v[j][3] = (float)I1[(int64_t)yb * W + xb];
-        }
-#pragma unroll
-        for (int j = 0; j < NL; j++) {
-            if (!ok[j]) continue;
-            const int i = threadIdx.x + 256 * j, ly = i / VR_LW, lx = i - ly * VR_LW;
-            const float warped = v[j][0] * wgt[j][0] + v[j][1] * wgt[j][1] + v[j][2] * wgt[j][2] + v[j][3] * wgt[j][3];
-            s_avg[ly][lx] = (i0[j] + warped) * 0.5f;
-            s_iz[ly][lx] = warped - i0[j];
-        }
-    }
-    __syncthreads();
-    // first differences of the averaged image on the tile + 1 halo (replicated border = clamped neighbour coordinates)
-    for (int i = threadIdx.x; i < VR_LW * VR_LH; i += 256) {
-        const int ly = i / VR_LW, lx = i - ly * VR_LW;
-        if (lx < 1 || ly < 1 || lx >= VR_LW - 1 || ly >= VR_LH - 1) continue;
+    for (int j = 0; j < NL; j++) {
+        const int i = threadIdx.x + 256 * j, ly = i / VR_TW, lx = i - ly * VR_TW;
         const int x = x0 + lx, y = y0 + ly;
-        if (x < 0 || y < 0 || x >= W || y >= H) continue;
-        const int xr = vr_clampi(x + 1, W - 1) - x0, xl = vr_clampi(x - 1, W - 1) - x0;
-        const int yd = vr_clampi(y + 1, H - 1) - y0, yu = vr_clampi(y - 1, H - 1) - y0;
-        s_ix[ly][lx] = s_avg[ly][xr] - s_avg[ly][xl];
-        s_iy[ly][lx] = s_avg[yd][lx] - s_avg[yu][lx];
+        ok[j] = x < W && y < H;
+        p[j] = ok[j] ? (int64_t)y * W + x : 0;
+        f[j] = flow[p[j]]; i0[j] = (float)I0[p[j]];
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < VR_TW * VR_TH; i += 256) {
-        const int ty = i / VR_TW, tx = i - ty * VR_TW;
-        const int lx = tx + 2, ly = ty + 2;
+    float v[NL][4], wgt[NL][4];
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+        const int i = threadIdx.x + 256 * j, ly = i / VR_TW, lx = i - ly * VR_TW;
         const int x = x0 + lx, y = y0 + ly;
-        if (x >= W || y >= H) continue;
-        const int xr = vr_clampi(x + 1, W - 1) - x0, xl = vr_clampi(x - 1, W - 1) - x0;
-        const int yd = vr_clampi(y + 1, H - 1) - y0, yu = vr_clampi(y - 1, H - 1) - y0;
-        const float ixz = s_iz[ly][xr] - s_iz[ly][xl], iyz = s_iz[yd][lx] - s_iz[yu][lx];
-        const float ixx = s_ix[ly][xr] - s_ix[ly][xl], ixy = s_ix[yd][lx] - s_ix[yu][lx];
-        const float iyy = s_iy[yd][lx] - s_iy[yu][lx];
-        const int64_t p = (int64_t)y * W + x;
-        D1[p] = make_float4(s_ix[ly][lx], s_iy[ly][lx], ixz, iyz);
-        D2[p] = make_float4(ixx, ixy, iyy, s_iz[ly][lx]);
+        const float mx = (float)x + f[j].x, my = (float)y + f[j].y;
+        const int fx = tf_cvround(mx * 32.f), fy = tf_cvround(my * 32.f);
+        const int sx = tf_sat_short(fx >> 5), sy = tf_sat_short(fy >> 5);
+        const int ax = fx & 31, ay = fy & 31;
+        const float tx1 = (float)ax * (1.f / 32.f), tx0 = 1.f - tx1, ty1 = (float)ay * (1.f / 32.f), ty0 = 1.f - ty1;
+        wgt[j][0] = ty0 * tx0; wgt[j][1] = ty0 * tx1; wgt[j][2] = ty1 * tx0; wgt[j][3] = ty1 * tx1;
+        const int xa = vr_clampi(sx, W - 1), xb = vr_clampi(sx + 1, W - 1), ya = vr_clampi(sy, H - 1), yb = vr_clampi(sy + 1, H - 1);
+        v[j][0] = (float)I1[(int64_t)ya * W + xa]; v[j][1] = (float)I1[(int64_t)ya * W + xb];
+        v[j][2] = (float)I1[(int64_t)yb * W + xa]; v[j][3] = (float)I1[(int64_t)yb * W + xb];
+    }
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+        if (!ok[j]) continue;
+        const float warped = v[j][0] * wgt[j][0] + v[j][1] * wgt[j][1] + v[j][2] * wgt[j][2] + v[j][3] * wgt[j][3];
+        A[p[j]] = make_float2((i0[j] + warped) * 0.5f, warped - i0[j]);
     }
 }
 
@@ -118,7 +84,7 @@ k_vr_prepare(const uint8_t *__restrict__ I0, const uint8_t *__restrict__ I1, con
 // special values.  The reciprocal and its Newton step depend on d alone; the scalings and the fix-up do nothing when n
 // is 0 or 2^-100 < |n| < 2^96 |d| and the quotient is a normal number.  vr_div_shared performs exactly the remaining
 // five operations and the fix-up (which also gives -0 / d its sign), so its result is the hardware division's bit for bit in that range.  It is used only where the
-// range is guaranteed: the derivative planes of k_vr_prepare are exact multiples of 2^-11 of magnitude <= 1020 (sums
+// range is guaranteed: the derivative values k_vr_system forms are exact multiples of 2^-11 of magnitude <= 1020 (sums
 // and differences of uint8 values and of bilinear samples with 1/32-quantised weights, all exact in float), so a
 // product of two of them is 0 or lies in [2^-22, 2^20], and the denominators lie in [zeta^2, 2^22].
 // tf_selftest_shared_divide compares the two forms on random operands of that range (tests/test_gpu_parity.py).
@@ -180,60 +146,55 @@ template <bool FAST> __device__ __forceinline__ float vr_over_sqrt(float a, floa
 
 __device__ __forceinline__ float2 vr_add2(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 
-// The smoothness weights are formed here rather than in a pass of their own (16 B read + 4 B written, and a 4 B read here):
-// every thread computes the weight of ITS pixel (written to `wt` for the SOR kernel), the left neighbour's weight comes
-// from the neighbouring lane (lane 0 computes it itself), the upper neighbour's from the wave above through LDS (the first
-// wave of the 64 x 4 block computes the row above itself): 1.27 weights per pixel, each the same expression (vr_weight).
-template <bool FAST = false>
-__global__ void __launch_bounds__(256)
-k_vr_system(const float4 *__restrict__ D1, const float4 *__restrict__ D2, const float2 *__restrict__ Wf,
-            const float2 *__restrict__ dW, int H, int W, VrP P, float4 *__restrict__ S, float *__restrict__ A12o,
-            float *__restrict__ wt, VrB bs)
+// ---- the 2x2 system of every pixel, from the sources -------------------------------------------------------------------
+// One 256-thread workgroup owns a VRS_TW x VRS_TH tile and stages in LDS, with replicated-border (clamped) coordinates:
+//   s_a   A = {avg, Iz} over the tile + 2          s_w, s_d   W and dW over the tile + 1          (origin x0 - 2 in x for all)
+// then, after a barrier, every smoothness weight of the tile + 1 up / left ONCE in full-exec passes (s_wt), and after a second
+// barrier the systems: wave w owns the tile rows w and w + 4, lane l the pixel pair (2l, 2l + 1) of the row -- one red and one
+// black pixel, whose colours are a per-wave constant, so both accumulation orders are straight-line code.  Rows and row clamps
+// are scalars, column clamps per-thread constants; a tile whose columns all lie two pixels inside the image (XIN) has none.
+// The seven difference planes are k_vr_prepare's former expressions on the staged values: first differences at clamped
+// neighbour coordinates, second differences of first differences taken at the NEIGHBOUR's clamped neighbours.
+#define VRS_TW 128
+#define VRS_TH 8
+#define VRS_AW (VRS_TW + 4)
+#define VRS_AH (VRS_TH + 4)
+#define VRS_FH (VRS_TH + 2)
+#define VRS_WH (VRS_TH + 1)
+static_assert(VRS_TW == 128 && VRS_TH == 8, "one wave per tile row, two rows per wave; the extra weight passes assume 8 rows");
+
+struct VrsX { int c, l, r, ll, lr, rl, rr; };                      // LDS columns of a pixel, its clamped neighbours and theirs
+
+template <bool XIN>
+__device__ __forceinline__ VrsX vrs_columns(int x, int x0, int W)
 {
-    __shared__ float s_w[4][64];
-    {
-        const int64_t b = blockIdx.z;
-        D1 += b * bs.plane; D2 += b * bs.plane; Wf += b * bs.flow; S += b * bs.plane; A12o += b * bs.plane; wt += b * bs.plane;
-        if (dW) dW += b * bs.plane;
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + wv;
-    const bool in = x < W && y < H;
-    const int64_t j = in ? (int64_t)y * W + x : 0;
-    const float2 z2 = make_float2(0.f, 0.f);
-    const bool has_r = x + 1 < W, has_l = x > 0, has_d = y + 1 < H, has_u = y > 0;
-    // EVERY load of the thread is issued here, before the first use: a missing neighbour reads the pixel itself (the
-    // value the replicated border stands for), so the loads are unconditional and in flight together, and the
-    // derivative planes arrive while the weights are being formed.  (Loads behind the weights' barrier, or behind
-    // per-neighbour branches, cost the kernel six dependent memory round trips.)
-    const int64_t jr = (in && has_r) ? j + 1 : j, jl = (in && has_l) ? j - 1 : j;
-    const int64_t jd = (in && has_d) ? j + W : j, ju = (in && has_u) ? j - W : j;
-    const int64_t jdl = (in && has_l && has_d) ? j + W - 1 : jl, jur = (in && has_u && has_r) ? j - W + 1 : ju;
-    const float4 d1 = D1[j], d2 = D2[j];
-    const float2 w0 = Wf[j], wr = Wf[jr], wlf = Wf[jl], wd = Wf[jd], wuf = Wf[ju];
-    float2 d = z2, dr = z2, dd = z2, dl = z2, ddl = z2, dup = z2, dur = z2, wur = z2;
-    if (dW) { d = dW[j]; dr = dW[jr]; dd = dW[jd]; dl = dW[jl]; ddl = dW[jdl]; }
-    const float2 wdl = Wf[jdl];
-    if (wv == 0) { wur = Wf[jur]; if (dW) { dup = dW[ju]; dur = dW[jur]; } }
-    const float2 cO = vr_add2(w0, d);
-    const float wp = vr_weight<FAST>(cO, vr_add2(wr, dr), vr_add2(wd, dd), P);      // missing neighbour = the pixel itself
-    if (in) wt[j] = wp;
-    s_w[wv][lane] = wp;
-    float wl = __shfl_up(wp, 1);
-    if (lane == 0 && in && has_l) {
-        // weight of (x - 1, y): its right neighbour is this pixel, its lower one (x - 1, y + 1) or itself
-        wl = vr_weight<FAST>(vr_add2(wlf, dl), cO, vr_add2(wdl, ddl), P);
-    }
-    float wu0 = 0.f;
-    if (wv == 0 && in && has_u) {
-        // weight of (x, y - 1): its lower neighbour is this pixel, its right one (x + 1, y - 1) or itself
-        wu0 = vr_weight<FAST>(vr_add2(wuf, dup), vr_add2(wur, dur), cO, P);
-    }
-    __syncthreads();
-    float wu = wv == 0 ? wu0 : s_w[wv > 0 ? wv - 1 : 0][lane];
-    if (!in) return;
-    wl = has_l ? wl : 0.f; wu = has_u ? wu : 0.f;
-    const float Ix = d1.x, Iy = d1.y, Ixz = d1.z, Iyz = d1.w, Ixx = d2.x, Ixy = d2.y, Iyy = d2.z, Iz = d2.w;
+    VrsX X;
+    X.c = x - x0 + 2;
+    if (XIN) { X.l = X.c - 1; X.r = X.c + 1; X.ll = X.c - 2; X.lr = X.c; X.rl = X.c; X.rr = X.c + 2; return X; }
+    const int l = vr_clampi(x - 1, W - 1), r = vr_clampi(x + 1, W - 1), o = 2 - x0;
+    X.l = l + o; X.r = r + o;
+    X.ll = vr_clampi(l - 1, W - 1) + o; X.lr = vr_clampi(l + 1, W - 1) + o;
+    X.rl = vr_clampi(r - 1, W - 1) + o; X.rr = vr_clampi(r + 1, W - 1) + o;
+    return X;
+}
+
+struct VrsY { int c, u, d, uu, ud, du, dd; };                      // s_a row offsets (elements), the same scheme
+
+// one pixel: fc = its flow-array offset (row * VRS_AW + column), red = its colour
+template <bool FAST>
+__device__ __forceinline__ void vrs_pixel(const float2 *s_a, const float2 *s_w, const float2 *s_d, const float *s_wt,
+                                          const VrsX X, const VrsY Y, int fc, bool red, bool has_l, bool has_r, bool has_u, bool has_d,
+                                          const VrP &P, float4 &So, float &A12o, float &wpo)
+{
+    const float2 aL = s_a[Y.c + X.l], aR = s_a[Y.c + X.r], aU = s_a[Y.u + X.c], aD = s_a[Y.d + X.c];
+    const float Ix = aR.x - aL.x, Iy = aD.x - aU.x, Ixz = aR.y - aL.y, Iyz = aD.y - aU.y, Iz = s_a[Y.c + X.c].y;
+    const float Ixx = (s_a[Y.c + X.rr].x - s_a[Y.c + X.rl].x) - (s_a[Y.c + X.lr].x - s_a[Y.c + X.ll].x);
+    const float Ixy = (s_a[Y.d + X.r].x - s_a[Y.d + X.l].x) - (s_a[Y.u + X.r].x - s_a[Y.u + X.l].x);
+    const float Iyy = (s_a[Y.dd + X.c].x - s_a[Y.du + X.c].x) - (s_a[Y.ud + X.c].x - s_a[Y.uu + X.c].x);
+    // a missing neighbour reads the pixel itself (the value the replicated border stands for)
+    const float2 w0 = s_w[fc], wr = s_w[fc + 1], wlf = s_w[fc - 1], wd = s_w[fc + VRS_AW], wuf = s_w[fc - VRS_AW], d = s_d[fc];
+    const float wp = s_wt[fc];
+    const float wl = has_l ? s_wt[fc - 1] : 0.f, wu = has_u ? s_wt[fc - VRS_AW] : 0.f;
     const float du = d.x, dv = d.y;
     // ComputeDataTerm.  The fifteen quotients whose numerator is a product of two derivative values share the
     // reciprocal work of their three denominators (vr_div_shared: bit-identical to `/` in their range, see there)
@@ -264,8 +225,7 @@ k_vr_system(const float4 *__restrict__ D1, const float4 *__restrict__ D2, const 
     const float lft_ux = wl * (w0.x - wlf.x), lft_vx = wl * (w0.y - wlf.y);
     const float own_uy = wp * (wd.x - w0.x), own_vy = wp * (wd.y - w0.y);
     const float up_uy = wu * (w0.x - wuf.x), up_vy = wu * (w0.y - wuf.y);
-    const bool red = ((x + y) & 1) == 0;
-    if (red) {
+    if (red) {                                                       // wave-uniform
         if (has_r) { b1 += own_ux; A11 += wp; b2 += own_vx; A22 += wp; }
         if (has_l) { b1 -= lft_ux; A11 += wl; b2 -= lft_vx; A22 += wl; }
         if (has_d) { b1 += own_uy; A11 += wp; b2 += own_vy; A22 += wp; }
@@ -276,8 +236,124 @@ k_vr_system(const float4 *__restrict__ D1, const float4 *__restrict__ D2, const 
         if (has_u) { b1 -= up_uy; A11 += wu; b2 -= up_vy; A22 += wu; }
         if (has_d) { b1 += own_uy; A11 += wp; b2 += own_vy; A22 += wp; }
     }
-    S[j] = make_float4(A11, A22, b1, b2);
-    A12o[j] = A12;
+    So = make_float4(A11, A22, b1, b2); A12o = A12; wpo = wp;
+}
+
+template <bool FAST, bool XIN>
+__device__ __forceinline__ void vrs_rows(const float2 *s_a, const float2 *s_w, const float2 *s_d, const float *s_wt, int wv, int lane,
+                                         int x0, int y0, int H, int W, const VrP &P, float4 *__restrict__ S, float *__restrict__ A12o,
+                                         float *__restrict__ wt)
+{
+    const int x = x0 + 2 * lane;
+    const VrsX Xa = vrs_columns<XIN>(x, x0, W), Xb = vrs_columns<XIN>(x + 1, x0, W);
+    const bool in_a = XIN || x < W, in_b = XIN || x + 1 < W;
+    const bool has_la = XIN || x > 0, has_ra = in_b, has_rb = XIN || x + 2 < W;
+#pragma unroll
+    for (int k = 0; k < VRS_TH / 4; k++) {
+        const int r = wv + 4 * k, y = y0 + r;                        // scalars
+        if (y >= H) continue;
+        const int yu = vr_clampi(y - 1, H - 1), yd = vr_clampi(y + 1, H - 1), o = 2 - y0;
+        VrsY Y;
+        Y.c = (r + 2) * VRS_AW; Y.u = (yu + o) * VRS_AW; Y.d = (yd + o) * VRS_AW;
+        Y.uu = (vr_clampi(yu - 1, H - 1) + o) * VRS_AW; Y.ud = (vr_clampi(yu + 1, H - 1) + o) * VRS_AW;
+        Y.du = (vr_clampi(yd - 1, H - 1) + o) * VRS_AW; Y.dd = (vr_clampi(yd + 1, H - 1) + o) * VRS_AW;
+        const bool has_u = y > 0, has_d = y + 1 < H, red_a = (r & 1) == 0;     // x0 and y0 are even
+        const int fc = (r + 1) * VRS_AW + 2 * lane + 2;
+        float4 Sa, Sb; float a12a, a12b, wpa, wpb;
+        vrs_pixel<FAST>(s_a, s_w, s_d, s_wt, Xa, Y, fc, red_a, has_la, has_ra, has_u, has_d, P, Sa, a12a, wpa);
+        vrs_pixel<FAST>(s_a, s_w, s_d, s_wt, Xb, Y, fc + 1, !red_a, true, has_rb, has_u, has_d, P, Sb, a12b, wpb);
+        const int64_t j = (int64_t)y * W + x;
+        if (in_a) { S[j] = Sa; A12o[j] = a12a; wt[j] = wpa; }
+        if (in_b) { S[j + 1] = Sb; A12o[j + 1] = a12b; wt[j + 1] = wpb; }
+    }
+}
+
+template <bool FAST = false>
+__global__ void __launch_bounds__(256)
+k_vr_system(const float2 *__restrict__ A, const float2 *__restrict__ Wf, const float2 *__restrict__ dW, int H, int W, VrP P,
+            float4 *__restrict__ S, float *__restrict__ A12o, float *__restrict__ wt, VrB bs)
+{
+    __shared__ __align__(16) float2 s_a[VRS_AH * VRS_AW], s_w[VRS_FH * VRS_AW], s_d[VRS_FH * VRS_AW];
+    __shared__ __align__(16) float s_wt[VRS_WH * VRS_AW];
+    {
+        const int64_t b = blockIdx.z;
+        A += b * bs.plane; Wf += b * bs.flow; S += b * bs.plane; A12o += b * bs.plane; wt += b * bs.plane;
+        if (dW) dW += b * bs.plane;
+    }
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int x0 = blockIdx.x * VRS_TW, y0 = blockIdx.y * VRS_TH;
+    const float2 z2 = make_float2(0.f, 0.f);
+    // Stage 1: every load of the thread, then the LDS stores.  Wave w loads the rows w, w + 4, w + 8 of each array, a lane
+    // the columns lane and lane + 64; the last four columns of all rows are one more load of wave 0 (A), 2 (W) and 3 (dW).
+    {
+        const int gx0 = vr_clampi(x0 - 2 + lane, W - 1), gx1 = vr_clampi(x0 + 62 + lane, W - 1);
+        float2 ta[3][2], tw[3][2], td[3][2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int r = wv + 4 * k;
+            const float2 *row = A + (int64_t)vr_clampi(y0 - 2 + r, H - 1) * W;
+            ta[k][0] = row[gx0]; ta[k][1] = row[gx1];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int r = wv + 4 * k;
+            tw[k][0] = tw[k][1] = td[k][0] = td[k][1] = z2;
+            if (r < VRS_FH) {
+                const int64_t ro = (int64_t)vr_clampi(y0 - 1 + r, H - 1) * W;
+                tw[k][0] = Wf[ro + gx0]; tw[k][1] = Wf[ro + gx1];
+                if (dW) { td[k][0] = dW[ro + gx0]; td[k][1] = dW[ro + gx1]; }
+            }
+        }
+        // tail columns 128 .. 131: lane -> row lane / 4, column 128 + lane % 4
+        const int tr = lane >> 2, tc = 128 + (lane & 3), gxt = vr_clampi(x0 - 2 + tc, W - 1);
+        float2 tt = z2;
+        if (wv == 0) {
+            if (tr < VRS_AH) tt = A[(int64_t)vr_clampi(y0 - 2 + tr, H - 1) * W + gxt];
+        } else if (wv == 2) {
+            if (tr < VRS_FH) tt = Wf[(int64_t)vr_clampi(y0 - 1 + tr, H - 1) * W + gxt];
+        } else if (wv == 3) {
+            if (tr < VRS_FH && dW) tt = dW[(int64_t)vr_clampi(y0 - 1 + tr, H - 1) * W + gxt];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int r = wv + 4 * k;
+            s_a[r * VRS_AW + lane] = ta[k][0]; s_a[r * VRS_AW + 64 + lane] = ta[k][1];
+            if (r < VRS_FH) {
+                s_w[r * VRS_AW + lane] = tw[k][0]; s_w[r * VRS_AW + 64 + lane] = tw[k][1];
+                s_d[r * VRS_AW + lane] = td[k][0]; s_d[r * VRS_AW + 64 + lane] = td[k][1];
+            }
+        }
+        if (wv == 0) { if (tr < VRS_AH) s_a[tr * VRS_AW + tc] = tt; }
+        else if (wv == 2) { if (tr < VRS_FH) s_w[tr * VRS_AW + tc] = tt; }
+        else if (wv == 3) { if (tr < VRS_FH) s_d[tr * VRS_AW + tc] = tt; }
+    }
+    __syncthreads();
+    // Stage 2: the weight of every pixel of the tile + 1 up / left, each once (vr_weight; the staged border is replicated, so
+    // a missing right / lower neighbour is the pixel itself).  Flow-array rows 0 .. 8, columns 1 .. 129: four passes of
+    // a wave over its rows w and w + 4 (columns 2 .. 129), and a fifth in which wave 1 takes column 1 of all rows and
+    // waves 2 and 3 the two halves of row 8.
+    {
+        auto weight_at = [&](int o) {
+            return vr_weight<FAST>(vr_add2(s_w[o], s_d[o]), vr_add2(s_w[o + 1], s_d[o + 1]), vr_add2(s_w[o + VRS_AW], s_d[o + VRS_AW]), P);
+        };
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const int o = (wv + 4 * (p >> 1)) * VRS_AW + 2 + 64 * (p & 1) + lane;
+            s_wt[o] = weight_at(o);
+        }
+        if (wv == 1) {
+            if (lane < VRS_WH) { const int o = lane * VRS_AW + 1; s_wt[o] = weight_at(o); }
+        } else if (wv >= 2) {
+            const int o = VRS_TH * VRS_AW + 2 + 64 * (wv - 2) + lane;
+            s_wt[o] = weight_at(o);
+        }
+    }
+    __syncthreads();
+    // Stage 3: the systems
+    if (x0 >= 2 && x0 + VRS_TW + 2 <= W)
+        vrs_rows<FAST, true>(s_a, s_w, s_d, s_wt, wv, lane, x0, y0, H, W, P, S, A12o, wt);
+    else
+        vrs_rows<FAST, false>(s_a, s_w, s_d, s_wt, wv, lane, x0, y0, H, W, P, S, A12o, wt);
 }
 
 // one colour of one red-black SOR sweep: thread -> the pixel of that colour in its pixel pair
@@ -492,8 +568,8 @@ extern "C" size_t tf_varref_workspace_bytes_batch(int64_t B, int64_t H, int64_t 
 {
     if (H <= 0 || W <= 0 || B <= 0) return 0;
     const size_t n = vr_plane(H * W, B) * (size_t)B;
-    // D1, D2, S (float4), A12, wt (float), dW and its ping-pong partner (float2)
-    return 3 * tf_align_up(n * 16, 256) + 2 * tf_align_up(n * 4, 256) + 2 * tf_align_up(n * 8, 256) + 4096;
+    // S (float4), A12, wt (float), A, dW and its ping-pong partner (float2)
+    return tf_align_up(n * 16, 256) + 2 * tf_align_up(n * 4, 256) + 3 * tf_align_up(n * 8, 256) + 4096;
 }
 extern "C" size_t tf_varref_workspace_bytes(int64_t H, int64_t W) { return tf_varref_workspace_bytes_batch(1, H, W); }
 
@@ -527,7 +603,8 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
     const int64_t n = H * W;
     const int64_t np = (int64_t)vr_plane(n, B);
     TfArena ar(ws, ws_bytes);
-    float4 *D1 = ar.take<float4>(np * B), *D2 = ar.take<float4>(np * B), *S = ar.take<float4>(np * B);
+    float4 *S = ar.take<float4>(np * B);
+    float2 *A = ar.take<float2>(np * B);
     float *A12 = ar.take<float>(np * B), *wt = ar.take<float>(np * B);
     float2 *dW = ar.take<float2>(np * B), *dW2 = ar.take<float2>(np * B);
     if (!ar.ok()) { tf_set_error("tf_varref: workspace too small"); return TF_ENOMEM; }
@@ -541,12 +618,12 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
     const float2 *Wf = (const float2 *)flow;
     const int iH = (int)H, iW = (int)W;
     {
-        TfProfScope ps(TFK_VR_PREPARE, (1.0 + 1.0 + 8.0 + 32.0) * nb, s);
+        TfProfScope ps(TFK_VR_PREPARE, (1.0 + 1.0 + 8.0 + 8.0) * nb, s);
         hipLaunchKernelGGL(k_vr_prepare, dim3((iW + VR_TW - 1) / VR_TW, (iH + VR_TH - 1) / VR_TH, Z), dim3(256), 0, s,
-                           I0, I1, Wf, iH, iW, D1, D2, bs);
+                           I0, I1, Wf, iH, iW, A, bs);
     }
     TF_CHECK_LAUNCH();
-    const dim3 g1((iW + 63) / 64, (iH + 3) / 4, Z), g2(((iW + 1) / 2 + 63) / 64, (iH + 3) / 4);
+    const dim3 g1((iW + VRS_TW - 1) / VRS_TW, (iH + VRS_TH - 1) / VRS_TH, Z), g2(((iW + 1) / 2 + 63) / 64, (iH + 3) / 4);
     if (tiled) {
         static TfDeviceOnce once;                  // function attributes are per device
         TfDeviceOnce::Guard guard(once);
@@ -562,12 +639,12 @@ static int vr_run(const uint8_t *I0, const uint8_t *I1, int64_t B, int64_t img_s
     bool flow_done = false;
     for (int it = 0; it < params->fixed_point_iterations; it++) {
         {
-            // algorithmic bytes: D1 + D2 32, W 8, dW 8 read; S 16, A12 4, weight 4 written (no dW in the first iteration)
-            TfProfScope ps(TFK_VR_SYSTEM, (32.0 + 8.0 + (dW_cur ? 8.0 : 0.0) + 16.0 + 4.0 + 4.0) * nb, s);
+            // algorithmic bytes: A 8, W 8, dW 8 read; S 16, A12 4, weight 4 written (no dW in the first iteration)
+            TfProfScope ps(TFK_VR_SYSTEM, (8.0 + 8.0 + (dW_cur ? 8.0 : 0.0) + 16.0 + 4.0 + 4.0) * nb, s);
             if (fast)
-                hipLaunchKernelGGL(k_vr_system<true>, g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf, dW_cur, iH, iW, P, S, A12, wt, bs);
+                hipLaunchKernelGGL(k_vr_system<true>, g1, dim3(256), 0, s, (const float2 *)A, Wf, dW_cur, iH, iW, P, S, A12, wt, bs);
             else
-                hipLaunchKernelGGL(k_vr_system<false>, g1, dim3(256), 0, s, (const float4 *)D1, (const float4 *)D2, Wf, dW_cur, iH, iW, P, S, A12, wt, bs);
+                hipLaunchKernelGGL(k_vr_system<false>, g1, dim3(256), 0, s, (const float2 *)A, Wf, dW_cur, iH, iW, P, S, A12, wt, bs);
         }
         TF_CHECK_LAUNCH();
         if (tile_path) {

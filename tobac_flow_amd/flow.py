@@ -347,7 +347,7 @@ class VariationalRefinement:
         cus = t.cuda.get_device_properties(i0.device).multi_processor_count
         group = int(max(1, min(B, -(-rounds * cus // tiles))))
         # ... but only where ONE image does not fill the chip for several rounds by itself (fewer tiles than 4 x the CUs) and within
-        # 6.5 GB of scratch (72 B per pixel and image).  At 5424^2 an image is 8.9 rounds; three per launch were measured 3 %
+        # 6.5 GB of scratch (48 B per pixel and image).  At 5424^2 an image is 8.9 rounds; three per launch were measured 3 %
         # slower in bench.py's timed region (vr_sor 925 -> 952 ms per step: longer launches interleave worse with the floods' kernels)
         if tiles >= 4 * cus and rounds > 0:
             # ... unless its last round is poorly filled: the smallest group of up to four images that wastes < 3 % of its rounds
