@@ -721,6 +721,15 @@ int tf_slice_labels(const int32_t *labels, int64_t T, int64_t hw, int32_t *out, 
  *   sqrt of the smallest d2[k][p] over k = max(t - time_margin, 0) .. min(t + time_margin, T - 1), +inf where all of them
  *   are INT32_MAX; src[t][p] (int64, may be NULL; needs nearest) = k * hw + nearest[k][p] for the EARLIEST k that holds the
  *   minimum (np.nanargmin), -1 where there is none.  The double square root is correctly rounded (= np.sqrt).
+ * tf_edt_time_envelope (version 105): scipy.ndimage.distance_transform_edt with sampling = (sampling_t, 1, 1) of the whole
+ *   (T, H, W) volume (validation.py:39-49 get_marker_distance_ellipse) from the same two arrays: the lower envelope along t
+ *   of (sampling_t * dt)^2 + d2[k][p].  In float64, a = fl((k - t) * sampling_t), A = fl(a * a), key_k = fl(A + d2[k][p]);
+ *   the winner is the k of the smallest key, of equal keys the one with the smaller |k - t|, then the earlier frame.
+ *   dist[t][p] (double) = sqrt(fl(fl(A + dy * dy) + dx * dx)) with (dy, dx) from nearest[k][p]: SciPy's own expression for
+ *   that feature, so the value equals SciPy's wherever the nearest feature is unique; +inf where no frame has a feature.
+ *   src[t][p] (int64, may be NULL; needs nearest) = k * H * W + nearest[k][p], -1 where there is none.  nearest == NULL
+ *   (then src must be NULL): dist = sqrt(key), which is not SciPy's summation order.  sampling_t must be finite and > 0,
+ *   the shape one that tf_edt2d_frames accepts.  No workspace, no atomics; T * H * W may exceed 2^31.
  * tf_label_nanmin: np.nanmin of a field over every label (label_utils.py:58-140 apply_func_to_labels with func=np.nanmin,
  *   validation.py:13-21, 144-152).  labels: int32 (n,); field: TF_U8, TF_F32 or TF_F64 (n,); ids: n_ids int64 label ids on
  *   the device.  out_min[k] (double) = the minimum over the voxels of ids[k] that are not NaN, NaN where it has none;
@@ -734,6 +743,8 @@ int tf_edt2d_frames(const void *vol, int dtype, int64_t T, int64_t H, int64_t W,
                     size_t ws_bytes, void *stream);
 int tf_edt_cylinder(const int32_t *d2, const int32_t *nearest, int64_t T, int64_t hw, int64_t time_margin, double *dist,
                     int64_t *src, void *stream);
+int tf_edt_time_envelope(const int32_t *d2, const int32_t *nearest, int64_t T, int64_t H, int64_t W, double sampling_t,
+                         double *dist, int64_t *src, void *stream);
 size_t tf_label_nanmin_workspace_bytes(int64_t n_labels);
 int tf_label_nanmin(const int32_t *labels, const void *field, int dtype, int64_t n, int64_t n_labels, const int64_t *ids,
                     int64_t n_ids, double *out_min, int64_t *out_count, void *ws, size_t ws_bytes, void *stream);

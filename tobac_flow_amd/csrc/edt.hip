@@ -4,6 +4,8 @@
 //                    int32 squared distances and the raveled index of a nearest feature: a column pass and a row pass
 //   tf_edt_cylinder  validation.py:52-104 get_marker_distance_cylinder: the minimum over +- time_margin frames, the
 //                    earliest frame on ties, its square root as a double and the source voxel
+//   tf_edt_time_envelope  validation.py:39-49 get_marker_distance_ellipse: SciPy's 3-D transform with sampling (s, 1, 1) as the
+//                    lower envelope along t of (s dt)^2 + d2, evaluated in SciPy's summation order (edt_kernels.h)
 //   tf_label_nanmin  np.nanmin applied to every label by tobac_flow/utils/label_utils.py:58-140 apply_func_to_labels
 //                    (validation.py:13-21, 144-152): one read of labels and field, a finish per requested id
 //
@@ -41,6 +43,13 @@ k_edt_cylinder(int64_t T, int64_t hw, int64_t tm, const int32_t *__restrict__ d2
                double *__restrict__ dist, int64_t *__restrict__ src)
 {
     edt_cyl_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, T, hw, tm, d2, nearest, dist, src);
+}
+
+__global__ void __launch_bounds__(256)
+k_edt_envelope(int64_t T, int64_t hw, int32_t W, double s, const int32_t *__restrict__ d2, const int32_t *__restrict__ nearest,
+               double *__restrict__ dist, int64_t *__restrict__ src)
+{
+    edt_env_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, T, hw, W, s, d2, nearest, dist, src);
 }
 
 __global__ void __launch_bounds__(256)
@@ -136,6 +145,20 @@ extern "C" int tf_edt_cylinder(const int32_t *d2, const int32_t *nearest, int64_
     TF_REQUIRE(blocks <= 0x7fffffffll, "tf_edt_cylinder: volume too large for one launch");
     hipLaunchKernelGGL(k_edt_cylinder, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T, hw,
                        time_margin < T ? time_margin : T, d2, nearest, dist, src);
+    TF_CHECK_LAUNCH();
+    return TF_OK;
+}
+
+// ---- tf_edt_time_envelope ----------------------------------------------------------------------------------------------
+extern "C" int tf_edt_time_envelope(const int32_t *d2, const int32_t *nearest, int64_t T, int64_t H, int64_t W, double sampling_t,
+                                    double *dist, int64_t *src, void *stream)
+{
+    TF_REQUIRE(d2 && dist && (!src || nearest), "tf_edt_time_envelope: bad arguments (src needs nearest)");
+    TF_REQUIRE(edt_shape_ok(T, H, W), "tf_edt_time_envelope: bad shape ((H - 1)^2 + (W - 1)^2 < 2^31 is required)");
+    TF_REQUIRE(sampling_t > 0 && sampling_t <= 1.7976931348623157e308, "tf_edt_time_envelope: sampling_t must be finite and > 0");
+    const int64_t hw = H * W, blocks = (hw + 255) / 256;        // one lane per pixel, looping over t; hw < 2^31 by edt_shape_ok
+    hipLaunchKernelGGL(k_edt_envelope, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T, hw, (int32_t)W, sampling_t, d2,
+                       nearest, dist, src);
     TF_CHECK_LAUNCH();
     return TF_OK;
 }

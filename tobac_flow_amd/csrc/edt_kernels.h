@@ -1,6 +1,6 @@
-// Kernel bodies of edt.hip (tf_edt2d_frames, tf_edt_cylinder, tf_label_nanmin).  Kept apart from the entry points so that
-// the same text compiles for the host: tools/edt_host_check.cpp supplies the vector types and the atomics and runs the
-// bodies lane after lane under AddressSanitizer.  Nothing here touches the HIP runtime.
+// Kernel bodies of edt.hip (tf_edt2d_frames, tf_edt_cylinder, tf_edt_time_envelope, tf_label_nanmin).  Kept apart from the
+// entry points so that the same text compiles for the host: tools/edt_host_check.cpp supplies the vector types and the
+// atomics and runs the bodies lane after lane under AddressSanitizer.  Nothing here touches the HIP runtime.
 #pragma once
 #include <stdint.h>
 #include "wstats_kernels.h"                                       // ws_key, ws_load4 and the 4096-voxel work layout
@@ -106,6 +106,60 @@ __device__ inline void edt_cyl_body(int64_t i, int64_t T, int64_t hw, int64_t tm
     }
     dist[i] = bt < 0 ? (double)__builtin_inf() : sqrt((double)best);
     if (src) src[i] = bt < 0 ? -1 : bt * hw + (int64_t)nearest[bt * hw + p];
+}
+
+// ---- tf_edt_time_envelope ----------------------------------------------------------------------------------------------
+// scipy.ndimage.distance_transform_edt(..., sampling=(s, 1, 1)) of a (T, H, W) volume from the per-frame transform: the
+// squared distance (s dt)^2 + dy^2 + dx^2 is smallest, for a fixed frame, at that frame's nearest in-plane feature, so the
+// 3-D transform is the lower envelope along t of (s dt)^2 + d2[k].  In float64, for output voxel (t, y, x) and frame k:
+//   a = fl((double)(k - t) * s), A = fl(a * a), key_k = fl(A + (double)d2[k][p])
+// The winner is the k of the smallest key; of equal keys the one with the smaller |k - t|, then the earlier frame.  The
+// distance is SciPy's own expression for the winner's feature (the axis differences times their sampling, squared, summed in
+// axis order, one square root): sqrt(fl(fl(A + dy * dy) + dx * dx)).  Without `nearest` there is no (dy, dx) and the
+// distance is sqrt(key), which is NOT SciPy's summation order.  No product or sum here may be contracted into an FMA (the
+// library is built with -ffp-contract=off).
+// One lane per pixel p, looping over t: per t it looks at dt = 0, -1, +1, -2, +2, .. and stops at the first |dt| whose A is
+// no smaller than the best key (key_k >= A_k, and A does not decrease with |dt|) or that leaves the volume on both sides.
+// A wave re-reads its own T x 256 B of d2 from cache; `nearest` is read at the winners only.  hw = H * W < 2^31.
+__device__ inline void edt_env_body(int64_t p, int64_t T, int64_t hw, int32_t W, double s, const int32_t *__restrict__ d2,
+                                    const int32_t *__restrict__ nearest, double *__restrict__ dist, int64_t *__restrict__ src)
+{
+    if (p >= hw) return;
+    const int32_t y = (int32_t)(p / W), x = (int32_t)(p - (int64_t)y * W);
+    const int32_t *col = d2 + p;
+    for (int64_t t = 0; t < T; t++) {
+        double best = (double)__builtin_inf();
+        int64_t bk = -1;
+        const int32_t v0 = col[t * hw];
+        if (v0 != EDT_NONE) { best = (double)v0; bk = t; }        // A = 0: the key is d2 itself
+        const int64_t reach = t > T - 1 - t ? t : T - 1 - t;
+        for (int64_t d = 1; d <= reach; d++) {
+            const double a = (double)d * s, A = a * a;            // (-d * s)^2 is the same number
+            if (bk >= 0 && A >= best) break;
+            const int64_t lo = t - d, hi = t + d;
+            const int32_t vl = lo >= 0 ? col[lo * hw] : EDT_NONE, vh = hi < T ? col[hi * hw] : EDT_NONE;
+            if (vl != EDT_NONE) {
+                const double key = A + (double)vl;
+                if (bk < 0 || key < best) { best = key; bk = lo; }    // bk < 0: a key that overflowed to inf still is a feature
+            }
+            if (vh != EDT_NONE) {
+                const double key = A + (double)vh;
+                if (bk < 0 || key < best) { best = key; bk = hi; }
+            }
+        }
+        const int64_t i = t * hw + p;
+        if (bk < 0) {
+            dist[i] = (double)__builtin_inf();
+            if (src) src[i] = -1;
+        } else if (!nearest) {
+            dist[i] = sqrt(best);
+        } else {
+            const int32_t n = nearest[bk * hw + p], fy = n / W, fx = n - fy * W;
+            const double a = (double)(bk - t) * s, dy = (double)(fy - y), dx = (double)(fx - x);
+            dist[i] = sqrt((a * a + dy * dy) + dx * dx);
+            if (src) src[i] = bk * hw + (int64_t)n;
+        }
+    }
 }
 
 // ---- tf_label_nanmin ---------------------------------------------------------------------------------------------------

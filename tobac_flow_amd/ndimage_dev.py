@@ -380,6 +380,86 @@ def distance_transform_edt_frames(x, return_distances=True, return_indices=False
     return out[0] if len(out) == 1 else tuple(out)
 
 
+def _sampling_t(sampling_t):
+    s = float(sampling_t)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"the sampling along t must be finite and > 0, got {sampling_t!r}")
+    return s
+
+
+def edt_time_envelope(d2, nearest, sampling_t):
+    """tf_edt_time_envelope: (float64 distances, int64 source voxels or None) of the 3-D transform with sampling
+    (sampling_t, 1, 1) from the (T, H, W) outputs of edt_squared_frames -- per voxel the frame k with the smallest
+    fl(fl((k - t) sampling_t)^2 + d2[k]) (of equal ones the nearer frame, then the earlier), the distance to that frame's
+    nearest feature in SciPy's summation order, inf where no frame has a feature, and the raveled index of the feature in
+    the volume (-1 where none).  With nearest=None the distance is the square root of that smallest sum itself, which is
+    not SciPy's order of summation, and there are no source voxels."""
+    t = _lib.torch()
+    s = _sampling_t(sampling_t)
+    if d2.dim() != 3 or 0 in d2.shape or d2.dtype != t.int32:
+        raise ValueError("d2 must be a non-empty (T, H, W) int32 tensor")
+    if nearest is not None and (nearest.shape != d2.shape or nearest.dtype != t.int32):
+        raise ValueError("nearest must be an int32 tensor of d2's shape")
+    d2 = d2.contiguous()
+    nearest = nearest.contiguous() if nearest is not None else None
+    T, H, W = d2.shape
+    dist = t.empty((T, H, W), dtype=t.float64, device=d2.device)
+    src = t.empty((T, H, W), dtype=t.int64, device=d2.device) if nearest is not None else None
+    _lib.check(_lib.lib().tf_edt_time_envelope(_lib.ptr(d2), _lib.ptr(nearest), T, H, W, s, _lib.ptr(dist), _lib.ptr(src),
+                                               _lib.stream_ptr()), "tf_edt_time_envelope")
+    return dist, src
+
+
+def _edt_sampling(sampling, ndim):
+    """the sampling along t of distance_transform_edt; every in-plane sampling must be 1"""
+    if sampling is None:
+        return 1.0
+    s = np.asarray(sampling, np.float64)
+    if s.ndim == 0:
+        s = np.full(ndim, float(s))
+    if s.shape != (ndim,):
+        raise ValueError(f"sampling must be a scalar or one value per axis ({ndim}), got {sampling!r}")
+    if not np.all(s[-2:] == 1):
+        raise ValueError("distance_transform_edt: only the leading (time) axis of a (T, H, W) input may have a sampling "
+                         f"other than 1 -- the in-plane transform is the integer one -- got {sampling!r}")
+    return _sampling_t(s[0]) if ndim == 3 else 1.0
+
+
+def distance_transform_edt(x, sampling=None, return_distances=True, return_indices=False):
+    """scipy.ndimage.distance_transform_edt(x, sampling=sampling, return_distances=..., return_indices=...) for a (H, W)
+    or (T, H, W) device tensor: the float64 distance of every voxel to the nearest voxel where x == 0 and the (ndim, ...)
+    int32 indices of that voxel.  `sampling` is None, 1, or for a volume (s_t, 1, 1) with s_t finite and > 0: the in-plane
+    transform is the exact integer one (edt_squared_frames), the time axis is its lower envelope (edt_time_envelope), and
+    the distance is SciPy's expression for the reported voxel.  It equals SciPy's bit for bit wherever the nearest zero
+    voxel is unique, and everywhere for an integer s_t; of several equally near ones this function reports the nearer
+    frame, then the earlier one, and within a frame the one edt_squared_frames reports, SciPy the one its sweep meets.
+    An input without any zero voxel gives inf and -1 (SciPy's result for it is meaningless).  Returns what SciPy returns:
+    the distances, the indices, or the tuple of both."""
+    if not (return_distances or return_indices):
+        raise RuntimeError("at least one of return_distances/return_indices must be True")
+    ndim = len(x.shape)
+    if ndim not in (2, 3) or 0 in x.shape:
+        raise ValueError(f"a non-empty (H, W) or (T, H, W) tensor is required, got shape {tuple(x.shape)}")
+    s = _edt_sampling(sampling, ndim)
+    if ndim == 2:
+        out = distance_transform_edt_frames(x[None], return_distances, return_indices)
+        if return_distances and return_indices:
+            return out[0][0], out[1][:, 0]
+        return out[:, 0] if return_indices else out[0]
+    t = _lib.torch()
+    d2, nearest = edt_squared_frames(x == 0, return_nearest=True)       # the distance is evaluated at the feature: SciPy's order
+    dist, src = edt_time_envelope(d2, nearest, s)
+    if not return_indices:
+        return dist
+    H, W = x.shape[1:]
+    frame = t.div(src, H * W, rounding_mode="floor")
+    rest = src - frame * (H * W)
+    row = t.div(rest, W, rounding_mode="floor")
+    indices = t.stack([frame, row, rest - row * W]).to(t.int32)
+    indices[:, src < 0] = -1
+    return (dist, indices) if return_distances else indices
+
+
 def label_nanmin(labels, field, ids):
     """tf_label_nanmin: (float64 minima, int64 counts) for the label ids `ids` (a 1-D int64 numpy array, every id >= 1):
     np.nanmin of `field` (bool, uint8, float32 or float64 device tensor; other types are widened to float64) over the

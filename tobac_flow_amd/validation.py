@@ -16,7 +16,9 @@ tensors in give device tensors out.  Divergences: per-label results are always o
 single id to a scalar), an id < 1 in `coord` / `index` is a ValueError (the reference evaluates the background as a
 region), and a negative `time_margin` is a ValueError (the reference fails inside np.nanargmin).  The validate_*
 wrappers of the reference only store what validate_markers returns in an xarray Dataset and are not taken
-(there is no xarray here); get_marker_distance_ellipse is not taken either."""
+(there is no xarray here).  get_marker_distance_ellipse keeps refusing; the anisotropic 3-D transform it stands for is
+get_marker_distance_ellipse_dev: exact in the plane, SciPy's own float64 expression along t, equal to the reference
+wherever the nearest marker is unique."""
 import numpy as np
 
 from tobac_flow_amd.postprocess import _check_index, _is_tensor, _lib, _shape
@@ -94,6 +96,32 @@ def get_marker_distance_ellipse(markers, time_margin, margin):
     of this module does not extend to it."""
     raise NotImplementedError("get_marker_distance_ellipse: the anisotropic 3-D transform is not integer-exact and the "
                               "validation script never calls it; use get_marker_distance_cylinder")
+
+
+def get_marker_distance_ellipse_dev(markers, time_margin, margin):
+    """The reference's get_marker_distance_ellipse (validation.py:39-49) on the GPU: for every voxel of the (T, H, W) volume
+    `markers` the distance to the nearest marker (voxel != 0) where one frame counts as `margin / time_margin` pixels --
+    scipy.ndimage.distance_transform_edt(markers == 0, sampling=(margin / time_margin, 1, 1)) -- and the value of that
+    marker: `(distances, closest_marker)`, float64 and the dtype of `markers`.  The per-frame integer transform
+    (tf_edt2d_frames) is followed by its lower envelope along t (tf_edt_time_envelope); the distance is SciPy's own
+    expression for the reported marker, so it equals the reference's bit for bit wherever the nearest marker is unique
+    (DESIGN.md).  Of equally near markers the one in the nearer frame is taken, then the earlier frame, and within a frame
+    the one ndimage_dev.edt_squared_frames reports.  A volume without any marker gives inf and 0 (the reference's result
+    for it is meaningless).  `margin / time_margin` is evaluated as written; a result that is not finite and > 0 is a
+    ValueError."""
+    sampling = margin / time_margin
+    if not (np.isfinite(sampling) and sampling > 0):
+        raise ValueError(f"margin / time_margin must be finite and > 0, got {sampling!r}")
+    _volume_shape(markers, "markers")
+    from tobac_flow_amd import ndimage_dev
+    lib = _lib()
+    t = lib.torch()
+    dev = lib.to_dev(markers, share=True)
+    d2, nearest = ndimage_dev.edt_squared_frames(dev, return_nearest=True)
+    dist, src = ndimage_dev.edt_time_envelope(d2, nearest, float(sampling))
+    values = dev.reshape(-1)[src.reshape(-1).clamp(min=0)].reshape(src.shape)
+    closest = t.where(src < 0, t.zeros_like(values), values)
+    return _out(dist, markers), _out(closest, markers)
 
 
 def _label_ids(labels, index):
@@ -219,4 +247,4 @@ def get_edge_filter(gridded_flash_ds, margin, time_margin):
 
 
 __all__ = ("get_min_dist_for_objects", "get_marker_distance", "get_marker_distance_ellipse", "get_marker_distance_cylinder",
-           "validate_markers", "get_edge_filter")
+           "validate_markers", "get_edge_filter", "get_marker_distance_ellipse_dev")

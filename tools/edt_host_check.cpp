@@ -7,8 +7,9 @@
 // Lanes run one after the other (all of a workgroup's loads of sq[] before its scans, as the barrier orders them), so
 // the atomics are plain read-modify-writes.  Checked: every load and store inside its buffer, the squared distances
 // against the brute-force minimum over all features of the frame, the reported feature against the documented rule
-// (smallest |x' - x|, then the left one, then the upper one), the cylinder minimum with its earliest-frame rule, and
-// the per-label minimum at every alignment and tail form.
+// (smallest |x' - x|, then the left one, then the upper one), the cylinder minimum with its earliest-frame rule, the
+// envelope along t (its pruned scan against the plain minimum over all frames, with the nearer-then-earlier frame on equal
+// keys, and the distance in SciPy's summation order) and the per-label minimum at every alignment and tail form.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -133,6 +134,31 @@ static void edt_case(const Truth &truth, int64_t T, int64_t H, int64_t W, bool w
         const size_t i = (size_t)(t * hw + p);
         CHECK(bt < 0 ? std::isinf(dist[i]) && dist[i] > 0 : dist[i] == std::sqrt((double)best));
         if (want_nearest) CHECK(src[i] == (bt < 0 ? -1 : bt * hw + nearest[(size_t)(bt * hw + p)]));
+    }
+    // the envelope along t against the plain rule: over ALL frames the smallest key, then the nearer frame, then the earlier
+    if (tm) return;                                                // once per volume and element type
+    for (double s : {10.0 / 3.0, 1.0, 3.0, 0.3, 1e9, 1e200}) {
+        std::fill(dist.begin(), dist.end(), -1.0);
+        std::fill(src.begin(), src.end(), (int64_t)-7);
+        for (int64_t p = 0; p < (hw + 255) / 256 * 256; p++)
+            edt_env_body(p, T, hw, (int32_t)W, s, d2.data(), want_nearest ? nearest.data() : nullptr, dist.data(), want_nearest ? src.data() : nullptr);
+        for (int64_t t = 0; t < T; t++) for (int64_t p = 0; p < hw; p++) {
+            double best = INFINITY; int64_t bk = -1;
+            for (int64_t k = 0; k < T; k++) {
+                const int32_t v = d2[(size_t)(k * hw + p)];
+                if (v == EDT_NONE) continue;
+                const double a = (double)(k - t) * s, key = a * a + (double)v;
+                const bool nearer = std::llabs(k - t) < std::llabs(bk - t) || (std::llabs(k - t) == std::llabs(bk - t) && k < bk);
+                if (bk < 0 || key < best || (key == best && nearer)) { best = key; bk = k; }
+            }
+            const size_t i = (size_t)(t * hw + p);
+            if (bk < 0) { CHECK(std::isinf(dist[i]) && dist[i] > 0); if (want_nearest) CHECK(src[i] == -1); continue; }
+            if (!want_nearest) { CHECK(dist[i] == std::sqrt(best)); continue; }
+            const int64_t n = nearest[(size_t)(bk * hw + p)];
+            const double a = (double)(bk - t) * s, dy = (double)(n / W - p / W), dx = (double)(n % W - p % W);
+            CHECK(src[i] == bk * hw + n);
+            CHECK(dist[i] == std::sqrt((a * a + dy * dy) + dx * dx));
+        }
     }
 }
 

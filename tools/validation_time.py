@@ -4,9 +4,13 @@ tf_edt2d_frames, tf_edt_cylinder and tf_label_nanmin on their own (the last on t
 labels, against the bytes it really reads), and three frames that take the transform apart: every voxel a feature (the
 row scan stops at once: what is left is the column pass and the row pass's loads and stores), ONE feature in a corner (the
 worst case of the pruned row scan, every pixel walks its row), and no feature (its rows are filled, not scanned).  Next to them scipy.ndimage.distance_transform_edt, the call the device path replaces, on
-ONE frame of the same labels and on the single-feature frame, on this machine's CPU.
+ONE frame of the same labels and on the single-feature frame, on this machine's CPU.  The 3-D transform with a time
+sampling: get_marker_distance_ellipse_dev, tf_edt_time_envelope alone (with and without the nearest features), beside them
+tf_edt_cylinder with sources, and SciPy's 3-D call with sampling (margin / time_margin, 1, 1) on as many frames of the
+labels as it finishes in about SCIPY_SECONDS (two frames first, then the count their time predicts; 0 skips it).
 Wall time around each call with a device synchronise, HIP events around the kernels; median of RUNS after WARM warm-ups.
-Usage: python tools/validation_time.py [N] [T] (development aid; the figures are kept in profiles/validation_edt.txt)"""
+Usage: python tools/validation_time.py [N] [T] [SCIPY_SECONDS] (development aid; the figures are kept in
+profiles/validation_edt.txt and profiles/validation_ellipse.txt)"""
 import statistics
 import sys
 import time
@@ -21,6 +25,7 @@ from tobac_flow_amd import _lib, ndimage_dev as nd, validation
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 5424
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+SCIPY_SECONDS = float(sys.argv[3]) if len(sys.argv) > 3 else 60.0
 MARGIN, TIME_MARGIN = 10, 3                                       # the defaults of scripts/dcc_validation.py
 WARM, RUNS = 1, 3
 
@@ -75,6 +80,7 @@ def main():
     report("get_marker_distance_cylinder(labels)", lambda: validation.get_marker_distance_cylinder(labels, TIME_MARGIN))
     report("get_marker_distance_cylinder(labels, get_closest=True)",
            lambda: validation.get_marker_distance_cylinder(labels, TIME_MARGIN, get_closest=True))
+    report("get_marker_distance_ellipse_dev(labels)", lambda: validation.get_marker_distance_ellipse_dev(labels, TIME_MARGIN, MARGIN))
     report("get_marker_distance_cylinder(flash grid)", lambda: validation.get_marker_distance_cylinder(grid, TIME_MARGIN))
     glm_distance = validation.get_marker_distance_cylinder(grid, TIME_MARGIN)
     edge = torch.zeros((T, N, N), dtype=torch.bool, device=dev)      # get_edge_filter's result without gaps or missing data
@@ -93,6 +99,17 @@ def main():
     report("tf_edt2d_frames (labels, d2 and nearest)", lambda: nd.edt_squared_frames(labels, True), events)
     d2 = nd.edt_squared_frames(labels)[0]
     report("tf_edt_cylinder (distances only)", lambda: nd.edt_cylinder(d2, None, TIME_MARGIN), events)
+    nearest = nd.edt_squared_frames(labels, True)[1]
+    report("tf_edt_cylinder (distances and sources)", lambda: nd.edt_cylinder(d2, nearest, TIME_MARGIN), events)
+    env = report(f"tf_edt_time_envelope alone (sampling {MARGIN}/{TIME_MARGIN}, distances and sources)",
+                 lambda: nd.edt_time_envelope(d2, nearest, MARGIN / TIME_MARGIN), events)
+    moved = d2.numel() * (4 + 4 + 8 + 8)                           # d2 once, nearest at the winners, dist and src once
+    print(f"  = {moved / 1e6 / env:.0f} GB/s of the {moved / 1e9:.2f} GB it has to move (d2 and nearest read once, dist and src written)", flush=True)
+    report(f"tf_edt_time_envelope alone (sampling {MARGIN}/{TIME_MARGIN}, distances only, no nearest)",
+           lambda: nd.edt_time_envelope(d2, None, MARGIN / TIME_MARGIN), events)
+    report("tf_edt_time_envelope alone (sampling 1e9: no frame looks beyond itself)", lambda: nd.edt_time_envelope(d2, nearest, 1e9), events)
+    report("tf_edt_time_envelope alone (sampling 0.3: every scan runs to the ends of t)", lambda: nd.edt_time_envelope(d2, nearest, 0.3), events)
+    del nearest
     # tf_label_nanmin alone (its init, pass and finish kernels; operands, outputs and scratch allocated beforehand).  It
     # reads 4 B of labels per voxel and the field only under the lanes that hold a label among their four voxels
     L = _lib.lib()
@@ -131,6 +148,20 @@ def main():
     t2 = time.perf_counter()
     print(f"scipy.ndimage.distance_transform_edt with indices on this machine's CPU, ONE {N}^2 frame (one run): labels "
           f"{(t1 - t0) * 1e3:.0f} ms, single feature {(t2 - t1) * 1e3:.0f} ms (device, single feature: {worst:.1f} ms)", flush=True)
+    if SCIPY_SECONDS > 0:
+        sampling = (MARGIN / TIME_MARGIN, 1, 1)
+        host = labels.cpu().numpy() == 0
+        frames = min(2, T)
+        while True:
+            t0 = time.perf_counter()
+            ndi.distance_transform_edt(host[:frames], return_indices=True, sampling=sampling)
+            seconds = time.perf_counter() - t0
+            print(f"scipy.ndimage.distance_transform_edt, 3-D with indices, sampling ({MARGIN}/{TIME_MARGIN}, 1, 1), on this machine's CPU, "
+                  f"{frames} x {N}^2 frames (one run): {seconds:.1f} s = {seconds / frames:.2f} s per frame", flush=True)
+            more = min(T, int(frames * SCIPY_SECONDS / seconds))
+            if more <= frames or frames > 2:
+                break
+            frames = more
 
 
 if __name__ == "__main__":
