@@ -749,6 +749,24 @@ size_t tf_label_nanmin_workspace_bytes(int64_t n_labels);
 int tf_label_nanmin(const int32_t *labels, const void *field, int dtype, int64_t n, int64_t n_labels, const int64_t *ids,
                     int64_t n_ids, double *out_min, int64_t *out_count, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- subsegment_labels: tobac_flow/label.py:13-80 (version 106) -----------------------------------------------------------
+ * The per-voxel passes between tf_label / tf_edt2d_frames / tf_label_sizes and the per-frame tf_watershed of the recipe
+ * (tobac_flow_amd/label.py subsegment_labels).
+ * tf_subseg_prepare: label.py:52-56.  labels: int32 (n,) per-step labels, 0 = background; d2: int32 (n,) squared in-plane
+ *   distance to the nearest background voxel (tf_edt2d_frames of labels == 0); counts: int64[n_labels + 1] on the device
+ *   (tf_label_sizes).  dist_mask[i] (double) = sqrt(d2[i]) / sqrt(counts[labels[i]] / pi): two correctly rounded square
+ *   roots and one division, nothing fused and no reciprocal, so the value equals numpy's bit for bit.  shrunk[i] (uint8)
+ *   = dist_mask[i] > shrink_factor.  A label outside [0, n_labels] is written as background (0 and 0).  One pass, 64-bit
+ *   indexed, four voxels per lane where the arrays are 16-byte aligned.
+ * tf_subseg_rank: the flood key of one frame.  values: double (n,); sorted_keys: the n_keys DISTINCT values of `values`,
+ *   ascending, on the device.  rank[i] (float) = n_keys - 1 - (index of values[i] in sorted_keys) = the rank of
+ *   -values[i] among the frame's distinct -values: a strictly order-preserving map of the float64 key the reference
+ *   floods, exact in float32.  TF_EINVAL when n_keys > 2^24 (nothing is launched).  Binary search, 64-bit indexed; a value
+ *   that is not a key gets the rank of the first key not below it. */
+int tf_subseg_prepare(const int32_t *labels, const int32_t *d2, const int64_t *counts, int64_t n_labels, int64_t n,
+                      double shrink_factor, double *dist_mask, uint8_t *shrunk, void *stream);
+int tf_subseg_rank(const double *values, int64_t n, const double *sorted_keys, int64_t n_keys, float *rank, void *stream);
+
 /* ---- measurement aid (bench.py's roofline figure) ---------------------------------------------
  * tf_profile_enable(1): every kernel launch of the library is bracketed by HIP events on its own
  * stream and tagged with its ALGORITHMIC byte count.  tf_profile_collect() synchronises

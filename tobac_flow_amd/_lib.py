@@ -148,6 +148,8 @@ _PROTOS = {
     "tf_edt_time_envelope": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P]),
     "tf_label_nanmin_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
     "tf_label_nanmin": (_c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_subseg_prepare": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P]),
+    "tf_subseg_rank": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P]),
     "tf_slice_labels": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_pair_counts": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_sizes": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P]),

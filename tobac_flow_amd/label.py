@@ -8,8 +8,25 @@ run-length / sort / reduce-by-key pass over the volume on the GPU; the small lab
 reference's own order inside the library (labels ascending, each unvisited label opens a group and absorbs, breadth
 first, every not-yet-visited label it overlaps, forward neighbours before backward ones; the relation is DIRECTED, so
 first come, first served).
-`subsegment_labels` (label.py:13-80, needs scikit-image) is outside the hot path: production passes
-subsegment_shrink=0.
+
+`subsegment_labels` (label.py:13-80; subsegment_shrink != 0) splits every per-step region by a distance-transform
+watershed.  The reference composes it from SciPy and scikit-image; here it is a chain of device operators:
+flat_label (tf_label), the exact integer distance transform of every frame (tf_edt2d_frames), the pixel counts
+(tf_label_sizes), tf_subseg_prepare (dist_mask in float64, bit for bit numpy's, and the shrunk markers),
+ndimage_dev.peak_local_max_2d per frame (candidates on the device, the shared host `select_peaks` for the selection),
+flat_label of the markers, tf_subseg_rank and one tf_watershed per frame.  Two facts fix that shape.  scikit-image pushes
+every marker of a frame with age 0, so the pop order of equal-valued markers depends on the whole content of THAT frame's
+heap: the flood runs frame by frame, in the reference's order (on_ambiguous="reference").  And the flood's key has to keep
+the order of the float64 -dist_mask: rounded to float32, values of different regions meet and the heap's arrangement
+changes with them; the flood only compares keys, so the per-frame rank of -dist_mask, stored as float32, is exact.  The
+reference's -1 background markers never enter scikit-image's flood (its _validate_inputs multiplies the markers by the
+mask); they are 0 here.
+Contract: where no peak-selection tie exists the labels equal the reference's bit for bit.  A peak-selection tie is two
+equal-valued peak candidates closer than peak_min_distance (Chebyshev) that do not both lie inside one shrunk marker:
+scikit-image orders candidates with numpy's non-stable argsort, so which of the two becomes a peak changes with the numpy
+version; the result is then a valid greedy selection (tests/test_host_logic.py documents the same tie for select_peaks).
+Deviations: a frame without any background voxel raises ValueError (the reference's answer there rests on the float64
+rounding of 1e18 + d^2 under its time sampling of 1e9), and so does a frame with more than 2^24 distinct distances.
 """
 import ctypes
 import warnings
@@ -93,16 +110,85 @@ def _finish(new_dev, present_dev, dtype, on_device):
 def flow_label(flow, mask, structure=ndi.generate_binary_structure(3, 1), dtype=np.int32, overlap: float = 0.0,
                absolute_overlap: int = 0, subsegment_shrink: float = 0.0, peak_min_distance: int = 10):
     """Label 3-D connected objects in a semi-Lagrangian frame (reference: label.py:84-175)."""
-    if subsegment_shrink != 0:
-        raise NotImplementedError("subsegment_shrink != 0 (label.py:13-80, scikit-image watershed) is outside the "
-                                  "MI355X hot path; production uses subsegment_shrink=0")
     t = _lib.torch()
     on_device = isinstance(mask, t.Tensor)
     m = (_lib.to_dev(mask) != 0)
     if tuple(m.shape) != tuple(flow.shape):
         raise AssertionError("Data input must have the same shape as the Flow object")
-    new_dev = flow_label_dev(flow, m.to(t.uint8).contiguous(), structure, overlap, absolute_overlap)
+    if subsegment_shrink != 0:                               # label.py:126-131; a region without a marker stays 0 (_finish warns)
+        flat_dev = subsegment_labels_dev(m, subsegment_shrink, peak_min_distance)
+        new_dev = link_overlap_dev(flow, flat_dev, structure, overlap, absolute_overlap)
+    else:
+        new_dev = flow_label_dev(flow, m.to(t.uint8).contiguous(), structure, overlap, absolute_overlap)
     return _finish(new_dev, m, dtype, on_device)
+
+
+_INT32_MAX = 2 ** 31 - 1
+
+
+def subsegment_labels_dev(mask_dev, shrink_factor=0.1, peak_min_distance=5, stats=None):
+    """subsegment_labels on a (T, H, W) device tensor whose non-zero voxels are the regions; returns the device int32
+    subsegment labels (the recipe and its contract: the module docstring).  stats: a list that receives, per flooded frame,
+    (frame, the `stats` dictionary of its watershed_dev call)."""
+    from tobac_flow_amd import ndimage_dev as nd
+    from tobac_flow_amd.watershed import neighbour_offsets, watershed_dev
+    t = _lib.torch()
+    L = _lib.lib()
+    if mask_dev.dim() != 3 or 0 in mask_dev.shape:
+        raise ValueError(f"subsegment_labels: a non-empty (t, y, x) volume is required, got shape {tuple(mask_dev.shape)}")
+    T, H, W = (int(n) for n in mask_dev.shape)
+    labels = nd.flat_label(mask_dev != 0)                                        # label.py:49
+    inside = labels != 0
+    d2, _ = nd.edt_squared_frames(labels == 0)                                   # label.py:52, frame by frame and in integers
+    full = t.nonzero(d2[:, 0, 0] == _INT32_MAX).flatten()
+    if full.numel():
+        raise ValueError(f"subsegment_labels: frame {int(full[0])} has no background voxel: the distance to the edge of its "
+                         "region is not defined")
+    n_labels = int(labels.max())
+    counts = _label_sizes_dev(labels, n_labels)                                  # label.py:53
+    dist = _lib.empty((T, H, W), t.float64)
+    shrunk = _lib.empty((T, H, W), t.uint8)
+    _lib.check(L.tf_subseg_prepare(_lib.ptr(labels), _lib.ptr(d2), _lib.ptr(counts), n_labels, labels.numel(),
+                                   float(shrink_factor), _lib.ptr(dist), _lib.ptr(shrunk), _lib.stream_ptr()),
+               "tf_subseg_prepare")                                              # label.py:54-56
+    del d2
+    seeds = shrunk.view(t.bool)
+    for i in range(T):                                                           # label.py:59-64
+        peaks = nd.peak_local_max_2d(dist[i], min_distance=peak_min_distance, threshold_abs=1e-8)
+        if len(peaks):
+            p = t.from_numpy(np.ascontiguousarray(peaks, np.int64)).to(dist.device)
+            seeds[i][p[:, 0], p[:, 1]] = True
+    markers = nd.flat_label(seeds)                                               # label.py:66
+    markers.mul_(inside)                                                         # label.py:67, with 0 for the reference's -1
+    del seeds, shrunk
+
+    plane = ndi.generate_binary_structure(3, 1)
+    plane[0] = 0
+    plane[-1] = 0
+    nbr = neighbour_offsets(plane)                                               # (-y, -x, +x, +y): scikit-image's 2-D order
+    still = t.zeros((1, H, W, 2), dtype=t.float32, device=dist.device)
+    inside8 = inside.to(t.int8)
+    flood = (markers != 0).view(T, -1).any(1).cpu().numpy()                      # a frame without a marker stays 0
+    out = t.zeros((T, H, W), dtype=t.int32, device=dist.device)
+    for i in np.flatnonzero(flood):                                              # label.py:75-78
+        i = int(i)
+        keys = t.unique(dist[i])                                                 # the frame's distinct values, ascending
+        rank = _lib.empty((1, H, W), t.float32)
+        _lib.check(L.tf_subseg_rank(_lib.ptr(dist[i]), H * W, _lib.ptr(keys), keys.numel(), _lib.ptr(rank), _lib.stream_ptr()),
+                   "tf_subseg_rank")
+        flood_stats = {} if stats is not None else None
+        out[i] = watershed_dev(still, still, rank, markers[i:i + 1], inside8[i:i + 1], nbr, stats=flood_stats)[0]
+        if stats is not None:
+            stats.append((i, flood_stats))
+    return out
+
+
+def subsegment_labels(input_mask, shrink_factor: float = 0.1, peak_min_distance: int = 5):
+    """Split the regions of a (t, y, x) mask, time step by time step, by a watershed of their distance transform
+    (reference: label.py:13-80).  A numpy array gives a numpy int32 array, a device tensor a device int32 tensor."""
+    on_device = isinstance(input_mask, _lib.torch().Tensor)
+    out = subsegment_labels_dev(_lib.to_dev(input_mask), shrink_factor, peak_min_distance)
+    return out if on_device else _lib.to_host(out)
 
 
 def find_neighbour_labels(label, label_stack, bins, args, processed_labels, forward_labels, back_labels,
@@ -193,15 +279,19 @@ def label_sizes(labels, n_labels=None):
     """np.bincount(labels.ravel(), minlength=n_labels + 1) of a non-negative int32 volume (tf_label_sizes); ids above
     n_labels are not counted."""
     t = _lib.torch()
-    L = _lib.lib()
     lab = _lib.to_dev(labels, t.int32).contiguous()
     if n_labels is None:
         n_labels = int(lab.max()) if lab.numel() else 0
-    out = _lib.empty((int(n_labels) + 1,), t.int64)
     if lab.numel() == 0:
         return np.zeros(int(n_labels) + 1, np.int64)
-    _lib.check(L.tf_label_sizes(_lib.ptr(lab), lab.numel(), int(n_labels), _lib.ptr(out), _lib.stream_ptr()), "tf_label_sizes")
-    return _lib.to_host(out)
+    return _lib.to_host(_label_sizes_dev(lab, n_labels))
+
+
+def _label_sizes_dev(lab, n_labels):
+    """label_sizes of a non-empty contiguous int32 device volume, left on the device (int64[n_labels + 1])"""
+    out = _lib.empty((int(n_labels) + 1,), _lib.torch().int64)
+    _lib.check(_lib.lib().tf_label_sizes(_lib.ptr(lab), lab.numel(), int(n_labels), _lib.ptr(out), _lib.stream_ptr()), "tf_label_sizes")
+    return out
 
 
 def slice_labels_dev(labels):
@@ -303,6 +393,6 @@ def unique_per_frame(volume, n_labels=None):
     return uniq.cpu().numpy(), nz.cpu().numpy()
 
 
-__all__ = ("flow_label", "find_neighbour_labels", "flow_link_overlap", "flow_label_dev", "link_overlap_dev",
+__all__ = ("subsegment_labels", "subsegment_labels_dev", "flow_label", "find_neighbour_labels", "flow_link_overlap", "flow_label_dev", "link_overlap_dev",
            "pair_counts", "label_sizes", "slice_labels_dev", "make_step_labels_dev", "label_props", "unique_along_t",
            "unique_per_frame")
