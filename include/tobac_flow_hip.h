@@ -47,7 +47,7 @@ extern "C" {
 #define TF_F32 0
 #define TF_F64 1
 #define TF_I32 2
-#define TF_U8 3          /* tf_edt2d_frames, tf_label_nanmin only (bool arrays have these bytes) */
+#define TF_U8 3          /* tf_edt2d_frames, tf_label_nanmin, tf_label_filter only (bool arrays have these bytes) */
 
 /* reductions over the gathered (n_struct, H, W) stack, i.e. the `func` argument of
  * tobac_flow/convolve.py:248-348 for the callables the reference itself passes */
@@ -557,6 +557,28 @@ int tf_linearise(const float *field, int64_t n, double lower, double upper, floa
 int tf_label_extent(const int32_t *labels, const uint8_t *mask, int64_t T, int64_t H, int64_t W, int n_labels,
                     int *tmin, int *tmax, uint8_t *hit, void *stream);
 int tf_apply_lut(const int32_t *labels, int64_t n, const int32_t *lut, int n_lut, int32_t *out, void *stream);
+/* tf_label_filter (version 107): tobac_flow/analysis.py:15-201 -- what find_object_lengths, mask_labels and the
+ *   filter_labels_by_* family ask of one int32 (T, H, W) label volume, in ONE read of it: per label id 0 .. n_labels a
+ *   record of four int32 (16 B) on the device, records[id * 4 + {0, 1, 2, 3}] = { first leading index, last leading index,
+ *   hit bits, 0 }.  Bit k of the hit bits is set when some voxel of the label satisfies criteria[k] (a HOST array of
+ *   n_criteria entries, 0 .. 8):
+ *     dtype TF_U8            `data` is a byte mask of the volume's shape; satisfied where the byte is not 0 (op, threshold ignored)
+ *     dtype TF_F32 / TF_F64  `data` is a field of the volume's shape; satisfied where `field op threshold` holds, op one of
+ *                            TF_CMP_GE / GT / LE / LT.  The comparison is made in the field's own type: for TF_F32 the
+ *                            threshold is rounded to float first, as NumPy compares a float32 array with a Python float.
+ *                            A NaN in the field satisfies nothing.
+ *   Criterion operands are read only under voxels whose label lies in [1, n_labels]; ids outside are skipped, so record 0
+ *   stays empty.  The call initialises the records itself; a label that does not occur keeps { 0x7fffffff, -1, 0, 0 }, so
+ *   it is absent exactly when its last index is -1.  Shape contract as tf_label_extent (T < 65536); 64-bit indexing;
+ *   `records` 16-byte aligned.  Every value is exact (integer atomics only).  TF_EINVAL before any launch: null pointers,
+ *   n_criteria outside 0 .. 8, a criterion without data, an unknown dtype or op, a NaN threshold. */
+#define TF_CMP_GE 0
+#define TF_CMP_GT 1
+#define TF_CMP_LE 2
+#define TF_CMP_LT 3
+typedef struct { const void *data; int dtype; int op; double threshold; } tf_label_criterion;
+int tf_label_filter(const int32_t *labels, int64_t T, int64_t H, int64_t W, int64_t n_labels,
+                    const tf_label_criterion *criteria, int n_criteria, int32_t *records, void *stream);
 /* the same gather with ids <= 0 passed through (window stitch, tobac_flow/linking.py:153-161: background -1 and 0 keep
  * their value while the positive ids are renumbered) */
 int tf_apply_lut_keep_nonpositive(const int32_t *labels, int64_t n, const int32_t *lut, int n_lut, int32_t *out, void *stream);

@@ -33,6 +33,11 @@ class NormParams(ctypes.Structure):
                 ("quantiles", ctypes.c_int64), ("size", ctypes.c_int64), ("flags", ctypes.c_int)]
 
 
+class LabelCriterion(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int), ("op", ctypes.c_int), ("threshold", ctypes.c_double)]
+
+
+CMP_OPS = {">=": 0, ">": 1, "<=": 2, "<": 3}
 NORM_METHODS = {"linear": 0, "log": 1, "inverse_log": 2, "z_score": 3, "uniform": 4, "local_linear": 5}
 NORM_HAS_VMIN, NORM_HAS_VMAX, NORM_F32_SCALARS = 1, 2, 4
 FB_CHAIN_DEFAULT, FB_CHAIN_ONE_LANE, FB_CHAIN_TWO_PART = 0, 1, 2
@@ -123,6 +128,7 @@ _PROTOS = {
     "tf_grey_morph": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P]),
     "tf_linearise": (_c.c_int, [_P, _c.c_int64, _c.c_double, _c.c_double, _P, _P]),
     "tf_label_extent": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _P, _P, _P]),
+    "tf_label_filter": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.POINTER(LabelCriterion), _c.c_int, _P, _P]),
     "tf_apply_lut": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int, _P, _P]),
     "tf_apply_lut_keep_nonpositive": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int, _P, _P]),
     "tf_field_masks": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P]),

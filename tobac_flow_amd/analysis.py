@@ -1,5 +1,6 @@
-"""Label filters used by the detection recipes (host glue; mirrors the first three groups of
-/root/reference/tobac_flow/analysis.py:15-201) and the per-label statistics of analysis.py:204-245 / 293-376 as
+"""Label filters used by the detection recipes (mirrors the first three groups of
+tobac_flow/analysis.py:15-201 of the reference: NumPy arrays take the reference's own host code, a label tensor on the GPU
+takes one read of the volume by tf_label_filter and one tf_apply_lut gather) and the per-label statistics of analysis.py:204-245 / 293-376 as
 segmented reductions on the GPU (tf_label_stats), and the coverage / unique-count maps of analysis.py:245-290
 (get_label_stats: tf_unique_along_t, tf_unique_per_frame).  The xarray packaging (long_name, units attributes) is out of
 scope: xarray is not in this image."""
@@ -7,14 +8,85 @@ import numpy as np
 from scipy import ndimage as ndi
 
 
+def _is_dev(x):
+    """a torch tensor on the GPU (decided without importing torch for a NumPy caller)"""
+    return type(x).__module__.startswith("torch") and bool(getattr(x, "is_cuda", False))
+
+
+def _dev_mask(labels, mask):
+    """the mask as a device tensor of the labels' shape: a tensor as it is, a host array uploaded"""
+    from tobac_flow_amd import _lib
+    if tuple(labels.shape) != tuple(mask.shape):
+        raise AssertionError("Labels and mask parameters must have the same shape")
+    return mask.to(labels.device) if _lib.is_tensor(mask) else _lib.to_dev(np.asarray(mask))
+
+
+def _dev_measure(labels, masks=()):
+    """(lengths, hits, present) of ndimage_dev.label_filter for a label tensor and a list of masks"""
+    from tobac_flow_amd import ndimage_dev as nd
+    if labels.dim() != 3:
+        raise ValueError("a label tensor must be a (t, y, x) volume")
+    return nd.label_filter(labels, [_dev_mask(labels, m) for m in masks])
+
+
+def _dev_lengths(lengths, present):
+    if not present.all():
+        # the reference subscripts find_objects' None for an id that does not occur (analysis.py:31-33)
+        raise TypeError(f"'NoneType' object is not subscriptable (label {int(np.flatnonzero(~present)[0]) + 1} does not occur)")
+    return lengths
+
+
+def _dev_empty_comprehension(fn, *args):
+    """An all-zero volume hands SciPy's labeled_comprehension an empty label range (analysis.py:78-86), which this SciPy
+    rejects with a ValueError.  Run that very call on a one-voxel stand-in so that the behaviour is the reference's,
+    whatever it is."""
+    fn(np.zeros((1, 1, 1), np.int32), *args)
+
+
+def _dev_filter(labels, masks, min_length, *, empty, legacy=False, every_id=False):
+    """the filters' device form: one tf_label_filter, one tf_apply_lut.  `empty`: what an all-zero volume does in the host
+    form (a zero-argument callable that raises, or None: the volume comes back unchanged).  `every_id`: an id that does not
+    occur is a ValueError (filter_labels_by_mask: the reference casts labeled_comprehension's None for it to an integer)."""
+    from tobac_flow_amd import ndimage_dev as nd
+    lengths, hits, present = _dev_measure(labels, masks)
+    if lengths.size == 0:
+        if empty is not None:
+            empty()
+        return labels if legacy else labels.clone()
+    if every_id and not present.all():
+        raise ValueError(f"label {int(np.flatnonzero(~present)[0]) + 1} does not occur in the volume")
+    keep = np.ones(lengths.size, bool)
+    if min_length is not None:
+        keep &= _dev_lengths(lengths, present) >= min_length
+    keep &= hits.all(axis=1)
+    out = nd.remap_labels(labels, keep).to(labels.dtype)
+    if legacy:                                                     # the reference renumbers its argument in place
+        labels.copy_(out)
+        return labels
+    return out
+
+
+_ONE = np.zeros((1, 1, 1), bool)
+
+
 def find_object_lengths(labels, axis: int = 0):
-    """Extent of every label along `axis` (reference: analysis.py:15-35)."""
+    """Extent of every label along `axis` (reference: analysis.py:15-35).  A label tensor on the GPU is measured there
+    (axis 0; another axis downloads it) and gives a NumPy array all the same: every caller indexes host arrays with it."""
+    if _is_dev(labels):
+        if axis != 0 or labels.dim() != 3:
+            labels = labels.cpu().numpy()
+        else:
+            lengths, _, present = _dev_measure(labels)
+            return _dev_lengths(lengths, present) if lengths.size else np.array([])
     return np.array([o[axis].stop - o[axis].start for o in ndi.find_objects(labels)])
 
 
 def mask_labels(labels, mask):
-    """Boolean per label (1..max): does it overlap `mask`? (reference: analysis.py:38-63)"""
+    """Boolean per label (1..max): does it overlap `mask`? (reference: analysis.py:38-63).  NumPy array also for a label
+    tensor on the GPU."""
     assert labels.shape == mask.shape, "Labels and mask parameters must have the same shape"
+    if _is_dev(labels):
+        return _dev_measure(labels, [mask])[1][:, 0]
     hit = np.unique(labels[mask])
     out = np.zeros(labels.max() + 1, dtype=bool)
     out[hit] = True
@@ -36,26 +108,40 @@ def _any_in(labels, mask, dtype=None, default=None):
 
 
 def filter_labels_by_length(labels, min_length):
+    if _is_dev(labels):
+        return _dev_filter(labels, [], min_length, empty=None)
     return _keep(labels, _lengths_ok(labels, min_length))
 
 
 def filter_labels_by_mask(labels, mask):
+    if _is_dev(labels):
+        return _dev_filter(labels, [mask], None, every_id=True,
+                           empty=lambda: _dev_empty_comprehension(filter_labels_by_mask, _ONE))
     return _keep(labels, _any_in(labels, mask))
 
 
 def filter_labels_by_length_and_mask(labels, mask, min_length):
+    if _is_dev(labels):
+        return _dev_filter(labels, [mask], min_length,
+                           empty=lambda: _dev_empty_comprehension(filter_labels_by_length_and_mask, _ONE, min_length))
     return _keep(labels, np.logical_and(_lengths_ok(labels, min_length), _any_in(labels, mask)))
 
 
 def filter_labels_by_multimask(labels, masks):
     if type(masks) is not list:
         raise ValueError("masks input must be a list of masks to process")
+    if _is_dev(labels):
+        return _dev_filter(labels, masks, None,
+                           empty=lambda: _dev_empty_comprehension(filter_labels_by_multimask, [_ONE] * len(masks)))
     return _keep(labels, np.logical_and.reduce([_any_in(labels, m, np.bool_, 0) for m in masks]))
 
 
 def filter_labels_by_length_and_multimask(labels, masks, min_length):
     if type(masks) is not list:
         raise ValueError("masks input must be a list of masks to process")
+    if _is_dev(labels):
+        return _dev_filter(labels, masks, min_length,
+                           empty=lambda: _dev_empty_comprehension(filter_labels_by_length_and_multimask, [_ONE] * len(masks), min_length))
     return _keep(labels, np.logical_and(_lengths_ok(labels, min_length),
                                         np.logical_and.reduce([_any_in(labels, m, np.bool_, 0) for m in masks])))
 
@@ -79,16 +165,22 @@ def _legacy_filter(labels, keep_fn):
 
 
 def filter_labels_by_length_legacy(labels, min_length):
+    if _is_dev(labels):
+        return _dev_filter(labels, [], min_length, empty=None, legacy=True)
     return _legacy_filter(labels, lambda n, where: n >= min_length)
 
 
 def filter_labels_by_length_and_mask_legacy(labels, mask, min_length):
+    if _is_dev(labels):
+        return _dev_filter(labels, [mask], min_length, empty=None, legacy=True)
     return _legacy_filter(labels, lambda n, where: n >= min_length and np.any(mask.ravel()[where]))
 
 
 def filter_labels_by_length_and_multimask_legacy(labels, masks, min_length):
     if type(masks) is not list:
         raise ValueError("masks input must be a list of masks to process")
+    if _is_dev(labels):
+        return _dev_filter(labels, masks, min_length, empty=None, legacy=True)
     return _legacy_filter(labels, lambda n, where: n >= min_length and np.all([np.any(m.ravel()[where]) for m in masks]))
 
 

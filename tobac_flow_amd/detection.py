@@ -48,9 +48,9 @@ class _TimeCoord:
 
 class DeviceField:
     """A (t, y, x) field that lives in HBM together with the time coordinate the recipes read as `field.t` -- what a
-    device-resident pipeline hands detect_cores / detect_growth_markers / get_anvil_markers / detect_anvils /
-    relabel_anvils in place of the reference's xr.DataArray (a bare torch tensor has no coordinates, and `Tensor.t` is
-    the transpose).  `data`: torch tensor on the GPU; `t`: datetime64 array of length data.shape[0].  Results of the
+    device-resident pipeline hands detect_cores / detect_growth_markers / detect_growth_markers_multichannel /
+    get_anvil_markers / detect_anvils / relabel_anvils in place of the reference's xr.DataArray (a bare torch tensor has
+    no coordinates, and `Tensor.t` is the transpose).  `data`: torch tensor on the GPU; `t`: datetime64 array of length data.shape[0].  Results of the
     recipes are then device tensors.  `a - b` / `a + b` / `-a` of two fields give a field (the scripts pass `wvd - swd`)."""
 
     def __init__(self, data, t):
@@ -311,7 +311,45 @@ detect_growth = get_growth_rate      # alias for BASELINE.json's wording (SURVEY
 
 def detect_growth_markers_multichannel(flow, wvd, bt, t_sigma=1, overlap=0.5, subsegment_shrink=0, min_length=4,
                                        lower_threshold=0.25, upper_threshold=0.5):
-    """Growth markers from WVD and BT together (reference: detection.py:203-254)."""
+    """Growth markers from WVD and BT together (reference: detection.py:203-254; `t_sigma` is unused there too).  numpy /
+    DataArray in and out like the reference, DeviceField in and device tensors out; in between the two fields are uploaded
+    once and every step (semi-Lagrangian derivatives, moving averages, curvature filters, opening, flow labelling, the
+    length / multi-mask label filter) stays in HBM.  The filter reads its three criteria -- wvd_s >= upper, bt_s <= -upper,
+    wvd > -5 -- from the fields themselves in one pass over the labels (ndimage_dev.label_filter), so no boolean volume
+    is made for it.  _detect_growth_markers_multichannel_host gives identical results (tests/test_gpu_label_filter.py)."""
+    from tobac_flow_amd import ndimage_dev as nd
+    from tobac_flow_amd.analysis import _dev_lengths
+    t = _lib.torch()
+    wvd_d, bt_d = _to_device(wvd), _to_device(bt)
+
+    def smoothed(field_d, coord):
+        dt = t.from_numpy(np.asarray(get_time_diff_from_coord(coord))).to(field_d.device)[:, None, None]
+        return filtered_tdiff(flow, flow.diff(field_d, method="linear") / dt)     # float32 / float64 -> float64, as in numpy
+
+    wvd_s, bt_s = smoothed(wvd_d, wvd.t), smoothed(bt_d, bt.t)
+    markers = (((wvd_s * get_curvature_filter(wvd_d)) >= lower_threshold)
+               | ((bt_s * get_curvature_filter(bt_d, direction="positive")) <= -lower_threshold))
+    markers = flow.label(nd.binary_opening(markers, _plane_struct()), overlap=overlap, subsegment_shrink=subsegment_shrink)
+    if int(t.count_nonzero(markers).item()) > 0:
+        lengths, hits, present = nd.label_filter(markers, [(wvd_s, ">=", upper_threshold), (bt_s, "<=", -upper_threshold),
+                                                           (wvd_d, ">", -5)])
+        markers = nd.remap_labels(markers, np.logical_and(_dev_lengths(lengths, present) >= min_length, hits.all(axis=1)))
+    else:
+        warnings.warn("No regions detected in labeled array", RuntimeWarning)
+    if _is_device(wvd):                                                # device-resident pipeline: nothing visits the host
+        return wvd_s, bt_s, markers
+    wvd_s, bt_s, markers = _lib.to_host(wvd_s), _lib.to_host(bt_s), _lib.to_host(markers, remember=True)
+    if _is_dataarray(wvd):
+        import xarray as xr
+        wvd_s = xr.DataArray(wvd_s, wvd.coords, wvd.dims)
+        bt_s = xr.DataArray(bt_s, bt.coords, bt.dims)
+        markers = xr.DataArray(markers, wvd.coords, wvd.dims)
+    return wvd_s, bt_s, markers
+
+
+def _detect_growth_markers_multichannel_host(flow, wvd, bt, t_sigma=1, overlap=0.5, subsegment_shrink=0, min_length=4,
+                                             lower_threshold=0.25, upper_threshold=0.5):
+    """detect_growth_markers_multichannel with the reference's own NumPy / SciPy glue between the device operators."""
     wvd_s = filtered_tdiff(flow, _rate(flow, wvd))
     bt_s = filtered_tdiff(flow, _rate(flow, bt))
     markers = np.logical_or((wvd_s * get_curvature_filter(wvd)) >= lower_threshold,

@@ -100,6 +100,52 @@ def label_extent(labels, mask=None):
     return lengths, hit[1:].cpu().numpy().astype(bool)
 
 
+def label_filter(labels, criteria=()):
+    """(lengths int64[n], hits bool[n, K], present bool[n]) for the labels 1..n of a (t, y, x) label tensor, n its largest
+    label, in one read of the volume (tf_label_filter): the extent along the leading axis (0 for an id that does not occur),
+    whether some voxel of the label satisfies each of the K <= 8 criteria, and whether the id occurs at all.  A criterion is
+    a bool / uint8 tensor of the labels' shape (satisfied where non-zero) or a tuple (field_tensor, op, threshold) with op
+    one of ">=", ">", "<=", "<": float32 and float64 fields are compared in their own dtype, as NumPy compares an array
+    with a Python float; any other dtype is converted to float64.  n = 0 returns empty arrays without a launch."""
+    t = _lib.torch()
+    lab = labels.to(t.int32).contiguous()
+    if lab.dim() != 3:
+        raise ValueError("label_filter: the labels must be a (t, y, x) volume")
+    T, H, W = lab.shape
+    criteria = list(criteria)
+    K = len(criteria)
+    if K > 8:
+        raise ValueError("label_filter: at most 8 criteria")
+    crit = (_lib.LabelCriterion * max(K, 1))()
+    keep = []                                                       # the operands stay alive until the kernel is enqueued
+    for k, c in enumerate(criteria):
+        if isinstance(c, tuple):
+            field, op, threshold = c
+            if op not in _lib.CMP_OPS:
+                raise ValueError(f"label_filter: unknown comparison {op!r}")
+            field = field if field.dtype in (t.float32, t.float64) else field.to(t.float64)
+            field = field.to(lab.device).contiguous()
+            crit[k] = _lib.LabelCriterion(field.data_ptr(), _float_type(field), _lib.CMP_OPS[op], float(threshold))
+        else:
+            field = c.to(lab.device)
+            field = (field.view(t.uint8) if field.dtype == t.bool else field if field.dtype == t.uint8 else (field != 0).view(t.uint8)).contiguous()
+            crit[k] = _lib.LabelCriterion(field.data_ptr(), _lib.TF_U8, 0, 0.0)
+        if tuple(field.shape) != tuple(lab.shape):
+            raise ValueError("label_filter: a criterion must have the shape of the labels")
+        keep.append(field)
+    n = max(int(lab.max().item()), 0) if lab.numel() else 0
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros((0, K), bool), np.zeros(0, bool)
+    rec = t.empty((n + 1, 4), dtype=t.int32, device=lab.device)
+    _lib.check(_lib.lib().tf_label_filter(_lib.ptr(lab), T, H, W, n, crit, K, _lib.ptr(rec), _lib.stream_ptr()), "tf_label_filter")
+    r = rec[1:].cpu().numpy().astype(np.int64)
+    del keep
+    present = r[:, 1] >= 0
+    lengths = np.where(present, r[:, 1] - r[:, 0] + 1, 0)
+    hits = ((r[:, 2:3] >> np.arange(K)[None, :]) & 1).astype(bool)
+    return lengths, hits, present
+
+
 def remap_labels(labels, locations):
     """utils.label_utils.remap_labels(labels, locations) for a boolean `locations` of length max label"""
     t = _lib.torch()
