@@ -789,6 +789,67 @@ int tf_subseg_prepare(const int32_t *labels, const int32_t *d2, const int64_t *c
                       double shrink_factor, double *dist_mask, uint8_t *shrunk, void *stream);
 int tf_subseg_rank(const double *values, int64_t n, const double *sorted_keys, int64_t n_keys, float *rank, void *stream);
 
+/* ---- point observations onto a grid: np.histogramdd / scipy.stats.binned_statistic_dd (version 108) ---------------------
+ * The array-level binning of tobac_flow/glm.py:77-145 (np.histogram2d per frame), tobac_flow/nexrad.py:80-231 (two
+ * np.histogram2d and one binned_statistic_dd per site and frame) and scripts/grid_flux.py:65-112 (two binned_statistic_2d
+ * sums per variable): ONE pass over n_points points gives every output.  All pointers except the struct itself are
+ * device pointers; a NULL optional pointer switches its part off.
+ *   coord[d], d < n_dims (1 .. 3): n_points coordinates each, all TF_F32 or all TF_F64 (coord_dtype); float32 is widened
+ *     exactly.  coord[0] is the slowest output axis.
+ *   edges[d]: n_edges[d] >= 2 non-decreasing doubles (the caller checks the order), arbitrary, not uniform.
+ *   bin: k = upper_bound(edges, v) - 1 = searchsorted(edges, v, side="right") - 1; the point is kept if 0 <= k <
+ *     n_edges - 1 on every axis.  Always the search's answer (a guess from the mean step is only verified against the edges).
+ *   rule = TF_BIN_RULE_NUMPY (np.histogramdd): v == edges[last] belongs to the last bin; any other v >= edges[last], +-inf
+ *     and NaN are dropped silently.
+ *   rule = TF_BIN_RULE_SCIPY (scipy.stats._binned_statistic._bin_numbers, SciPy 1.15): v >= edges[last] belongs to the last
+ *     bin iff np.around(v, d) == np.around(edges[last], d), d = decimals[d] = int(-log10(min edge width)) + 6 from the
+ *     host, round_scale[d] = 10^|d|; np.around is evaluated as NumPy does, in the coordinates' type, on the point and on
+ *     the last edge (SciPy casts the edges to float32 for float32 samples: the caller passes such edges and their d).  A non-finite
+ *     value (TF_BIN_STATUS_VALUE) or coordinate (TF_BIN_STATUS_COORD) of a point that passes its masks, falls into a time
+ *     window and has an output left to add to is OR-ed into *status (uint32, may be NULL) and the point contributes
+ *     nothing.  TF_BIN_STATUS_RULES_DIFFER is OR-ed in when NumPy's rule would have decided otherwise about such a point
+ *     on some axis: while it is clear, the counts of this call are np.histogramdd's as well.
+ *   keep (uint8, optional) gates everything; keep_value (uint8, optional) gates count_v, sum_w, sum_wv only; with
+ *     TF_BIN_FINITE_VALUE in flags a non-finite value silently drops the point from those three as well (under either
+ *     rule: `wh = np.isfinite(data)` of grid_flux.py:66).
+ *   flip_mask: bit d set writes axis d mirrored, bin n_d - 1 - k (`np.histogram2d(y, x, (y_bins[::-1], x_bins))[0][::-1]`
+ *     of glm.py:89 and nexrad.py:104 without a second pass: edges[d] is the reversed, increasing array).
+ *   time (int64[n_points]) with win_start, win_end (int64[n_frames], both non-decreasing), all three or none: the point
+ *     goes to every frame f with win_start[f] <= t < win_end[f], the range [upper_bound(win_end, t), upper_bound(win_start,
+ *     t)).  Without them n_frames must be 1.
+ *   outputs, each optional, (n_frames, n_0[, n_1[, n_2]]) with n_d = n_edges[d] - 1, ACCUMULATED into (+=): count (int32)
+ *     the points that pass keep; count_v (int32) those that also pass keep_value / the finite test; sum_w, sum_wv (double)
+ *     the sums of weight and of weight * value over the count_v points.  value, weight: TF_F32 or TF_F64, optional (a
+ *     missing weight is 1, sum_wv needs value); the product is evaluated in NumPy's result type of the two operands
+ *     (float32 * float32 rounds in float32) and then widened.
+ * Counts are integer atomics: exact, identical in every run.  Sums are double atomics, one set per run of equal (frame
+ * range, bin) that a lane meets among its 16 points: they differ from a sequential sum by the summation order only and
+ * may differ in the last bits from run to run.  n_points < 2^31 (TF_EINVAL beyond); flat indices are 64-bit. */
+#define TF_BIN_MAX_DIMS 3
+#define TF_BIN_RULE_NUMPY 0
+#define TF_BIN_RULE_SCIPY 1
+#define TF_BIN_FINITE_VALUE 1
+#define TF_BIN_STATUS_COORD 1u
+#define TF_BIN_STATUS_VALUE 2u
+#define TF_BIN_STATUS_RULES_DIFFER 4u
+typedef struct TfBinPoints {
+    int32_t n_dims, coord_dtype, value_dtype, weight_dtype, rule, flags;
+    int32_t decimals[TF_BIN_MAX_DIMS];
+    int32_t flip_mask;
+    double round_scale[TF_BIN_MAX_DIMS];
+    int64_t n_points, n_frames;
+    int64_t n_edges[TF_BIN_MAX_DIMS];
+    const void *coord[TF_BIN_MAX_DIMS];
+    const double *edges[TF_BIN_MAX_DIMS];
+    const uint8_t *keep, *keep_value;
+    const void *value, *weight;
+    const int64_t *time, *win_start, *win_end;
+    int32_t *count, *count_v;
+    double *sum_w, *sum_wv;
+    uint32_t *status;
+} TfBinPoints;
+int tf_bin_points(const TfBinPoints *params_host, void *stream);
+
 /* ---- measurement aid (bench.py's roofline figure) ---------------------------------------------
  * tf_profile_enable(1): every kernel launch of the library is bracketed by HIP events on its own
  * stream and tagged with its ALGORITHMIC byte count.  tf_profile_collect() synchronises

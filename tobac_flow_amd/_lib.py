@@ -33,11 +33,26 @@ class NormParams(ctypes.Structure):
                 ("quantiles", ctypes.c_int64), ("size", ctypes.c_int64), ("flags", ctypes.c_int)]
 
 
+class BinPoints(ctypes.Structure):
+    """TfBinPoints of include/tobac_flow_hip.h"""
+    _fields_ = [("n_dims", ctypes.c_int32), ("coord_dtype", ctypes.c_int32), ("value_dtype", ctypes.c_int32),
+                ("weight_dtype", ctypes.c_int32), ("rule", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("decimals", ctypes.c_int32 * 3), ("flip_mask", ctypes.c_int32), ("round_scale", ctypes.c_double * 3),
+                ("n_points", ctypes.c_int64), ("n_frames", ctypes.c_int64), ("n_edges", ctypes.c_int64 * 3),
+                ("coord", ctypes.c_void_p * 3), ("edges", ctypes.c_void_p * 3), ("keep", ctypes.c_void_p),
+                ("keep_value", ctypes.c_void_p), ("value", ctypes.c_void_p), ("weight", ctypes.c_void_p),
+                ("time", ctypes.c_void_p), ("win_start", ctypes.c_void_p), ("win_end", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("count_v", ctypes.c_void_p), ("sum_w", ctypes.c_void_p),
+                ("sum_wv", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 class LabelCriterion(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int), ("op", ctypes.c_int), ("threshold", ctypes.c_double)]
 
 
 CMP_OPS = {">=": 0, ">": 1, "<=": 2, "<": 3}
+BIN_RULE_NUMPY, BIN_RULE_SCIPY, BIN_FINITE_VALUE = 0, 1, 1
+BIN_STATUS_COORD, BIN_STATUS_VALUE, BIN_STATUS_RULES_DIFFER = 1, 2, 4
 NORM_METHODS = {"linear": 0, "log": 1, "inverse_log": 2, "z_score": 3, "uniform": 4, "local_linear": 5}
 NORM_HAS_VMIN, NORM_HAS_VMAX, NORM_F32_SCALARS = 1, 2, 4
 FB_CHAIN_DEFAULT, FB_CHAIN_ONE_LANE, FB_CHAIN_TWO_PART = 0, 1, 2
@@ -156,6 +171,7 @@ _PROTOS = {
     "tf_label_nanmin": (_c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_subseg_prepare": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P]),
     "tf_subseg_rank": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P]),
+    "tf_bin_points": (_c.c_int, [_c.POINTER(BinPoints), _P]),
     "tf_slice_labels": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_pair_counts": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_sizes": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P]),

@@ -13,6 +13,7 @@ from tobac_flow_amd.utils.normalisation_utils import (inverse_log_norm, linear_n
 from tobac_flow_amd.utils.stats_utils import (get_weighted_proportions, mse, n_unique_along_axis, weighted_average_and_std,
                                               weighted_average_uncertainty, weighted_stats,
                                               weighted_stats_and_uncertainties, weighted_uncertainties)
+from tobac_flow_amd.utils.xarray_utils import get_coord_bin_edges
 
 __all__ = (
     "get_datetime_from_coord", "get_time_diff_from_coord", "time_diff",
@@ -23,4 +24,5 @@ __all__ = (
     "select_normalisation_method", "to_8bit", "uniform_norm", "z_norm",
     "mse", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
     "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions",
+    "get_coord_bin_edges",
 )
