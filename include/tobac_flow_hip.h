@@ -607,7 +607,8 @@ int tf_label(const uint8_t *in, int64_t T, int64_t H, int64_t W, const uint8_t *
  *   nearest-neighbour warps of the labels to t-1 / t+1 (structure * [1, 0, 1]; exactly one tap per outer plane, as the
  *   reference's tuple unpacking requires), overlap counts, the criterion `count > absolute_overlap and count >=
  *   overlap * min(n_locs, size(other))`, and the reference's first-come-first-served grouping in ascending label order
- *   (forward neighbours before backward ones).  out may alias nothing.  *n_objects_host = number of objects.
+ *   (forward neighbours before backward ones).  out may alias nothing.  *n_objects_host = number of groups opened: the
+ *   largest object id, unless ids without pixels follow the last id that has some (each opens a group of its own).
  * tf_flow_label: tobac_flow/label.py:84-175 with subsegment_shrink = 0: flat_label (utils/label_utils.py:143-180 =
  *   scipy.ndimage.label with the structure's t-planes zeroed) followed by the linking above.  mask: (T, H, W) uint8.
  * tf_window_overlap_pairs: tobac_flow/linking.py:49-93 / :96-140 -- `left` / `right` are the labels two consecutive

@@ -14,7 +14,8 @@ The reference works on an xarray.Dataset (absent from this image); `ds` here is 
 coordinates in ds["coords"] (a dict).  The per-label work keeps the reference's own tools
 (scipy.ndimage.labeled_comprehension, scipy.stats.mode, np.bincount / np.unique), so tie-breaking is theirs.
 PARITY STATUS: pinned by known answers worked out by hand in tests/test_oracle_known_answers.py; the reference holds no
-test or fixture for these functions.
+test or fixture for these functions.  slice_labels and remap_labels are also held to tests/golden/label_glue_ref.npz,
+which the reference's own functions wrote (tests/test_label_glue_cases_cpu.py).
 """
 import numpy as np
 import scipy.ndimage as ndi

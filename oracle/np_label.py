@@ -6,8 +6,9 @@ Loop-for-loop numpy restatement of the reference's flow-aware labelling
   flow_link_overlap     /root/reference/tobac_flow/label.py:249-321
   flat_label            /root/reference/tobac_flow/utils/label_utils.py:143-180
   find_overlapping_labels /root/reference/tobac_flow/utils/label_utils.py:352-376
-with the nearest-neighbour label warps taken from oracle/np_ops.convolve.  The reference has no test
-for these functions; the restatement keeps its control flow (per-label bincount / unique, BFS with a
+with the nearest-neighbour label warps taken from oracle/np_ops.convolve.  PARITY STATUS: pinned by
+tests/golden/label_glue_ref.npz, which the reference's own functions wrote (tests/test_label_glue_cases_cpu.py;
+the cross-window functions below included).  The restatement keeps its control flow (per-label bincount / unique, BFS with a
 `processed` array) so that label numbering and the first-come grouping of asymmetric overlaps are the
 reference's.
 """

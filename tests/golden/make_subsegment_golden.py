@@ -10,8 +10,8 @@ prepended line (``from __future__ import annotations`` -- python3.9 cannot evalu
 is written into the repository: the masks (bit-packed), the flows of the flow-linked case and the reference's labels.
 
 The flow-linked case.  flow_label only needs an object with `.convolve`; the reference's Flow.convolve remaps with OpenCV.
-The stand-in below shifts by the flows instead, which is what a nearest-neighbour remap does when every flow vector is
-INTEGER-VALUED, as the stored ones are (int8): the sample position is a pixel centre, there is nothing to round, and a
+The stand-in (tests/label_glue_cases.ShiftFlow) shifts by the flows instead, which is what a nearest-neighbour remap does
+when every flow vector is INTEGER-VALUED, as the stored ones are (int8): the sample position is a pixel centre, there is nothing to round, and a
 position outside the frame gives the fill value.  tobac_flow_amd's Flow, built from the same vectors as float32, rounds
 the same positions to themselves.
 
@@ -30,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 import subsegment_cases as sc  # noqa: E402
+from label_glue_cases import ShiftFlow  # noqa: E402
 
 if len(sys.argv) != 2:
     sys.exit(__doc__)
@@ -48,35 +49,6 @@ import skimage  # noqa: E402
 from tobac_flow.label import flow_label as ref_flow_label, subsegment_labels as ref_subsegment_labels  # noqa: E402
 
 assert skimage.__version__.startswith("0.18"), skimage.__version__
-
-
-class ShiftFlow:
-    """duck-typed Flow for flow_label: convolve(method="nearest") by integer-valued flows = an exact shift"""
-
-    def __init__(self, forward, backward):
-        assert forward.dtype.kind == "i" and backward.dtype.kind == "i"
-        self.forward_flow, self.backward_flow, self.shape = forward, backward, forward.shape[:-1]
-
-    @staticmethod
-    def _shift(src, flow, fill_value):
-        H, W = src.shape
-        yy, xx = np.mgrid[:H, :W]
-        x, y = xx + flow[..., 0], yy + flow[..., 1]
-        inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
-        return np.where(inside, src[np.where(inside, y, 0), np.where(inside, x, 0)], fill_value)
-
-    def convolve(self, data, structure=None, method="linear", fill_value=np.nan, dtype=np.float32, func=None):
-        assert method == "nearest" and func is None and data.shape == self.shape
-        s = np.asarray(structure) != 0
-        assert s[0].sum() == 1 and s[0, 1, 1] and s[2].sum() == 1 and s[2, 1, 1] and not s[1].any()
-        T = data.shape[0]
-        out = np.full((2,) + data.shape, fill_value, dtype=dtype)
-        for t in range(T):
-            if t > 0:
-                out[0, t] = self._shift(data[t - 1], self.backward_flow[t], fill_value)
-            if t < T - 1:
-                out[1, t] = self._shift(data[t + 1], self.forward_flow[t], fill_value)
-        return out
 
 
 try:

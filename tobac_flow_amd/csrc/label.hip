@@ -321,7 +321,9 @@ extern "C" size_t tf_flow_link_workspace_bytes(int64_t T, int64_t H, int64_t W, 
     return 2 * tf_align_up((size_t)N * 4, 256) + tf_pair_counts_workspace_bytes(N, max_runs) + 4096;
 }
 
-static void link_groups(int n_lab, const std::vector<int64_t> &sizes, const std::vector<u64> keys[2],
+// Returns the number of groups opened.  An id without pixels opens a group too and consumes a number (label.py:145-148), so
+// the count can exceed the largest object id written when such ids come after the last id that has pixels.
+static int32_t link_groups(int n_lab, const std::vector<int64_t> &sizes, const std::vector<u64> keys[2],
                         const std::vector<int64_t> cnts[2], double overlap, int64_t absolute_overlap, std::vector<int32_t> &lut)
 {
     // adjacency per direction (0 = forward, 1 = backward), CSR over the sorted keys
@@ -357,6 +359,7 @@ static void link_groups(int n_lab, const std::vector<int64_t> &sizes, const std:
         }
         for (int32_t m : stack) lut[m] = sizes[m] > 0 ? n_groups : 0;
     }
+    return n_groups;
 }
 
 extern "C" int tf_flow_link_overlap(const int32_t *flat_labels, const float *fwd, const float *bwd,
@@ -421,9 +424,7 @@ extern "C" int tf_flow_link_overlap(const int32_t *flat_labels, const float *fwd
         }
     }
     std::vector<int32_t> lut;
-    link_groups(n_lab, sizes, keys, cnts, overlap, absolute_overlap, lut);
-    int32_t n_groups = 0;
-    for (int32_t v : lut) n_groups = std::max(n_groups, v);
+    const int32_t n_groups = link_groups(n_lab, sizes, keys, cnts, overlap, absolute_overlap, lut);
     if (n_objects_host) *n_objects_host = n_groups;
     // relabel: the LUT goes through the (now free) pair-count scratch
     int32_t *d_lut = (int32_t *)rest;
