@@ -4,7 +4,10 @@ The one-lane iteration kernel k_fb_iter<2, 0> keeps two waves resident per SIMD;
 granules of 8.  What the two waves leave free -- 64 registers, and the LDS four of its workgroups do not hold -- is what the
 connectivity-1 flood sweeps have to fit into if they are to run BESIDE those waves instead of displacing them (DESIGN.md
 section 4, "What runs beside the iteration kernel").  The figures are the compiler's own
-(-Rpass-analysis=kernel-resource-usage on the Makefile's flags); no GPU is needed."""
+(-Rpass-analysis=kernel-resource-usage on the Makefile's flags); no GPU is needed.
+
+The per-label pass kernels that walk runs of equal labels (csrc/label_runs.h) are held to the same 64 registers for another
+reason: they are bound by memory and atomics, and 64 registers are the 8 waves per SIMD that hide both."""
 import os
 import re
 import shutil
@@ -21,6 +24,11 @@ FB_ITER = "_Z9k_fb_iterILi2ELi0EE"                        # k_fb_iter<2, 0>
 SWEEPS_IN_64 = ["_Z13k_ws_sweep_a63WsC"] + [f"_Z17k_ws_sweep_chain6ILi{k}ELb{r}EE" for k in (1, 2, 3, 0) for r in (0, 1)]
 # any neighbour count: not part of the budget, reported
 SWEEPS_ANY = ["_Z12k_ws_sweep_a3WsC", "_Z16k_ws_sweep_chainILb0EE", "_Z16k_ws_sweep_chainILb1EE", "_Z13k_ws_sweep_m1ILi6EE"]
+# the per-label pass kernels, every instantiation: (source, mangled prefix)
+LABEL_PASSES = ([("wstats.hip", f"_Z14k_wstats_pass{p}I{f}E") for p in (1, 2) for f in "fd"] + [("wstats.hip", "_Z12k_wprop_pass")]
+                + [("edt.hip", f"_Z19k_label_nanmin_passI{f}E") for f in "hfd"]
+                + [("props.hip", f"_Z13k_label_propsILb{a}EE") for a in (0, 1)]
+                + [("label_filter.hip", f"_Z14k_label_filterILb{a}EE") for a in (0, 1)])
 
 
 def _hipcc():
@@ -95,3 +103,19 @@ def test_the_other_sweep_forms_do_not_spill(resources):
         sw = _one(resources["ws"], kernel)
         print(kernel, sw, "allocated", _allocated(sw))
         assert sw["scratch"] == 0
+
+
+@pytest.fixture(scope="module")
+def label_resources(tmp_path_factory):
+    if _hipcc() is None:
+        pytest.skip("no hipcc")
+    tmp = str(tmp_path_factory.mktemp("label_pass_resources"))
+    return {source: _resources(source, tmp) for source in sorted({s for s, _ in LABEL_PASSES})}
+
+
+@pytest.mark.parametrize("source,kernel", LABEL_PASSES)
+def test_label_pass_kernels_keep_8_waves_per_simd(label_resources, source, kernel):
+    k = _one(label_resources[source], kernel)
+    print(kernel, k, "allocated", _allocated(k))
+    assert k["scratch"] == 0
+    assert _allocated(k) <= 64

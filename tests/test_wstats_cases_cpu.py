@@ -1,18 +1,24 @@
 """The yardsticks of the per-label weighted statistics, without a device: the float64 restatement of tests/wstats_cases.py
 and the per-region host forms of tobac_flow_amd.utils.stats_utils against the reference's own results in
-tests/golden/wstats_ref.npz, and the input validation of tobac_flow_amd.postprocess.
+tests/golden/wstats_ref.npz, the input validation of tobac_flow_amd.postprocess, and the kernel bodies compiled for the
+host (tools/wstats_host_check.cpp).
 
 Bounds.  NaN patterns are identical and min, max and the errors at them are equal.  The summed values (mean, std, uncertainty
 of the mean, combined error) of the float32 case are held to 4 x the largest relative difference between the reference's
 float32 results and the float64 restatement over the committed cases, measured when the fixture was written and stored in
 it (1.43e-7: the reference's own float32 summation error; the assertion therefore sits at 5.7e-7, below the project's
 rtol 2e-5 for this class); those of the float64 case to rtol 1e-12."""
+import os
+import shutil
+import subprocess
 from functools import partial
 
 import numpy as np
 import pytest
 
 import wstats_cases as wc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bound(name, meta):
@@ -206,3 +212,15 @@ def test_operands_that_merely_broadcast_take_the_host_form():
     assert np.array_equal(np.isnan(got), np.isnan(want))
     assert np.array_equal(got[:, wc.SELECTED], want[:, wc.SELECTED], equal_nan=True)
     np.testing.assert_allclose(got, want, rtol=1e-12, atol=0, equal_nan=True)
+
+
+def test_kernel_bodies_on_the_host_against_plain_loops(tmp_path):
+    """tools/wstats_host_check.cpp: the bodies of csrc/wstats_kernels.h, and the raveled run walker of csrc/label_runs.h
+    under them, compiled for the CPU and run lane after lane on exactly-sized buffers (its first lines give the
+    AddressSanitizer / UBSan command; here a plain build)"""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "wstats_host_check"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "wstats_host_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "all equal" in out.stdout, out.stdout + out.stderr

@@ -5,29 +5,17 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/tobac_flow_hip.h"
-#include "wstats_kernels.h"                                       // ws_vload / ws_load4
+#include "label_runs.h"                                           // the raveled work layout, lr_load4, lr_aligned16
 
 // ---- work layout -----------------------------------------------------------------------------------------------------
-// As wstats_kernels.h: a workgroup of 256 lanes takes BN_BLOCK = 4096 consecutive points, each of its four waves 1024 of
-// them in BN_ITERS = 4 steps of 256; in step k lane j holds the BN_VEC = 4 points from wave base + 256 k + 4 j, so one
-// load instruction of a wave reads 64 adjacent 16-byte pieces of a float32 operand.  A lane keeps ONE open run -- the
-// (frame range, bin) of its last kept point and the partial count / sums -- across its 16 points and issues one set of
-// atomics per frame of the range when the key changes and at the end.  Neighbouring pixels of a swath mostly share a bin;
-// scattered points do not, and then every point costs its atomics (profiles/point_binning.txt).
-#define BN_VEC WS_VEC
-#define BN_ITERS 4
-#define BN_WAVE_SPAN (64 * BN_VEC * BN_ITERS)
-#define BN_BLOCK (4 * BN_WAVE_SPAN)
-
-__host__ __device__ inline int64_t bn_first_point(int64_t block, int tid, int step)
-{
-    return block * BN_BLOCK + (int64_t)(tid >> 6) * BN_WAVE_SPAN + (int64_t)step * (64 * BN_VEC) + (int64_t)(tid & 63) * BN_VEC;
-}
-
-__host__ __device__ inline bool bn_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+// The raveled layout of label_runs.h with points for voxels: a workgroup of 256 lanes takes LR_BLOCK = 4096 consecutive
+// points, lane j of a wave the LR_VEC = 4 points from wave base + 256 k + 4 j in step k (lr_first_voxel).  A lane keeps
+// ONE open run -- the (frame range, bin) of its last kept point and the partial count / sums -- across its 16 points and
+// issues one set of atomics per frame of the range when the key changes and at the end.  Neighbouring pixels of a swath
+// mostly share a bin; scattered points do not, and then every point costs its atomics (profiles/point_binning.txt).
 
 // four consecutive int64: two adjacent 16-byte loads (little endian)
-__host__ __device__ inline void bn_load4_i64(const int64_t *__restrict__ p, int64_t i, int m, bool vec, int64_t v[BN_VEC])
+__host__ __device__ inline void bn_load4_i64(const int64_t *__restrict__ p, int64_t i, int m, bool vec, int64_t v[LR_VEC])
 {
     if (vec) {
         const int4 a = ((const int4 *)(p + i))[0], b = ((const int4 *)(p + i))[1];
@@ -38,7 +26,7 @@ __host__ __device__ inline void bn_load4_i64(const int64_t *__restrict__ p, int6
         return;
     }
 #pragma unroll
-    for (int j = 0; j < BN_VEC; j++) v[j] = j < m ? p[i + j] : 0;
+    for (int j = 0; j < LR_VEC; j++) v[j] = j < m ? p[i + j] : 0;
 }
 
 // np.around(v, decimals) in the type of v: multiply by 10^d, rint, divide for d > 0; divide, rint, multiply for d < 0
@@ -113,17 +101,17 @@ __host__ __device__ inline int64_t bn_axis_bin(C vc, const BnAxis &a, int rule, 
     return lo - 1;
 }
 
-__host__ __device__ inline void bn_load4_real(const void *__restrict__ p, int dtype, int64_t i, int m, bool vec, float f[BN_VEC],
-                                              double d[BN_VEC])
+__host__ __device__ inline void bn_load4_real(const void *__restrict__ p, int dtype, int64_t i, int m, bool vec, float f[LR_VEC],
+                                              double d[LR_VEC])
 {
     if (dtype == TF_F32) {
-        ws_load4<float>((const float *)p, i, m, vec, f, 0.f);
+        lr_load4<float>((const float *)p, i, m, vec, f, 0.f);
 #pragma unroll
-        for (int j = 0; j < BN_VEC; j++) d[j] = (double)f[j];
+        for (int j = 0; j < LR_VEC; j++) d[j] = (double)f[j];
     } else {
-        ws_load4<double>((const double *)p, i, m, vec, d, 0.0);
+        lr_load4<double>((const double *)p, i, m, vec, d, 0.0);
 #pragma unroll
-        for (int j = 0; j < BN_VEC; j++) f[j] = 0.f;
+        for (int j = 0; j < LR_VEC; j++) f[j] = 0.f;
     }
 }
 
@@ -141,13 +129,13 @@ __device__ inline void bn_points_body(int64_t block, int tid, const TfBinPoints 
         if (d >= nd) continue;
         ax[d] = bn_axis(p, d);
         n_bins *= ax[d].ne - 1;
-        vec_c = vec_c && bn_aligned16(p.coord[d]);
+        vec_c = vec_c && lr_aligned16(p.coord[d]);
     }
     const bool scipy = p.rule == TF_BIN_RULE_SCIPY, finite_value = (p.flags & TF_BIN_FINITE_VALUE) != 0;
     const bool want_value = p.count_v || p.sum_w || p.sum_wv;
     const bool f32_product = p.value && p.value_dtype == TF_F32 && !(p.weight && p.weight_dtype == TF_F64);
-    const bool vec_keep = bn_aligned16(p.keep), vec_kv = bn_aligned16(p.keep_value), vec_t = bn_aligned16(p.time);
-    const bool vec_v = bn_aligned16(p.value), vec_w = bn_aligned16(p.weight);
+    const bool vec_keep = lr_aligned16(p.keep), vec_kv = lr_aligned16(p.keep_value), vec_t = lr_aligned16(p.time);
+    const bool vec_v = lr_aligned16(p.value), vec_w = lr_aligned16(p.weight);
 
     int64_t cur_bin = -1, cur_f0 = 0, cur_f1 = 0;
     int32_t cnt = 0, cnt_v = 0;
@@ -165,31 +153,31 @@ __device__ inline void bn_points_body(int64_t block, int tid, const TfBinPoints 
         }
     };
 #pragma unroll 1
-    for (int step = 0; step < BN_ITERS; step++) {
-        const int64_t i = bn_first_point(block, tid, step);
+    for (int step = 0; step < LR_ITERS; step++) {
+        const int64_t i = lr_first_voxel(block, tid, step);
         if (i >= n) break;
-        const int m = n - i < BN_VEC ? (int)(n - i) : BN_VEC;
-        const bool full = m == BN_VEC;
-        uint8_t kp[BN_VEC] = {1, 1, 1, 1}, kv[BN_VEC] = {1, 1, 1, 1};
+        const int m = n - i < LR_VEC ? (int)(n - i) : LR_VEC;
+        const bool full = m == LR_VEC;
+        uint8_t kp[LR_VEC] = {1, 1, 1, 1}, kv[LR_VEC] = {1, 1, 1, 1};
         if (p.keep) {
-            ws_load4<uint8_t>(p.keep, i, m, vec_keep && full, kp, (uint8_t)0);
+            lr_load4<uint8_t>(p.keep, i, m, vec_keep && full, kp, (uint8_t)0);
             if (!(kp[0] | kp[1] | kp[2] | kp[3])) continue;       // nothing kept: the open run stays open
         }
-        C cv[TF_BIN_MAX_DIMS][BN_VEC];
+        C cv[TF_BIN_MAX_DIMS][LR_VEC];
 #pragma unroll
         for (int d = 0; d < TF_BIN_MAX_DIMS; d++)
-            if (d < nd) ws_load4<C>((const C *)p.coord[d], i, m, vec_c && full, cv[d], (C)0);
-        int64_t tv[BN_VEC] = {0, 0, 0, 0};
+            if (d < nd) lr_load4<C>((const C *)p.coord[d], i, m, vec_c && full, cv[d], (C)0);
+        int64_t tv[LR_VEC] = {0, 0, 0, 0};
         if (p.time) bn_load4_i64(p.time, i, m, vec_t && full, tv);
-        float vf[BN_VEC] = {0.f, 0.f, 0.f, 0.f}, wf[BN_VEC] = {1.f, 1.f, 1.f, 1.f};
-        double vd[BN_VEC] = {0, 0, 0, 0}, wd[BN_VEC] = {1, 1, 1, 1};
+        float vf[LR_VEC] = {0.f, 0.f, 0.f, 0.f}, wf[LR_VEC] = {1.f, 1.f, 1.f, 1.f};
+        double vd[LR_VEC] = {0, 0, 0, 0}, wd[LR_VEC] = {1, 1, 1, 1};
         if (want_value) {
-            if (p.keep_value) ws_load4<uint8_t>(p.keep_value, i, m, vec_kv && full, kv, (uint8_t)0);
+            if (p.keep_value) lr_load4<uint8_t>(p.keep_value, i, m, vec_kv && full, kv, (uint8_t)0);
             if (p.value) bn_load4_real(p.value, p.value_dtype, i, m, vec_v && full, vf, vd);
             if (p.weight) bn_load4_real(p.weight, p.weight_dtype, i, m, vec_w && full, wf, wd);
         }
 #pragma unroll
-        for (int j = 0; j < BN_VEC; j++) {
+        for (int j = 0; j < LR_VEC; j++) {
             if (j >= m || !kp[j]) continue;
             int64_t f0 = 0, f1 = 1;
             if (p.time) {                                         // win_start[f] <= t < win_end[f]: a contiguous range of frames
@@ -210,7 +198,7 @@ __device__ inline void bn_points_body(int64_t block, int tid, const TfBinPoints 
                 bin = bin * nb + (k < 0 ? 0 : ((p.flip_mask >> d) & 1) ? nb - 1 - k : k);
             }
             bool with_value = want_value && kv[j];
-            if (with_value && p.value && !ws_finite(vd[j])) {
+            if (with_value && p.value && !lr_finite(vd[j])) {
                 if (finite_value) with_value = false;
                 else if (scipy) { status |= TF_BIN_STATUS_VALUE; continue; }
             }

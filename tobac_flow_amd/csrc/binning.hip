@@ -47,7 +47,7 @@ extern "C" int tf_bin_points(const TfBinPoints *params_host, void *stream)
     TF_REQUIRE(!p.sum_wv || p.value || p.n_points == 0, "tf_bin_points: sum_wv needs values");
     TF_REQUIRE(p.count || p.count_v || p.sum_w || p.sum_wv, "tf_bin_points: no output");
     if (p.n_points == 0) return TF_OK;
-    const int64_t blocks = (p.n_points + BN_BLOCK - 1) / BN_BLOCK;
+    const int64_t blocks = (p.n_points + LR_BLOCK - 1) / LR_BLOCK;
     hipStream_t s = (hipStream_t)stream;
     if (p.coord_dtype == TF_F32)
         hipLaunchKernelGGL(k_bin_points<float>, dim3((unsigned)blocks), dim3(256), 0, s, p);

@@ -170,18 +170,16 @@ extern "C" size_t tf_label_nanmin_workspace_bytes(int64_t n_labels)
     return tf_align_up((size_t)n_labels * LM_REC * sizeof(unsigned long long), 256) + 256;
 }
 
-static bool lm_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 template <typename F>
 static int lm_run(const int32_t *labels, const F *x, int64_t n, int64_t n_labels, const int64_t *ids, int64_t n_ids,
                   double *out_min, int64_t *out_count, unsigned long long *acc, hipStream_t s)
 {
-    const int64_t blocks = (n + WS_BLOCK - 1) / WS_BLOCK, id_blocks = (n_ids + 255) / 256;
+    const int64_t blocks = (n + LR_BLOCK - 1) / LR_BLOCK, id_blocks = (n_ids + 255) / 256;
     TF_REQUIRE(blocks <= 0x7fffffffll && id_blocks <= 0x7fffffffll, "tf_label_nanmin: volume too large for one launch");
     hipLaunchKernelGGL(k_label_nanmin_init, dim3((unsigned)((n_labels + 255) / 256)), dim3(256), 0, s, n_labels, acc);
     TF_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_label_nanmin_pass<F>, dim3((unsigned)blocks), dim3(256), 0, s, labels, x, n,
-                       lm_aligned16(labels) && lm_aligned16(x), n_labels, acc);
+                       lr_aligned16(labels) && lr_aligned16(x), n_labels, acc);
     TF_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_label_nanmin_finish, dim3((unsigned)id_blocks), dim3(256), 0, s, n_ids, ids, n_labels,
                        (const unsigned long long *)acc, out_min, out_count);

@@ -3,7 +3,7 @@
 // atomics and runs the bodies lane after lane under AddressSanitizer.  Nothing here touches the HIP runtime.
 #pragma once
 #include <stdint.h>
-#include "wstats_kernels.h"                                       // ws_key, ws_load4 and the 4096-voxel work layout
+#include "label_runs.h"                                           // lr_key, the raveled work layout and its walker
 
 // ---- tf_edt2d_frames ---------------------------------------------------------------------------------------------------
 // Exact squared Euclidean distance to the nearest feature (voxel != 0; NaN != 0, so NaN is one) of the same frame, in
@@ -163,25 +163,25 @@ __device__ inline void edt_env_body(int64_t p, int64_t T, int64_t hw, int32_t W,
 }
 
 // ---- tf_label_nanmin ---------------------------------------------------------------------------------------------------
-// Record per label id (id - 1 indexes it): [0] the smallest ws_key of the label's non-NaN values, LM_ALLNAN where it has
-// voxels and all are NaN, WS_NONE where it has none; [1] the number of its non-NaN voxels.  The work layout is that of
-// wstats_kernels.h: a lane keeps one open run over its 16 voxels and issues one atomicMin (skipped where the record
-// already holds a smaller key) and one atomicAdd per run that ends inside them; the runs still open at the end are
-// combined across the wave where its lanes agree on the label (lm_flush_wave).  Every real key, +inf's included, is
-// below LM_ALLNAN.
+// Record per label id (id - 1 indexes it): [0] the smallest lr_key of the label's non-NaN values, LM_ALLNAN where it has
+// voxels and all are NaN, LR_NONE where it has none; [1] the number of its non-NaN voxels.  The work layout is the
+// raveled one of label_runs.h, walked by its lr_walk: a lane keeps one open run over its 16 voxels and issues one
+// atomicMin (skipped where the record already holds a smaller key) and one atomicAdd per run that ends inside them; the
+// runs still open at the end are combined across the wave where its lanes agree on the label (lm_flush_wave).  Every real
+// key, +inf's included, is below LM_ALLNAN.
 #define LM_REC 2
-#define LM_ALLNAN (WS_NONE - 1)
+#define LM_ALLNAN (LR_NONE - 1)
 
 __device__ inline void lm_init_body(int64_t l, int64_t n_labels, unsigned long long *acc)
 {
     if (l >= n_labels) return;
-    acc[LM_REC * l] = WS_NONE;
+    acc[LM_REC * l] = LR_NONE;
     acc[LM_REC * l + 1] = 0;
 }
 
 __device__ inline void lm_flush(int32_t cur, unsigned long long kmin, unsigned long long cnt, unsigned long long *acc)
 {
-    if (kmin == WS_NONE) return;                                  // cur is in [1, n_labels] whenever a voxel was met
+    if (kmin == LR_NONE) return;                                  // cur is in [1, n_labels] whenever a voxel was met
     unsigned long long *r = acc + LM_REC * (int64_t)(cur - 1);
     if (r[0] > kmin) atomicMin(r, kmin);                          // a stale read only costs a redundant atomic
     if (cnt) atomicAdd(r + 1, cnt);
@@ -194,7 +194,7 @@ __device__ inline void lm_flush(int32_t cur, unsigned long long kmin, unsigned l
 __device__ inline void lm_flush_wave(int tid, int32_t cur, unsigned long long kmin, unsigned long long cnt, unsigned long long *acc)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const bool has = kmin != WS_NONE;
+    const bool has = kmin != LR_NONE;
     int32_t top = has ? cur : 0;                                  // labels are >= 1
     for (int o = 32; o; o >>= 1) {
         const int32_t v = __shfl_xor(top, o);
@@ -215,41 +215,31 @@ __device__ inline void lm_flush_wave(int tid, int32_t cur, unsigned long long km
 }
 
 template <typename F>
+struct LmPass {
+    const F *__restrict__ x; bool vec; unsigned long long *acc;
+    unsigned long long cnt = 0, kmin = LR_NONE;
+    F xv[LR_VEC];
+
+    __device__ __forceinline__ void load(int64_t i, int m, bool full) { lr_load4<F>(x, i, m, vec && full, xv, (F)0); }
+    __device__ __forceinline__ bool ends(int) const { return false; }
+    __device__ __forceinline__ void open(int32_t, bool, int) { cnt = 0; kmin = LR_NONE; }
+    __device__ __forceinline__ void add(int64_t, int j)
+    {
+        const double xd = (double)xv[j];
+        unsigned long long k = LM_ALLNAN;
+        if (xd == xd) { k = lr_key(xd); cnt++; }
+        kmin = k < kmin ? k : kmin;
+    }
+    __device__ __forceinline__ void close(int32_t cur) { lm_flush(cur, kmin, cnt, acc); cnt = 0; kmin = LR_NONE; }
+    __device__ __forceinline__ void last(int tid, int32_t cur) { lm_flush_wave(tid, cur, kmin, cnt, acc); }
+};
+
+template <typename F>
 __device__ inline void lm_pass_body(int64_t block, int tid, const int32_t *__restrict__ labels, const F *__restrict__ x, int64_t n,
                                     bool vec, int64_t n_labels, unsigned long long *acc)
 {
-    int32_t cur = 0;
-    unsigned long long cnt = 0, kmin = WS_NONE;
-    auto flush = [&]() { lm_flush(cur, kmin, cnt, acc); };
-#pragma unroll
-    for (int step = 0; step < WS_ITERS; step++) {
-        const int64_t i = ws_first_voxel(block, tid, step);
-        if (i >= n) break;
-        const int m = n - i < WS_VEC ? (int)(n - i) : WS_VEC;
-        const bool full = m == WS_VEC;
-        int32_t lv[WS_VEC];
-        ws_load4<int32_t>(labels, i, m, vec && full, lv, 0);
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < WS_VEC; j++) any |= lv[j] >= 1 && lv[j] <= n_labels;
-        if (!any) { flush(); cur = 0; cnt = 0; kmin = WS_NONE; continue; }
-        F xv[WS_VEC];
-        ws_load4<F>(x, i, m, vec && full, xv, (F)0);
-#pragma unroll
-        for (int j = 0; j < WS_VEC; j++) {
-            const int32_t l = lv[j];
-            if (l != cur) {
-                flush();
-                cur = l; cnt = 0; kmin = WS_NONE;
-            }
-            if (l < 1 || l > n_labels) continue;
-            const double xd = (double)xv[j];
-            unsigned long long k = LM_ALLNAN;
-            if (xd == xd) { k = ws_key(xd); cnt++; }
-            kmin = k < kmin ? k : kmin;
-        }
-    }
-    lm_flush_wave(tid, cur, kmin, cnt, acc);
+    LmPass<F> v{x, vec, acc};
+    lr_walk(block, tid, labels, n, vec, n_labels, v);
 }
 
 // For the k-th requested id: out_min[k] = the minimum, NaN where the label has no non-NaN voxel; out_count[k] = the
@@ -264,7 +254,7 @@ __device__ inline void lm_finish_body(int64_t k, int64_t n_ids, const int64_t *_
     int64_t count = -1;
     if (id >= 1 && id <= n_labels) {
         const unsigned long long key = acc[LM_REC * (id - 1)];
-        if (key != WS_NONE) {
+        if (key != LR_NONE) {
             count = (int64_t)acc[LM_REC * (id - 1) + 1];
             if (key != LM_ALLNAN) {
                 union { double d; unsigned long long u; } c;

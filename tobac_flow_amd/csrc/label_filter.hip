@@ -8,16 +8,18 @@
 // `field >= upper` volumes never exist.  Criterion operands are read only under labelled voxels, and only while the
 // label's bit for that criterion is still clear.
 #include "tf_common.h"
+#include "label_runs.h"
 #include <math.h>
 
-// Work layout as k_label_props (props.hip:17-21): one lane takes LF_RUN consecutive voxels of ONE row, most lanes see
-// background only and leave after their loads, and the others flush once per run of equal labels.  No merge across the
-// wave, for the reason given there.
+// The row-chunk layout of label_runs.h, as k_label_props: one lane takes LR_ROW_RUN consecutive voxels of ONE row, most
+// lanes see background only and leave after their loads, and the others flush once per run of equal labels.  No merge
+// across the wave, for the reason given there.  The kernel keeps its own loop over the chunk and does not go through
+// lr_walk_row: on that walker it measured 7.5 % slower with three criteria, with the same loads and atomics in the code
+// object (profiles/label_runs.txt; the cause was not found).  Only the launch geometry (lr_row_grid) is shared.
 // Record per label id: {tmin, tmax, hits, 0} = 16 B, so four labels share a 64-B line and one label's atomics fall into
 // one line.  At the start of a run the lane reads the record once: a criterion whose bit is set already is not evaluated
 // for the run, and an atomic is issued only where the value read would change.  Bits are only ever set, tmin only falls
 // and tmax only rises, so a stale read costs a redundant evaluation or atomic, never a wrong answer.
-#define LF_RUN 16
 #define LF_MAX 8
 
 struct LfCrit { const void *data; int dtype, op; float th32; double th64; };
@@ -51,25 +53,25 @@ k_label_filter(const int32_t *__restrict__ labels, int64_t n_chunks, int H, int 
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_chunks) return;
     const int64_t row = c / chunks_per_row;                       // = t * H + y
-    const int x0 = (int)(c - row * chunks_per_row) * LF_RUN;
+    const int x0 = (int)(c - row * chunks_per_row) * LR_ROW_RUN;
     const int t = (int)(row / H);
-    const int m = min(LF_RUN, W - x0);
+    const int m = min(LR_ROW_RUN, W - x0);
     const int64_t base = row * W + x0;
     const int32_t *L = labels + base;
-    int32_t v[LF_RUN];
-    if (ALIGNED && m == LF_RUN) {
+    int32_t v[LR_ROW_RUN];
+    if (ALIGNED && m == LR_ROW_RUN) {
 #pragma unroll
-        for (int q = 0; q < LF_RUN / 4; q++) {
+        for (int q = 0; q < LR_ROW_RUN / 4; q++) {
             const int4 w4 = ((const int4 *)L)[q];
             v[4 * q] = w4.x; v[4 * q + 1] = w4.y; v[4 * q + 2] = w4.z; v[4 * q + 3] = w4.w;
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < LF_RUN; j++) v[j] = j < m ? L[j] : 0;
+        for (int j = 0; j < LR_ROW_RUN; j++) v[j] = j < m ? L[j] : 0;
     }
     int32_t any = 0;
 #pragma unroll
-    for (int j = 0; j < LF_RUN; j++) any |= v[j];
+    for (int j = 0; j < LR_ROW_RUN; j++) any |= v[j];
     if (any == 0) return;                                         // background costs nothing
 
     const int all = (1 << a.n) - 1;
@@ -83,7 +85,7 @@ k_label_filter(const int32_t *__restrict__ labels, int64_t n_chunks, int H, int 
         if (found & ~known) atomicOr(&r[2], found);
     };
 #pragma unroll
-    for (int j = 0; j < LF_RUN; j++) {
+    for (int j = 0; j < LR_ROW_RUN; j++) {
         const int32_t l = v[j];
         if (l != cur) {
             flush();
@@ -106,11 +108,12 @@ extern "C" int tf_label_filter(const int32_t *labels, int64_t T, int64_t H, int6
                                const tf_label_criterion *criteria, int n_criteria, int32_t *records, void *stream)
 {
     TF_REQUIRE(labels && records, "tf_label_filter: null pointer");
-    TF_REQUIRE((((uintptr_t)records) & 15) == 0, "tf_label_filter: records must be 16-byte aligned");
+    TF_REQUIRE(lr_aligned16(records), "tf_label_filter: records must be 16-byte aligned");
     TF_REQUIRE(n_labels >= 0 && n_labels < 0x7fffffffll, "tf_label_filter: n_labels out of range");
     TF_REQUIRE(n_criteria >= 0 && n_criteria <= LF_MAX, "tf_label_filter: 0 to 8 criteria");
     TF_REQUIRE(criteria || n_criteria == 0, "tf_label_filter: null criteria");
-    TF_REQUIRE(T > 0 && T < 65536 && H > 0 && W > 0 && H <= 0x7fffffff && W <= 0x7fffffff - LF_RUN, "tf_label_filter: bad shape");
+    LrRowGrid g;
+    if (const char *bad = lr_row_grid(labels, T, H, W, &g)) { tf_set_error("tf_label_filter: %s", bad); return TF_EINVAL; }
     LfArgs a;
     a.n = n_criteria;
     for (int k = 0; k < LF_MAX; k++) a.c[k] = LfCrit{nullptr, TF_U8, TF_CMP_GE, 0.0f, 0.0};
@@ -125,15 +128,11 @@ extern "C" int tf_label_filter(const int32_t *labels, int64_t T, int64_t H, int6
     }
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_ids = n_labels + 1;
-    const int64_t cpr = (W + LF_RUN - 1) / LF_RUN, n_chunks = T * H * cpr, blocks = (n_chunks + 255) / 256;
-    TF_REQUIRE(blocks <= 0x7fffffffll, "tf_label_filter: volume too large for one launch");
     hipLaunchKernelGGL(k_label_filter_init, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, s, (int4 *)records, n_ids);
     TF_CHECK_LAUNCH();
     if (n_labels == 0) return TF_OK;
-    if ((((uintptr_t)labels) & 15) == 0 && W % 4 == 0)
-        hipLaunchKernelGGL(k_label_filter<true>, dim3((unsigned)blocks), dim3(256), 0, s, labels, n_chunks, (int)H, (int)W, (int)cpr, n_labels, a, records);
-    else
-        hipLaunchKernelGGL(k_label_filter<false>, dim3((unsigned)blocks), dim3(256), 0, s, labels, n_chunks, (int)H, (int)W, (int)cpr, n_labels, a, records);
+    hipLaunchKernelGGL(g.aligned ? k_label_filter<true> : k_label_filter<false>, dim3(g.blocks), dim3(256), 0, s, labels, g.n_chunks,
+                       (int)H, (int)W, g.chunks_per_row, n_labels, a, records);
     TF_CHECK_LAUNCH();
     return TF_OK;
 }

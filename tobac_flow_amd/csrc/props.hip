@@ -11,18 +11,16 @@
 // only, so nothing of the volume's size is read besides the labels (4 B per voxel) and nothing of that size is allocated:
 // the reference's np.repeat stacks never exist.  The (H, W) planes are read only under labelled voxels.
 #include "tf_common.h"
+#include "label_runs.h"
 #include <algorithm>
 
 // ---- tf_label_props ------------------------------------------------------------------------------------------------
-// One lane takes PR_RUN consecutive voxels of ONE row (a run never straddles a row: y and the plane index change there)
-// and issues one set of atomics per run of equal labels inside them (labels are spatially coherent, and most lanes see
-// background only and leave without an atomic).  Runs are merged per lane, not across the wave: a wave's 64 lanes cover
-// 1024 voxels of a row, a merge across them saves atomics only for regions wider than 16 voxels and costs a segmented
-// scan of seven doubles per lane on every wave, labelled or not.
+// The row-chunk layout and walker of label_runs.h (lr_walk_row): one lane takes LR_ROW_RUN consecutive voxels of one row
+// and issues one set of atomics per run of equal labels inside them; why runs are not merged across the wave is said
+// there (here the scan would carry seven doubles per lane).
 // Record per label id (PR_REC doubles = 64 B, so one label's atomics fall into one 64-B line):
 //   0 count (int64)  1 sum area (NaN skipped)  2 sum area  3 sum area*x  4 sum area*y  5 sum area*lat  6 sum area*lon
 //   7 {tmin, tmax} (two int32)
-#define PR_RUN 16
 #define PR_REC 8
 
 struct PrIn { const double *area, *x, *y, *lat, *lon; const int32_t *t_rank; };
@@ -38,41 +36,38 @@ k_props_init(double *__restrict__ acc, int64_t n_ids)
     tm[0] = 0x7fffffff; tm[1] = -1;
 }
 
-template <bool ALIGNED>
-__global__ void __launch_bounds__(256)
-k_label_props(const int32_t *__restrict__ labels, int64_t n_chunks, int H, int W, int chunks_per_row, int64_t n_labels,
-              PrIn in, double *acc)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_chunks) return;
-    const int64_t row = c / chunks_per_row;                       // = t * H + y
-    const int x0 = (int)(c - row * chunks_per_row) * PR_RUN;
-    const int t = (int)(row / H), y = (int)(row - (int64_t)t * H);
-    const int m = min(PR_RUN, W - x0);
-    const int32_t *L = labels + row * W + x0;
-    int32_t v[PR_RUN];
-    if (ALIGNED && m == PR_RUN) {
-#pragma unroll
-        for (int q = 0; q < PR_RUN / 4; q++) {
-            const int4 w4 = ((const int4 *)L)[q];
-            v[4 * q] = w4.x; v[4 * q + 1] = w4.y; v[4 * q + 2] = w4.z; v[4 * q + 3] = w4.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < PR_RUN; j++) v[j] = j < m ? L[j] : 0;
-    }
-    int32_t any = 0;
-#pragma unroll
-    for (int j = 0; j < PR_RUN; j++) any |= v[j];
-    if (any == 0) return;                                         // background costs nothing
-
-    const bool has_loc = in.x || in.y || in.lat || in.lon;
-    const int64_t prow = (int64_t)y * W;
-    const double yv = in.y ? in.y[y] : 0.0;
-    const int rank = in.t_rank ? in.t_rank[t] : 0;
-    int32_t cur = 0; unsigned long long cnt = 0;
+struct PrRun {
+    const PrIn in; int W; double *acc;
+    bool has_loc; int64_t p0; int x0, rank; double yv;         // of the chunk: p0 = its first pixel of the (H, W) planes
+    unsigned long long cnt = 0;
     double an = 0, sw = 0, sx = 0, sy = 0, slat = 0, slon = 0;
-    auto flush = [&]() {
+
+    __device__ __forceinline__ void begin(int t, int y, int x0_)
+    {
+        has_loc = in.x || in.y || in.lat || in.lon;
+        x0 = x0_; p0 = (int64_t)y * W + x0_;
+        yv = in.y ? in.y[y] : 0.0;
+        rank = in.t_rank ? in.t_rank[t] : 0;
+    }
+    __device__ __forceinline__ bool ends(int) const { return false; }
+    __device__ __forceinline__ void open(int32_t, bool, int) { cnt = 0; an = sw = sx = sy = slat = slon = 0; }
+    __device__ __forceinline__ void add(int64_t, int j)
+    {
+        cnt++;
+        if (!in.area) return;
+        const int64_t p = p0 + j;
+        const double a = in.area[p];
+        if (!(a != a)) an += a;
+        sw += a;
+        if (has_loc) {
+            if (in.x) sx += a * in.x[x0 + j];
+            if (in.y) sy += a * yv;
+            if (in.lat) slat += a * in.lat[p];
+            if (in.lon) slon += a * in.lon[p];
+        }
+    }
+    __device__ __forceinline__ void close(int32_t cur)
+    {
         if (!cnt) return;                                         // cur is in [1, n_labels] whenever cnt != 0
         double *r = acc + PR_REC * (int64_t)cur;
         atomicAdd((unsigned long long *)r, cnt);
@@ -89,29 +84,17 @@ k_label_props(const int32_t *__restrict__ labels, int64_t n_chunks, int H, int W
             if (tm[0] > rank) atomicMin(&tm[0], rank);
             if (tm[1] < rank) atomicMax(&tm[1], rank);
         }
-    };
-#pragma unroll
-    for (int j = 0; j < PR_RUN; j++) {
-        const int32_t l = v[j];
-        if (l != cur) {
-            flush();
-            cur = l; cnt = 0; an = sw = sx = sy = slat = slon = 0;
-        }
-        if (l < 1 || l > n_labels) continue;
-        cnt++;
-        if (!in.area) continue;
-        const int64_t p = prow + x0 + j;
-        const double a = in.area[p];
-        if (!(a != a)) an += a;
-        sw += a;
-        if (has_loc) {
-            if (in.x) sx += a * in.x[x0 + j];
-            if (in.y) sy += a * yv;
-            if (in.lat) slat += a * in.lat[p];
-            if (in.lon) slon += a * in.lon[p];
-        }
+        cnt = 0;
     }
-    flush();
+};
+
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256)
+k_label_props(const int32_t *__restrict__ labels, int64_t n_chunks, int H, int W, int chunks_per_row, int64_t n_labels,
+              PrIn in, double *acc)
+{
+    PrRun v{in, W, acc};
+    lr_walk_row<ALIGNED>((int64_t)blockIdx.x * blockDim.x + threadIdx.x, labels, n_chunks, H, W, chunks_per_row, n_labels, v);
 }
 
 extern "C" int tf_label_props(const int32_t *labels, int64_t T, int64_t H, int64_t W, int64_t n_labels,
@@ -119,19 +102,16 @@ extern "C" int tf_label_props(const int32_t *labels, int64_t T, int64_t H, int64
                               const int32_t *t_rank, double *acc, void *stream)
 {
     TF_REQUIRE(labels && acc && n_labels >= 0, "tf_label_props: bad arguments");
-    TF_REQUIRE(T > 0 && T < 65536 && H > 0 && W > 0 && H <= 0x7fffffff && W <= 0x7fffffff - PR_RUN, "tf_label_props: bad shape");
+    LrRowGrid g;
+    if (const char *bad = lr_row_grid(labels, T, H, W, &g)) { tf_set_error("tf_label_props: %s", bad); return TF_EINVAL; }
     TF_REQUIRE(area || !(x || y || lat || lon), "tf_label_props: x, y, lat and lon are weighted by area");
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_ids = n_labels + 1;
     hipLaunchKernelGGL(k_props_init, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, s, acc, n_ids);
     TF_CHECK_LAUNCH();
-    const int64_t cpr = (W + PR_RUN - 1) / PR_RUN, n_chunks = T * H * cpr, blocks = (n_chunks + 255) / 256;
-    TF_REQUIRE(blocks <= 0x7fffffffll, "tf_label_props: volume too large for one launch");
     const PrIn in{area, x, y, lat, lon, t_rank};
-    if ((((uintptr_t)labels) & 15) == 0 && W % 4 == 0)
-        hipLaunchKernelGGL(k_label_props<true>, dim3((unsigned)blocks), dim3(256), 0, s, labels, n_chunks, (int)H, (int)W, (int)cpr, n_labels, in, acc);
-    else
-        hipLaunchKernelGGL(k_label_props<false>, dim3((unsigned)blocks), dim3(256), 0, s, labels, n_chunks, (int)H, (int)W, (int)cpr, n_labels, in, acc);
+    hipLaunchKernelGGL(g.aligned ? k_label_props<true> : k_label_props<false>, dim3(g.blocks), dim3(256), 0, s, labels, g.n_chunks,
+                       (int)H, (int)W, g.chunks_per_row, n_labels, in, acc);
     TF_CHECK_LAUNCH();
     return TF_OK;
 }

@@ -12,6 +12,7 @@
 // ties): one correctly rounded square root of the integer d2, one of count / pi, one division, each written as such and
 // compiled with -ffp-contract=off and without fast-math (no reciprocal, no fused step).
 #include "tf_common.h"
+#include "label_runs.h"                                           // lr_aligned16
 
 #define SUBSEG_PI 3.141592653589793                              // np.pi
 #define SUBSEG_MAX_BLOCKS ((int64_t)1 << 20)                     // grid-stride beyond that
@@ -72,15 +73,13 @@ static unsigned subseg_blocks(int64_t work)
     return (unsigned)(blocks < 1 ? 1 : (blocks < SUBSEG_MAX_BLOCKS ? blocks : SUBSEG_MAX_BLOCKS));
 }
 
-static bool subseg_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 extern "C" int tf_subseg_prepare(const int32_t *labels, const int32_t *d2, const int64_t *counts, int64_t n_labels, int64_t n,
                                  double shrink_factor, double *dist_mask, uint8_t *shrunk, void *stream)
 {
     TF_REQUIRE(labels && d2 && counts && dist_mask && shrunk, "tf_subseg_prepare: bad arguments");
     TF_REQUIRE(n > 0 && n_labels >= 0 && n_labels <= 0x7fffffffll, "tf_subseg_prepare: bad shape or label count");
     TF_REQUIRE(shrink_factor == shrink_factor, "tf_subseg_prepare: shrink_factor is NaN");
-    const bool vec = subseg_aligned16(labels) && subseg_aligned16(d2) && subseg_aligned16(dist_mask) && (((uintptr_t)shrunk) & 3) == 0;
+    const bool vec = lr_aligned16(labels) && lr_aligned16(d2) && lr_aligned16(dist_mask) && (((uintptr_t)shrunk) & 3) == 0;
     hipLaunchKernelGGL(k_subseg_prepare, dim3(subseg_blocks(vec ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, labels, d2,
                        counts, n_labels, n, vec, shrink_factor, dist_mask, shrunk);
     TF_CHECK_LAUNCH();

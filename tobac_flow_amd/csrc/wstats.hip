@@ -8,7 +8,7 @@
 // The reference sorts the whole label volume (bincount + argsort) per call and runs a Python function per label; here a
 // call reads labels, field and weights twice (once for the proportions), the errors only under labelled voxels, and
 // writes a record per label.  Weights that the scripts build with np.repeat(area[None], T, 0) stay one (H, W) plane.
-// The kernel bodies and the work layout are in wstats_kernels.h.
+// The kernel bodies are in wstats_kernels.h, the work layout and the run walker they use in label_runs.h.
 #include "tf_common.h"
 #include "wstats_kernels.h"
 
@@ -55,8 +55,6 @@ k_wprop_finish(int64_t n_labels, int K, const double *__restrict__ acc, double *
     wp_finish_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n_labels, K, acc, out);
 }
 
-static bool ws_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 extern "C" size_t tf_label_wstats_workspace_bytes(int64_t n_labels)
 {
     if (n_labels <= 0) return 0;
@@ -67,10 +65,10 @@ template <typename F>
 static int ws_run(const int32_t *labels, const F *x, const F *e, const F *w, int64_t n, int64_t hw, bool plane,
                   int64_t n_labels, double *out, double *acc, hipStream_t s)
 {
-    const int64_t blocks = (n + WS_BLOCK - 1) / WS_BLOCK, id_blocks = (n_labels + 255) / 256;
+    const int64_t blocks = (n + LR_BLOCK - 1) / LR_BLOCK, id_blocks = (n_labels + 255) / 256;
     TF_REQUIRE(blocks <= 0x7fffffffll && id_blocks <= 0x7fffffffll, "tf_label_wstats: volume too large for one launch");
-    const bool vec = ws_aligned16(labels) && ws_aligned16(x) && (!e || ws_aligned16(e));
-    const bool vec_w = ws_aligned16(w) && (!plane || hw % WS_VEC == 0);      // then i % hw keeps the alignment of i
+    const bool vec = lr_aligned16(labels) && lr_aligned16(x) && (!e || lr_aligned16(e));
+    const bool vec_w = lr_aligned16(w) && (!plane || hw % LR_VEC == 0);      // then i % hw keeps the alignment of i
     hipLaunchKernelGGL(k_wstats_init, dim3((unsigned)id_blocks), dim3(256), 0, s, n_labels, acc);
     TF_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_wstats_pass1<F>, dim3((unsigned)blocks), dim3(256), 0, s, labels, x, e, w, n, hw, plane, vec, vec_w, n_labels, acc);
@@ -123,11 +121,11 @@ extern "C" int tf_label_proportions(const int32_t *labels, const int32_t *flags,
     double *acc = ar.take<double>(cells);
     if (!ar.ok()) { tf_set_error("tf_label_proportions: workspace too small"); return TF_ENOMEM; }
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n = T * hw, blocks = (n + WS_BLOCK - 1) / WS_BLOCK, id_blocks = (n_labels + 255) / 256;
+    const int64_t n = T * hw, blocks = (n + LR_BLOCK - 1) / LR_BLOCK, id_blocks = (n_labels + 255) / 256;
     TF_REQUIRE(blocks <= 0x7fffffffll, "tf_label_proportions: volume too large for one launch");
     const bool plane = weights_plane != 0;
-    const bool vec = ws_aligned16(labels) && ws_aligned16(flags);
-    const bool vec_w = ws_aligned16(weights) && (!plane || hw % WS_VEC == 0);
+    const bool vec = lr_aligned16(labels) && lr_aligned16(flags);
+    const bool vec_w = lr_aligned16(weights) && (!plane || hw % LR_VEC == 0);
     TF_CHECK_HIP(hipMemsetAsync(acc, 0, cells * sizeof(double), s));
     hipLaunchKernelGGL(k_wprop_pass, dim3((unsigned)blocks), dim3(256), 0, s, labels, flags, weights, n, hw, plane, vec, vec_w, n_labels, fl, acc);
     TF_CHECK_LAUNCH();

@@ -24,6 +24,7 @@
 
 #define __host__
 #define __device__
+#define __forceinline__ inline
 #define __restrict__
 struct int4 { int32_t x, y, z, w; };
 struct float4 { float x, y, z, w; };
@@ -46,7 +47,7 @@ template <typename E> struct Buf {                                 // exactly-si
 
 static void run_all_lanes(const TfBinPoints &P)
 {
-    const int64_t blocks = (P.n_points + BN_BLOCK - 1) / BN_BLOCK;
+    const int64_t blocks = (P.n_points + LR_BLOCK - 1) / LR_BLOCK;
     for (int64_t b = 0; b < blocks; b++)
         for (int t = 0; t < 256; t++) {
             if (P.coord_dtype == TF_F32) bn_points_body<float>(b, t, P); else bn_points_body<double>(b, t, P);

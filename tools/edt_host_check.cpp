@@ -22,6 +22,7 @@
 
 #define __host__
 #define __device__
+#define __forceinline__ inline
 #define __restrict__
 struct int4 { int32_t x, y, z, w; };
 struct float4 { float x, y, z, w; };
@@ -40,7 +41,6 @@ template <typename E> struct Buf {                                 // exactly-si
     std::vector<E> store; E *p;
     Buf(const std::vector<E> &v, int shift) : store(v.size() + shift), p(nullptr) { if (!v.empty()) std::memcpy(store.data() + shift, v.data(), v.size() * sizeof(E)); p = store.data() + shift; }
 };
-static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 // the volumes of tests/validation_cases.py in spirit: labelled boxes with two empty frames; features in the corners and
 // along the borders of a row longer than a workgroup; one feature in a corner and a frame of features; degenerate axes
@@ -182,13 +182,13 @@ static void nanmin_case(int64_t n, int shift, unsigned seed)
         if (lab[(size_t)i] == 7) lab[(size_t)i] = 0;                                    // ... and one that is absent
     }
     Buf<int32_t> L(lab, shift ? 1 : 0); Buf<F> X(x, shift ? 1 : 0);
-    const bool vec = aligned16(L.p) && aligned16(X.p);
+    const bool vec = lr_aligned16(L.p) && lr_aligned16(X.p);
     std::vector<unsigned long long> acc((size_t)n_labels * LM_REC);
     const std::vector<int64_t> ids = {3, 7, 1, 12, 4, 5, 9, 2, 0, 6, 8};
     std::vector<double> mn(ids.size());
     std::vector<int64_t> cnt(ids.size());
     for (int64_t l = 0; l < 256; l++) lm_init_body(l, n_labels, acc.data());
-    for (int64_t b = 0; b < (n + WS_BLOCK - 1) / WS_BLOCK; b++) for (int t = 0; t < 256; t++) lm_pass_body<F>(b, t, L.p, X.p, n, vec, n_labels, acc.data());
+    for (int64_t b = 0; b < (n + LR_BLOCK - 1) / LR_BLOCK; b++) for (int t = 0; t < 256; t++) lm_pass_body<F>(b, t, L.p, X.p, n, vec, n_labels, acc.data());
     for (int64_t k = 0; k < 256; k++) lm_finish_body(k, (int64_t)ids.size(), ids.data(), n_labels, acc.data(), mn.data(), cnt.data());
     for (size_t k = 0; k < ids.size(); k++) {
         double want = NAN; int64_t all = 0, good = 0;
@@ -229,7 +229,7 @@ int main()
     // the largest frame the entry point admits: the arithmetic of the scan stays inside its types
     const int64_t side = 32768;
     CHECK((side - 1) * (side - 1) * 2 < (1ll << 31) && (uint64_t)(side - 1) * (side - 1) + (uint32_t)EDT_NONE < (1ull << 32));
-    CHECK(ws_key(INFINITY) < LM_ALLNAN && LM_ALLNAN < WS_NONE);
+    CHECK(lr_key(INFINITY) < LM_ALLNAN && LM_ALLNAN < LR_NONE);
     printf(failures ? "%d FAILURES\n" : "edt host check: all equal (%d failures)\n", failures);
     return failures != 0;
 }

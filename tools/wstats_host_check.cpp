@@ -1,5 +1,6 @@
-// Host check of the kernel bodies of tobac_flow_amd/csrc/wstats_kernels.h: the same text compiled for the CPU, run lane
-// after lane on exactly-sized heap buffers against plain loops, meant for AddressSanitizer + UBSan:
+// Host check of the kernel bodies of tobac_flow_amd/csrc/wstats_kernels.h and of the raveled walker of label_runs.h under
+// them: the same text compiled for the CPU, run lane after lane on exactly-sized heap buffers against plain loops, meant
+// for AddressSanitizer + UBSan:
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/wstats_host_check.cpp -o wstats_host_check
 //   ./wstats_host_check
@@ -18,6 +19,7 @@
 
 #define __host__
 #define __device__
+#define __forceinline__ inline
 #define __restrict__
 struct int4 { int32_t x, y, z, w; };
 struct float4 { float x, y, z, w; };
@@ -44,7 +46,6 @@ template <typename E> struct Buf {
     std::vector<E> store; E *p;
     Buf(const std::vector<E> &v, int shift) : store(v.size() + shift), p(nullptr) { if (!v.empty()) std::memcpy(store.data() + shift, v.data(), v.size() * sizeof(E)); p = store.data() + shift; }
 };
-static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 template <typename F>
 static void stats_case(int64_t T, int64_t hw, bool plane, bool with_e, int shift, unsigned seed)
@@ -64,10 +65,10 @@ static void stats_case(int64_t T, int64_t hw, bool plane, bool with_e, int shift
     for (int64_t i = 0; i < n; i++) if (lab[i] == 4) { w[plane ? i % hw : i] = NAN; break; }   // one label poisoned
     Buf<int32_t> L(lab, shift ? 1 : 0); Buf<F> X(x, shift ? 1 : 0), E(e, shift ? 1 : 0), W(w, shift ? 1 : 0);
     const F *ep = with_e ? E.p : nullptr;
-    const bool vec = aligned16(L.p) && aligned16(X.p) && (!ep || aligned16(ep));
-    const bool vec_w = aligned16(W.p) && (!plane || hw % WS_VEC == 0);
+    const bool vec = lr_aligned16(L.p) && lr_aligned16(X.p) && (!ep || lr_aligned16(ep));
+    const bool vec_w = lr_aligned16(W.p) && (!plane || hw % LR_VEC == 0);
     std::vector<double> acc((size_t)n_labels * WS_REC), out((size_t)n_labels * WS_OUT);
-    const int64_t blocks = (n + WS_BLOCK - 1) / WS_BLOCK;
+    const int64_t blocks = (n + LR_BLOCK - 1) / LR_BLOCK;
     for (int64_t l = 0; l < (n_labels + 255) / 256 * 256; l++) ws_init_body(l, n_labels, acc.data());
     for (int64_t b = 0; b < blocks; b++) for (int t = 0; t < 256; t++) ws_pass1_body<F>(b, t, L.p, X.p, ep, W.p, n, hw, plane, vec, vec_w, n_labels, acc.data());
     for (int64_t b = 0; b < blocks; b++) for (int t = 0; t < 256; t++) ws_pass2_body<F>(b, t, L.p, X.p, W.p, n, hw, plane, vec, vec_w, n_labels, acc.data());
@@ -110,9 +111,9 @@ static void proportions_case(int64_t T, int64_t hw, bool plane, int shift, unsig
     for (auto &v : w) { const int r = rng() % 20; v = r == 0 ? NAN : r == 1 ? 0.f : (float)(1 + rng() % 7) / 4.f; }
     for (int64_t i = 0; i < n; i++) if (lab[i] == 3) w[plane ? i % hw : i] = 0.f;                           // a label without weight
     Buf<int32_t> L(lab, shift ? 1 : 0), G(flag, shift ? 1 : 0); Buf<float> W(w, shift ? 1 : 0);
-    const bool vec = aligned16(L.p) && aligned16(G.p), vec_w = aligned16(W.p) && (!plane || hw % WS_VEC == 0);
+    const bool vec = lr_aligned16(L.p) && lr_aligned16(G.p), vec_w = lr_aligned16(W.p) && (!plane || hw % LR_VEC == 0);
     std::vector<double> acc((size_t)n_labels * (1 + fl.k), 0.0), out((size_t)n_labels * fl.k);
-    for (int64_t b = 0; b < (n + WS_BLOCK - 1) / WS_BLOCK; b++) for (int t = 0; t < 256; t++) wp_pass_body(b, t, L.p, G.p, W.p, n, hw, plane, vec, vec_w, n_labels, fl, acc.data());
+    for (int64_t b = 0; b < (n + LR_BLOCK - 1) / LR_BLOCK; b++) for (int t = 0; t < 256; t++) wp_pass_body(b, t, L.p, G.p, W.p, n, hw, plane, vec, vec_w, n_labels, fl, acc.data());
     for (int64_t l = 0; l < 256; l++) wp_finish_body(l, n_labels, fl.k, acc.data(), out.data());
     for (int64_t id = 1; id <= n_labels; id++) {
         double tot = 0, part[3] = {0, 0, 0};
@@ -142,31 +143,31 @@ int main()
                 }
     // indices beyond 2^32 through the index arithmetic only: 160 x 5424^2 = 4.7e9 voxels (144 frames, one day of full-disk
     // images, are 4.24e9: beyond int32, just short of 2^32)
-    const int64_t hw = 5424ll * 5424, n = 160 * hw, blocks = (n + WS_BLOCK - 1) / WS_BLOCK;
+    const int64_t hw = 5424ll * 5424, n = 160 * hw, blocks = (n + LR_BLOCK - 1) / LR_BLOCK;
     CHECK(n > (1ll << 32) && blocks <= 0x7fffffffll);
-    CHECK(ws_first_voxel(0, 0, 0) == 0 && ws_first_voxel(0, 63, 0) == 252 && ws_first_voxel(0, 0, 1) == 256 && ws_first_voxel(0, 64, 0) == 1024);
-    CHECK(ws_first_voxel(blocks - 1, 255, WS_ITERS - 1) == (blocks - 1) * 4096 + 4092);
-    CHECK(ws_first_voxel(blocks - 1, 0, 0) < n && ws_first_voxel(blocks, 0, 0) >= n);
+    CHECK(lr_first_voxel(0, 0, 0) == 0 && lr_first_voxel(0, 63, 0) == 252 && lr_first_voxel(0, 0, 1) == 256 && lr_first_voxel(0, 64, 0) == 1024);
+    CHECK(lr_first_voxel(blocks - 1, 255, LR_ITERS - 1) == (blocks - 1) * 4096 + 4092);
+    CHECK(lr_first_voxel(blocks - 1, 0, 0) < n && lr_first_voxel(blocks, 0, 0) >= n);
     {   // every voxel of a range around 2^32 and around the end of the volume is covered exactly once
-        for (int64_t b : {(int64_t)((1ll << 32) / WS_BLOCK - 1), (int64_t)((1ll << 32) / WS_BLOCK), blocks - 1}) {
-            std::vector<int> hit(WS_BLOCK, 0);
-            for (int t = 0; t < 256; t++) for (int k = 0; k < WS_ITERS; k++) {
-                const int64_t i = ws_first_voxel(b, t, k);
-                CHECK(i % WS_VEC == 0 && i >= b * WS_BLOCK && i + WS_VEC <= (b + 1) * WS_BLOCK);
-                for (int j = 0; j < WS_VEC; j++) hit[i + j - b * WS_BLOCK]++;
+        for (int64_t b : {(int64_t)((1ll << 32) / LR_BLOCK - 1), (int64_t)((1ll << 32) / LR_BLOCK), blocks - 1}) {
+            std::vector<int> hit(LR_BLOCK, 0);
+            for (int t = 0; t < 256; t++) for (int k = 0; k < LR_ITERS; k++) {
+                const int64_t i = lr_first_voxel(b, t, k);
+                CHECK(i % LR_VEC == 0 && i >= b * LR_BLOCK && i + LR_VEC <= (b + 1) * LR_BLOCK);
+                for (int j = 0; j < LR_VEC; j++) hit[i + j - b * LR_BLOCK]++;
                 CHECK(i % hw == (int64_t)((unsigned long long)i % (unsigned long long)hw));
             }
             CHECK(std::all_of(hit.begin(), hit.end(), [](int h) { return h == 1; }));
         }
-        unsigned long long slot = WS_NONE;                          // the index minimum is a 64-bit one
+        unsigned long long slot = LR_NONE;                          // the index minimum is a 64-bit one
         atomicMin(&slot, (unsigned long long)(n - 1)); atomicMin(&slot, (1ull << 32) + 5); atomicMin(&slot, (1ull << 33));
         CHECK(slot == (1ull << 32) + 5);
     }
     // keys: order-preserving over finite doubles, one key for both zeros
     const double vals[] = {-1e300, -2.5, -1e-310, -0.0, 0.0, 1e-310, 1.0, 3.5, 1e300};
     for (size_t a = 0; a + 1 < sizeof vals / sizeof *vals; a++)
-        CHECK(vals[a] == vals[a + 1] ? ws_key(vals[a]) == ws_key(vals[a + 1]) : ws_key(vals[a]) < ws_key(vals[a + 1]));
-    CHECK(ws_key(-1e300) > 0 && ws_key(1e300) < WS_NONE);
+        CHECK(vals[a] == vals[a + 1] ? lr_key(vals[a]) == lr_key(vals[a + 1]) : lr_key(vals[a]) < lr_key(vals[a + 1]));
+    CHECK(lr_key(-1e300) > 0 && lr_key(1e300) < LR_NONE);
     printf(failures ? "%d FAILURES\n" : "wstats host check: all equal (%d failures)\n", failures);
     return failures != 0;
 }
