@@ -48,6 +48,8 @@ extern "C" {
 #define TF_F64 1
 #define TF_I32 2
 #define TF_U8 3          /* tf_edt2d_frames, tf_label_nanmin, tf_label_filter only (bool arrays have these bytes) */
+#define TF_I16 4         /* tf_prepare_fields only: a packed channel */
+#define TF_I8 5          /* tf_stripe_deviation, tf_prepare_fields only: a DQF plane */
 
 /* reductions over the gathered (n_struct, H, W) stack, i.e. the `func` argument of
  * tobac_flow/convolve.py:248-348 for the callables the reference itself passes */
@@ -850,6 +852,71 @@ typedef struct TfBinPoints {
     uint32_t *status;
 } TfBinPoints;
 int tf_bin_points(const TfBinPoints *params_host, void *stream);
+
+/* ---- bt, wvd and swd from raw channel stacks (version 109) -------------------------------------------------------------
+ * The array-level work under the reference's loaders: load_mcmip (tobac_flow/dataloader.py:240-321), seviri_dataloader
+ * (:588-688), seviri_nat_dataloader (:833-958), get_stripe_deviation (:234-237), fill_time_gap_nan (:341-357) and the
+ * dropped frames of goes_dataloader:78-94.  The file decoders stay on the host; what they hand out goes in as it is.
+ *
+ * TfFieldPlane: one (T, H, W) operand with x contiguous; frame_stride and row_stride in ELEMENTS (row_stride >= W,
+ *   frame_stride >= row_stride), so a [y0:y1, x0:x1] cut of full frames needs no copy.  `data` is aligned to its element.
+ *   A channel is TF_F32 -- NaN and +-inf mean missing -- or TF_I16, packed: the stored bits are read as int16, or as uint16
+ *   with is_unsigned (GOES CMI is _Unsigned); `fill` is the fill value in the stored type (0 .. 65535 for unsigned) and
+ *   counts only with has_fill.  CF decoding: stored == fill gives NaN, anything else
+ *   (float)stored * scale + offset with two float32 roundings, never a fused multiply-add.  All channels of a call have
+ *   one dtype.  A DQF plane is TF_I8 or TF_U8 with an optional fill of its own; scale, offset, is_unsigned are ignored.
+ *
+ * tf_stripe_deviation: get_stripe_deviation of ONE DQF plane under xarray's skipna rule, a fill being NaN.  Per frame:
+ *   m[x] = nanmean over y, s[x] = nanstd over y (ddof 0), dev[y] = |nanmean over x of (D[y, x] - m[x]) / (s[x] + 1e-8)|,
+ *   all in float64; a row without a valid term has dev = NaN.  The count and sum D of the valid elements of a column are
+ *   exact integers from integer atomics, so m = sum D / n is np.nanmean's value bit for bit; s is np.nanstd's own second
+ *   pass, (D - m)^2 added down the column in row order, / n, sqrt: NumPy's value bit for bit as well.  The row sum runs in
+ *   float64 in a fixed order without floating-point atomics: dev is identical from run to run and differs from NumPy's
+ *   pairwise row mean by the summation order only, within (W + 4) 2^-53 mean_x |term| per row.  dev (T, H), optional: written.  row_flags (T, H) bytes, optional: 1 is
+ *   stored where dev > threshold (2 in the reference), nothing elsewhere -- the caller zeroes the table once and runs its
+ *   planes one after another on one stream, which ORs them without an atomic.  T <= 65535, H < 2^24, H W < 2^31.
+ *   ws_bytes < tf_stripe_workspace_bytes(T, H, W): TF_ENOMEM.
+ *
+ * tf_prepare_fields: up to TF_FIELD_MAX_RECIPES outputs, contiguous float32 (T_out, H, W).  Output r is channel[a], or
+ *   channel[a] - channel[b] with one float32 rounding (b = -1: none), then with has_floor np.maximum(x, floor) (NaN stays
+ *   NaN).  Output frame k is made from input frame src[k] (int32[T_out] on the device); src[k] < 0 or >= T is an all-NaN
+ *   frame: dropping, sorting and gap filling cost no pass of their own.  A voxel is bad, and EVERY output is NaN there, when
+ *   any output is non-finite there (infinities count), any of the n_dqf planes is non-zero or equals its fill there, or
+ *   row_flags[src[k] * H + y] (optional, the table of tf_stripe_deviation) is set.  n_masked (int32[T_out], optional):
+ *   written, the number of NaN voxels of each output frame, exact (one integer atomic per workgroup).
+ *   flags = TF_FIELD_COPY: no mask at all -- every output keeps the values of its recipe, infinities included, and only
+ *   the frame table acts (fill_time_gap_nan of a finished field); n_dqf = 0, row_flags and n_masked NULL.
+ * Bad arguments are TF_EINVAL before any launch. */
+#define TF_FIELD_MAX_CHANNELS 8
+#define TF_FIELD_MAX_DQF 8
+#define TF_FIELD_MAX_RECIPES 4
+#define TF_FIELD_COPY 1
+typedef struct TfFieldPlane {
+    const void *data;
+    int64_t frame_stride, row_stride;
+    int32_t dtype, has_fill, is_unsigned, fill;
+    float scale, offset;
+} TfFieldPlane;
+typedef struct TfFieldRecipe {
+    int32_t a, b, has_floor;
+    float floor;
+    float *out;
+} TfFieldRecipe;
+typedef struct TfFieldPrep {
+    int64_t T, H, W, T_out;
+    int32_t n_channels, n_dqf, n_recipes, flags;
+    TfFieldPlane channel[TF_FIELD_MAX_CHANNELS];
+    TfFieldPlane dqf[TF_FIELD_MAX_DQF];
+    TfFieldRecipe recipe[TF_FIELD_MAX_RECIPES];
+    const int32_t *src;
+    const uint8_t *row_flags;
+    int32_t *n_masked;
+} TfFieldPrep;
+size_t tf_stripe_workspace_bytes(int64_t T, int64_t H, int64_t W);
+int tf_stripe_deviation(const TfFieldPlane *dqf, int64_t T, int64_t H, int64_t W, double threshold,
+                        double *dev /* (T, H), optional */, uint8_t *row_flags /* (T, H), OR-ed into, optional */,
+                        void *ws, size_t ws_bytes, void *stream);
+int tf_prepare_fields(const TfFieldPrep *params_host, void *stream);
 
 /* ---- measurement aid (bench.py's roofline figure) ---------------------------------------------
  * tf_profile_enable(1): every kernel launch of the library is bracketed by HIP events on its own

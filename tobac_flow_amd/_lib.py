@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("TF_LIB_PATH") or os.path.join(_HERE, "csrc", "libtobac_flow_hip.so")
 
 INTERP = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos": 3}
-TF_F32, TF_F64, TF_I32, TF_U8 = 0, 1, 2, 3
+TF_F32, TF_F64, TF_I32, TF_U8, TF_I16, TF_I8 = 0, 1, 2, 3, 4, 5
 FUNC_STACK, FUNC_SOBEL, FUNC_SOBEL_UPHILL, FUNC_SOBEL_DOWNHILL, FUNC_NANMEAN, FUNC_DIFF, FUNC_ANY, FUNC_NANMAX = range(8)
 
 
@@ -44,6 +44,30 @@ class BinPoints(ctypes.Structure):
                 ("time", ctypes.c_void_p), ("win_start", ctypes.c_void_p), ("win_end", ctypes.c_void_p),
                 ("count", ctypes.c_void_p), ("count_v", ctypes.c_void_p), ("sum_w", ctypes.c_void_p),
                 ("sum_wv", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class FieldPlane(ctypes.Structure):
+    """TfFieldPlane of include/tobac_flow_hip.h"""
+    _fields_ = [("data", ctypes.c_void_p), ("frame_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("dtype", ctypes.c_int32), ("has_fill", ctypes.c_int32), ("is_unsigned", ctypes.c_int32),
+                ("fill", ctypes.c_int32), ("scale", ctypes.c_float), ("offset", ctypes.c_float)]
+
+
+class FieldRecipe(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_int32), ("b", ctypes.c_int32), ("has_floor", ctypes.c_int32), ("floor", ctypes.c_float),
+                ("out", ctypes.c_void_p)]
+
+
+FIELD_MAX_CHANNELS, FIELD_MAX_DQF, FIELD_MAX_RECIPES, FIELD_COPY = 8, 8, 4, 1
+
+
+class FieldPrep(ctypes.Structure):
+    """TfFieldPrep of include/tobac_flow_hip.h"""
+    _fields_ = [("T", ctypes.c_int64), ("H", ctypes.c_int64), ("W", ctypes.c_int64), ("T_out", ctypes.c_int64),
+                ("n_channels", ctypes.c_int32), ("n_dqf", ctypes.c_int32), ("n_recipes", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("channel", FieldPlane * FIELD_MAX_CHANNELS), ("dqf", FieldPlane * FIELD_MAX_DQF),
+                ("recipe", FieldRecipe * FIELD_MAX_RECIPES), ("src", ctypes.c_void_p), ("row_flags", ctypes.c_void_p),
+                ("n_masked", ctypes.c_void_p)]
 
 
 class LabelCriterion(ctypes.Structure):
@@ -172,6 +196,10 @@ _PROTOS = {
     "tf_subseg_prepare": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P]),
     "tf_subseg_rank": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P]),
     "tf_bin_points": (_c.c_int, [_c.POINTER(BinPoints), _P]),
+    "tf_stripe_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64]),
+    "tf_stripe_deviation": (_c.c_int, [_c.POINTER(FieldPlane), _c.c_int64, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P,
+                                       _c.c_size_t, _P]),
+    "tf_prepare_fields": (_c.c_int, [_c.POINTER(FieldPrep), _P]),
     "tf_slice_labels": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_pair_counts": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_sizes": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _P]),

@@ -12,7 +12,7 @@ void tf_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-extern "C" int tf_version(void) { return 108; }   // 101: tf_warp_offsets, tf_gather_offsets, tf_convolve_step; 102: tf_label_wstats, tf_label_proportions; 103: tf_edt2d_frames, tf_edt_cylinder, tf_label_nanmin; 104: tf_norm8_pair; 105: tf_edt_time_envelope; 106: tf_subseg_prepare, tf_subseg_rank; 107: tf_label_filter; 108: tf_bin_points
+extern "C" int tf_version(void) { return 109; }   // 101: tf_warp_offsets, tf_gather_offsets, tf_convolve_step; 102: tf_label_wstats, tf_label_proportions; 103: tf_edt2d_frames, tf_edt_cylinder, tf_label_nanmin; 104: tf_norm8_pair; 105: tf_edt_time_envelope; 106: tf_subseg_prepare, tf_subseg_rank; 107: tf_label_filter; 108: tf_bin_points; 109: tf_stripe_deviation, tf_prepare_fields
 extern "C" const char *tf_last_error(void) { return g_err; }
 extern "C" int tf_device_count(void) {
     int n = 0;
@@ -31,7 +31,8 @@ std::vector<Rec> g_recs;
 std::vector<hipEvent_t> g_free;
 std::mutex g_mu;
 const char *g_names[TFK_COUNT] = {"to8bit_pair", "fb_gaussian_blur", "fb_resize", "fb_polyexp", "fb_update_matrices",
-    "fb_blur_solve", "fb_iteration_fused", "smooth_flow", "convolve", "sobel", "ws_setup", "ws_relax_sweep", "ws_labels", "vr_prepare", "vr_system", "vr_sor", "binary_morph", "norm8_pair"};
+    "fb_blur_solve", "fb_iteration_fused", "smooth_flow", "convolve", "sobel", "ws_setup", "ws_relax_sweep", "ws_labels", "vr_prepare", "vr_system", "vr_sor", "binary_morph", "norm8_pair",
+    "stripe_columns", "stripe_rows", "prepare_fields"};
 hipEvent_t get_event() {
     if (!g_free.empty()) { hipEvent_t e = g_free.back(); g_free.pop_back(); return e; }
     hipEvent_t e; (void)hipEventCreate(&e); return e;
