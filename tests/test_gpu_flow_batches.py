@@ -520,3 +520,86 @@ def test_farneback_output_does_not_depend_on_the_workspace(kind, name):
     for fill in POISON:
         got = _fb_run(name, fr, B, H * W, 2 * H * W, kind=kind, parts=2, groups=((0, 2), (2, B)), fill=fill)
         _fb_same_as_pairs(got, name, H, W, B, f"{kind}, workspace filled with {fill}")
+
+
+# ----------------------------------------------------------------------------- 5. the reported workspace size is enough
+GUARD = 4096
+# (H, W, B, parameters away from the defaults)
+EXACT_CASES = [pytest.param(131, 140, 3, {}, id="131x140-B3-default"),                          # two pyramid levels, parts 2 + 1, fused
+               pytest.param(40, 47, 2, dict(pyr_scale=0.6, win_size=9), id="40x47-B2-scale06-win9"),   # no split; generic iteration with the M plane
+               # (47 * 0.6 < 32 px: 40 x 47 has level 0 only.  This one has a level 1 of 36 x 42, whose sampled blur rows -- 2 * 60 * 42
+               # floats -- are larger than the 60 * 70 plane)
+               pytest.param(60, 70, 2, dict(pyr_scale=0.6, win_size=9), id="60x70-B2-scale06-win9"),
+               pytest.param(33, 70, 1, {}, id="33x70-B1-default")]                              # one level
+
+
+class _GuardedWorkspace:
+    """`nbytes` of workspace with GUARD bytes of 0xA5 in front of it and behind it, in one allocation of the test's own: a
+    library that writes beyond the size it reported hits a guard band, not somebody else's memory"""
+
+    def __init__(self, nbytes, generous=False):
+        t = _torch()
+        self.nbytes = int(nbytes) * (4 if generous else 1)
+        self.buf = t.full((self.nbytes + 2 * GUARD,), 0xA5, dtype=t.uint8, device="cuda")
+        assert self.buf.data_ptr() % 256 == 0
+
+    def args(self):
+        return _at(self.buf, GUARD), self.nbytes
+
+    def intact(self):
+        return bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.nbytes:] == 0xA5).all())
+
+
+def _fb_guarded_run(p, fr, B, kind, generous=False):
+    """tf_farneback_batch / _split (parts 2) / _phase (1, then 2 for pairs 0 .. 1 and 2 .. B - 1) with, for every call, a
+    workspace of exactly the bytes its size function reports (four times that: generous).  Returns the flows and the workspaces."""
+    lib = _lib()
+    L = lib.lib()
+    H, W = fr.shape[1:]
+    dimg = _dev_frames(fr, H * W)
+    out = [_FlowBuffer(B, H, W, 2 * H * W) for _ in range(2)]
+    used = []
+
+    def call(fn, what, nbytes, b0, nb, *extra, parts=()):
+        assert nbytes > 0, what
+        used.append(_GuardedWorkspace(nbytes, generous))
+        lib.check(fn(_at(dimg, b0 * H * W), _at(dimg, (b0 + 1) * H * W), nb, *parts, H * W, H, W, ctypes.byref(p), out[0].ptr(b0), out[1].ptr(b0),
+                     2 * H * W, *used[-1].args(), lib.stream_ptr(), *extra), what)
+
+    if kind == "batch":
+        call(L.tf_farneback_batch, "tf_farneback_batch", L.tf_farneback_workspace_bytes_batch(B, H, W, ctypes.byref(p)), 0, B)
+    elif kind == "split":
+        call(L.tf_farneback_batch_split, "tf_farneback_batch_split", L.tf_farneback_workspace_bytes_split(B, 2, H, W, ctypes.byref(p)), 0, B, parts=(2,))
+    else:
+        call(L.tf_farneback_batch_phase, "tf_farneback_batch_phase 1", L.tf_farneback_workspace_bytes_phase(B, H, W, ctypes.byref(p), 1), 0, B, 1)
+        for b0, b1 in ((0, 2), (2, B)):
+            call(L.tf_farneback_batch_phase, "tf_farneback_batch_phase 2", L.tf_farneback_workspace_bytes_phase(b1 - b0, H, W, ctypes.byref(p), 2),
+                 b0, b1 - b0, 2)
+    res = out[0].frames(), out[1].frames()
+    _fb_status_ok()
+    return res, used
+
+
+@pytest.mark.parametrize("H,W,B,over", EXACT_CASES)
+def test_farneback_stays_inside_the_workspace_it_asks_for(H, W, B, over):
+    """Every entry point gets a workspace of exactly the bytes its size function reports, 4096 bytes inside an allocation
+    whose first and last 4096 bytes hold 0xA5: after the calls both guard bands are intact and the flows are those of
+    the same batch on a workspace four times as large.  A geometry that does not split runs the unsplit batch for parts 2
+    and reports no size for the phases."""
+    lib = _lib()
+    kw = dict(FB_DEFAULTS, **over)
+    p = lib.FarnebackParams(kw["num_levels"], kw["pyr_scale"], kw["win_size"], kw["num_iters"], kw["poly_n"], kw["poly_sigma"], lib.FB_CHAIN_DEFAULT, 0)
+    fr = _frames(np.random.default_rng(H * 1000 + W), B + 1, H, W)
+    want, _ = _fb_guarded_run(p, fr, B, "batch", generous=True)
+    assert np.abs(want[0]).max() > 0.1
+    splits = bool(lib.lib().tf_farneback_can_split(H, W, ctypes.byref(p)))
+    assert splits == _fb_can_split(H, W, kw) and (B >= 3 or not splits)
+    if not splits:
+        assert lib.lib().tf_farneback_workspace_bytes_phase(B, H, W, ctypes.byref(p), 1) == 0
+    for kind in ("batch", "split") + (("phase",) if splits else ()):
+        got, used = _fb_guarded_run(p, fr, B, kind)
+        _torch().cuda.synchronize()
+        for i, ws in enumerate(used):
+            assert ws.intact(), f"{kind}: call {i} wrote outside the {ws.nbytes} bytes it asked for"
+        for d in range(2):
+            _same_bits(got[d], want[d], f"{kind} on an exact workspace: {('forward', 'backward')[d]} flows")

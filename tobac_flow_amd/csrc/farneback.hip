@@ -24,12 +24,12 @@
 //     time) serves window sizes other than 13;
 //   * all of these are HBM / L2- or latency-bound stencils: no MFMA.
 #include "tf_common.h"
+#include "fb_plan.h"                                             // FB_MAX_KSIZE, the FBI_* strip geometry, levels, phases, scratch
 #include <math.h>
 #include <float.h>
 #include <stdlib.h>
 #include <atomic>
 
-#define FB_MAX_KSIZE 255
 #define FB_MAX_POLY_N 8
 
 __device__ __forceinline__ int fb_reflect101(int p, int len) {
@@ -712,12 +712,7 @@ k_fb_update_matrices(const float *__restrict__ R0, const float *__restrict__ R1,
 // The per-row evaluation is BRANCH-FREE (out-of-image gathers read a valid dummy address and are
 // discarded by selects) so that the loads of FBI_NB rows are in flight together, and the flow of the next
 // row group is fetched before the LDS phase of the current one.  Occupancy: two waves per SIMD = two four-wave workgroups per CU.
-#define FBI_M 6
-#define FBI_WIN (2 * FBI_M + 1)
-#ifndef FBI_T
-#define FBI_T 128                   // threads = evaluated columns per workgroup
-#endif
-#define FBI_OW (FBI_T - 2 * FBI_M)
+// (FBI_M, FBI_WIN, FBI_T, FBI_OW: fb_plan.h)
 // R[img] / fin[q] / fout[q] are the pointers of batch item 0; item b adds b * the matching stride
 struct FbIterArgs {
     const float *R[2]; const float *fin[2]; float *fout[2]; int dir[2]; int nd, nx; int64_t bs_R, bs_fin[2], bs_fout[2];
@@ -885,8 +880,7 @@ __device__ __forceinline__ void fb_taps_eval(const FbIterCtx &c, int s, const Fb
 //     waits for a lower ticket, which is running or done -- no deadlock whatever the dispatch order;
 //   * the 2 x 2 solve is OpenCV's expression on the window MEANS, with a true division.
 #define FBI_VS2 (FBI_T + 9)         // LDS row stride in doubles, odd: lanes (r, ch) of a scan hit different banks (137 * 2 mod 64 = 18)
-#define FBI_HDR 16384               // bytes of ticket counters in front of a batch's hand-over words: 16 ints per launch of a level (8 used: one per XCD)
-#define FBI_HW 20                   // hand-over words per row and strip: (g, V[next strip's x - 7]) x 5 channels x two halves, stored as four planes of H x 5
+// (FBI_HDR, FBI_HW -- the ticket counters and hand-over words in front of and in the blur scratch: fb_plan.h)
 
 __device__ __forceinline__ unsigned long long fb_hand_ld(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void fb_hand_st(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1503,95 +1497,6 @@ static void fb_prepare_poly(int n, double sigma, FbPoly *pp) {
     pp->ig11 = m[1][7]; pp->ig03 = m[0][9]; pp->ig33 = m[3][9]; pp->ig55 = m[5][11];
 }
 
-static int fb_levels(int64_t H, int64_t W, const tf_farneback_params *p) {
-    int k; double scale = 1;
-    for (k = 0; k < p->num_levels; k++) { scale *= p->pyr_scale; if (W * scale < 32 || H * scale < 32) break; }
-    return k;
-}
-
-// floats of blur scratch the iteration kernel borrows per pair at a level of h x w: 1 KB of ticket counters + the strips'
-// hand-over words (both directions)
-static size_t fb_hand_floats(int64_t h, int64_t w) {
-    const int64_t nx = (w + FBI_OW - 1) / FBI_OW;
-    return FBI_HDR / 4 + 2 * (size_t)(2 * (nx - 1) * h * FBI_HW);
-}
-// level k's image size and the largest plane / row-blur scratch among the levels k_lo .. k_hi
-static void fb_level_size(int H, int W, const tf_farneback_params *p, int k, int *h, int *w) {
-    double scale = 1; for (int i = 0; i < k; i++) scale *= p->pyr_scale;
-    *w = (int)lrint(W * scale); *h = (int)lrint(H * scale);
-}
-static void fb_phase_sizes(int H, int W, const tf_farneback_params *p, int k_hi, int k_lo, size_t *tmp_floats, size_t *plane) {
-    size_t t = 0, pl = 0;
-    for (int k = k_lo; k <= k_hi; k++) {
-        int h, w; fb_level_size(H, W, p, k, &h, &w);
-        pl = std::max(pl, (size_t)h * w);
-        // a full-size level: a whole image (+ rows; what a two-pass blur needs -- the size workspaces and batch hints have been
-        // computed from), the sampled blur H rows of w float2
-        t = std::max(t, k == 0 ? (size_t)H * W + 2 * (size_t)H + 64 : std::max((size_t)H * W / 4 + 2 * (size_t)H + 64, 2 * (size_t)H * w + 64));
-        t = std::max(t, fb_hand_floats(h, w));
-    }
-    if (k_lo == 0) t = std::max(t, std::max((size_t)H * W + 2 * (size_t)H + 64, fb_hand_floats(H, W)));
-    *tmp_floats = t; *plane = pl;
-}
-// floats of blur scratch per pair for all levels: the full-size blur (n + 2H + 64), the hand-over words and the sampled blur's
-// H rows of w float2 -- 2 H w floats, more than n from a pyramid scale above 0.5 on (1.2 n at level 1 of scale 0.6: sized
-// by n + 2H + 64, one pair's rows ran into the next pair's scratch)
-static size_t fb_full_tmp_floats(int64_t H, int64_t W, const tf_farneback_params *p) {
-    size_t t = 0, pl = 0;
-    fb_phase_sizes((int)H, (int)W, p, fb_levels(H, W, p), 0, &t, &pl);
-    return t;
-}
-static size_t fb_pair_floats(int64_t H, int64_t W, const tf_farneback_params *p) {
-    // per pair: tmp (fb_full_tmp_floats), blur, I, R[2] (5n each), 2 flow scratch (2n each); the 5-plane matrix M (5n) only for
-    // the unfused fallback (window sizes other than 13): the fused iteration never stores it
-    const size_t n = (size_t)H * W;
-    const bool fused = p->win_size == FBI_WIN;
-    return tf_align_up(fb_full_tmp_floats(H, W, p), 64) + 2 * tf_align_up(n, 64) + (fused ? 10 : 15) * tf_align_up(n, 64) + 2 * tf_align_up(2 * n, 64);
-}
-
-extern "C" size_t tf_farneback_workspace_bytes_batch(int64_t B, int64_t H, int64_t W, const tf_farneback_params *p)
-{
-    if (B <= 0 || H <= 0 || W <= 0 || !p) return 0;
-    return (size_t)B * fb_pair_floats(H, W, p) * sizeof(float) + 8192;
-}
-
-// Pairs per tf_farneback_batch call that fill the GPU best.  The iteration kernel runs one workgroup per (pair, strip,
-// direction) over all rows, four workgroups are resident per CU, and a workgroup does not speed up when its CU is
-// half empty: a launch costs ceil(chains / resident) rounds.  Returns the batch size <= max_pairs (and within
-// max_bytes of workspace, 0 = no limit) with the best fill of its last round, the larger one on ties within 2 %.
-extern "C" int64_t tf_farneback_batch_hint(int64_t H, int64_t W, const tf_farneback_params *p, int64_t max_pairs, size_t max_bytes)
-{
-    if (H <= 0 || W <= 0 || !p || max_pairs < 1) return 0;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    const int64_t slots = (int64_t)n_cu * 8 / (FBI_T / 64);                     // two waves per SIMD; one (strip, direction) per workgroup of FBI_T threads
-    const size_t per_pair_bytes = fb_pair_floats(H, W, p) * sizeof(float);
-    int64_t cap = max_pairs;
-    if (max_bytes > 0 && (int64_t)(max_bytes / per_pair_bytes) < cap) cap = (int64_t)(max_bytes / per_pair_bytes);
-    if (cap < 1) cap = 1;
-    if (cap > 1024) cap = 1024;
-    // A launch of the iteration kernel costs whole ROUNDS of resident workgroups, each as long as the level is high, at
-    // EVERY pyramid level: B pairs cost sum_l ceil(B strips_l / slots) rows_l and do sum_l (B strips_l / slots) rows_l of
-    // work.  The batch with the best ratio wins, the larger one among those within 1 % of it (at 5424^2 on 256 CUs: 42
-    // pairs, 94.6 %: full rounds at levels 0, 1 AND 2; 54 pairs: 92.1 %, 43 pairs: 85 % -- level 1 spills into a third round).
-    const int levels = fb_levels(H, W, p);
-    auto efficiency = [&](int64_t B) {
-        double cost = 0, work = 0, scale = 1;
-        for (int k = 0; k <= levels; k++) {
-            const int64_t w = (int64_t)lrint(W * scale), h = (int64_t)lrint(H * scale);
-            const int64_t chains = 2 * B * ((w + FBI_OW - 1) / FBI_OW), rounds = (chains + slots - 1) / slots;
-            cost += (double)rounds * (double)h; work += (double)chains / (double)slots * (double)h;
-            scale *= p->pyr_scale;
-        }
-        return work / cost;
-    };
-    double best_eff = 0;
-    for (int64_t B = 1; B <= cap; B++) best_eff = std::max(best_eff, efficiency(B));
-    int64_t pick = 1;
-    for (int64_t B = cap; B >= 1; B--) if (efficiency(B) >= best_eff - 0.01) { pick = B; break; }
-    return pick;
-}
-
 // ---- starved chains -> TF_ESTARVED ---------------------------------------------------------------------------------------
 // A ring of pinned, device-visible status words per device.  A chain of k_fb_iter that gives up on its left neighbour's
 // hand-over words (fb_chain_enter) stores 1 into the word its launch was handed; the host reads it once the launches are
@@ -1682,16 +1587,14 @@ static int fb_test_starve_polls()
     return v;
 }
 
-// Workgroups of the iteration kernel's full-resolution launch for B pairs (both directions), and how many of them the
-// device holds at once: a launch costs whole rounds of resident workgroups, so a caller that may cut a batch into parts
-// (tf_farneback_batch_phase) does so only while a part still fills a round.
-// resident two-wave workgroups of the current device (cached per device index: ADVICE r4 -- one `static int` kept the first
-// device's count for every device)
+// ---- sizes: every one read off the level plan (fb_plan.h) ------------------------------------------------------------------
+// resident two-wave workgroups of the iteration kernel on the current device: two waves per SIMD, one (strip, direction) per
+// workgroup of FBI_T threads (cached per device index: ADVICE r4 -- one `static int` kept the first device's count for every
+// device; 256 CUs where no device answers)
 static int fb_resident_slots()
 {
     static std::atomic<int> cache[TF_MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= TF_MAX_DEVICES) dev = 0;
+    const int dev = fb_current_device();
     int v = cache[dev].load(std::memory_order_relaxed);
     if (v == 0) {
         int n_cu = 256;
@@ -1701,303 +1604,291 @@ static int fb_resident_slots()
     }
     return v;
 }
+extern "C" size_t tf_farneback_workspace_bytes(int64_t H, int64_t W, const tf_farneback_params *p) { return fb_bytes(FB_WHOLE, 1, H, W, p); }
+extern "C" size_t tf_farneback_workspace_bytes_batch(int64_t B, int64_t H, int64_t W, const tf_farneback_params *p) { return fb_bytes(FB_WHOLE, B, H, W, p); }
+extern "C" size_t tf_farneback_workspace_bytes_split(int64_t B, int64_t parts, int64_t H, int64_t W, const tf_farneback_params *p) { return fb_bytes_split(B, parts, H, W, p); }
+extern "C" size_t tf_farneback_workspace_bytes_phase(int64_t B, int64_t H, int64_t W, const tf_farneback_params *p, int phase) { return fb_bytes(phase == 2 ? FB_FINE : FB_COARSE, B, H, W, p); }
+extern "C" int tf_farneback_can_split(int64_t H, int64_t W, const tf_farneback_params *p) { return fb_can_split(H, W, p) ? 1 : 0; }
+extern "C" int64_t tf_farneback_batch_hint(int64_t H, int64_t W, const tf_farneback_params *p, int64_t max_pairs, size_t max_bytes)
+{
+    return fb_batch_hint(H, W, p, max_pairs, max_bytes, fb_resident_slots());
+}
+// workgroups of the iteration kernel's full-resolution launch for B pairs (both directions), and how many the device holds at once
 extern "C" int64_t tf_farneback_iteration_workgroups(int64_t H, int64_t W, const tf_farneback_params *p, int64_t B, int64_t *resident_out)
 {
     if (H <= 0 || W <= 0 || !p || B < 1) return 0;
     if (resident_out) *resident_out = fb_resident_slots();
-    return 2 * B * ((W + FBI_OW - 1) / FBI_OW);
+    return 2 * B * fb_strips(W);
 }
 
-extern "C" size_t tf_farneback_workspace_bytes(int64_t H, int64_t W, const tf_farneback_params *p)
+// ---- one phase of pyramid levels ----------------------------------------------------------------------------------------------
+// a checked call (fb_check_args) ...
+struct FbCall {
+    const uint8_t *img[2]; float *out[2]; int B; int64_t img_stride, flow_stride; int H, W; const tf_farneback_params *p;
+    void *ws; size_t ws_bytes; hipStream_t s; FbPoly pp;
+};
+// ... and one phase of it over B of its pairs: what the four steps of a level share
+struct FbRun {
+    const FbCall &c; const FbPhase &ph; int B;
+    const uint8_t *img[2];                       // the first pair of the range
+    float *a[FB_ARRAYS];                         // the phase's scratch arrays (fb_carve_offsets): B items back to back, strides ph.stride[]
+    int nd, dirs[2];                             // the directions asked for
+    float *slot[2][2]; int64_t slot_bs[2][2];    // per direction two ping-pong slots: slot 0 = the caller's output (stride flow_stride), slot 1 = scratch
+    int cur, pw, phh;                            // the slot that holds the current flow (of either direction) and that flow's size
+    int64_t bs(int i) const { return (int64_t)ph.stride[i]; }
+};
+
+// step 1: the level's two images (Gaussian blur of the full-size frame, resized) and their polynomial expansions
+static int fb_level_images(const FbRun &r, const FbLevel &l)
 {
-    return tf_farneback_workspace_bytes_batch(1, H, W, p);
-}
-
-// scratch of one phase: every array holds B items back to back; bs_* = the items' stride in floats
-struct FbScratch { float *tmp, *blur, *I, *R[2], *M, *fbuf[2]; int64_t bs_tmp, bs_n, bs_R, bs_f; };
-static size_t fb_scratch_floats(size_t tmp_floats, size_t plane, bool fused) {
-    return tf_align_up(tmp_floats, 64) + 2 * tf_align_up(plane, 64) + (fused ? 10 : 15) * tf_align_up(plane, 64) + 2 * tf_align_up(2 * plane, 64);
-}
-static bool fb_carve(TfArena &ar, int B, size_t tmp_floats, size_t plane, bool fused, FbScratch *S) {
-    S->bs_tmp = (int64_t)tf_align_up(tmp_floats, 64); S->bs_n = (int64_t)tf_align_up(plane, 64);
-    S->bs_R = 5 * S->bs_n; S->bs_f = (int64_t)tf_align_up(2 * plane, 64);
-    S->tmp = ar.take<float>(S->bs_tmp * B); S->blur = ar.take<float>(S->bs_n * B); S->I = ar.take<float>(S->bs_n * B);
-    S->R[0] = ar.take<float>(S->bs_R * B); S->R[1] = ar.take<float>(S->bs_R * B);
-    S->M = fused ? nullptr : ar.take<float>(S->bs_R * B);          // unfused fallback only
-    S->fbuf[0] = ar.take<float>(S->bs_f * B); S->fbuf[1] = ar.take<float>(S->bs_f * B);
-    return ar.ok();
-}
-
-// pyramid levels k_hi .. k_lo for B pairs (pointers at the first pair of the range); cur / pw / ph carry the state of the
-// levels above over to the next call
-static int fb_run_levels(const uint8_t *prev, const uint8_t *next, int B, int64_t img_stride, int H, int W, const tf_farneback_params *p,
-                         float *const out[2], int64_t flow_stride, const FbScratch &S, int k_hi, int k_lo, int cur[2], int *pw_io, int *ph_io,
-                         const FbPoly &pp, hipStream_t s)
-{
+    const int H = r.c.H, W = r.c.W, B = r.B, h = l.h, w = l.w;
     const size_t n = (size_t)H * W;
-    float *tmp = S.tmp, *blur = S.blur, *I = S.I, *M = S.M;
-    float *const R[2] = {S.R[0], S.R[1]};
-    const int64_t bs_tmp = S.bs_tmp, bs_n = S.bs_n, bs_R = S.bs_R;
-    const uint8_t *img[2] = {prev, next};
-    int nd = 0, dirs[2];
-    for (int d = 0; d < 2; d++) if (out[d]) dirs[nd++] = d;
-    // per direction two ping-pong slots: slot 0 = the caller's output (stride flow_stride), slot 1 = scratch
-    float *slot[2][2]; int64_t slot_bs[2][2];
-    for (int d = 0; d < 2; d++) { slot[d][0] = out[d]; slot_bs[d][0] = flow_stride; slot[d][1] = S.fbuf[d]; slot_bs[d][1] = S.bs_f; }
-    int pw = *pw_io, ph = *ph_io;
-    const dim3 block(64, 4);
-    const bool fused = p->win_size == FBI_WIN;
-    for (int k = k_hi; k >= k_lo; k--) {
-        double scale = 1; for (int i = 0; i < k; i++) scale *= p->pyr_scale;
-        const double sigma = (1. / scale - 1) * 0.5;
-        int smooth_sz = (int)lrint(sigma * 5) | 1; if (smooth_sz < 3) smooth_sz = 3;
-        TF_REQUIRE(smooth_sz <= FB_MAX_KSIZE, "tf_farneback: blur kernel too large");
-        const int w = (int)lrint(W * scale), h = (int)lrint(H * scale);
-        const int64_t plane = (int64_t)w * h;
-        const dim3 glev((w + 63) / 64, (h + 3) / 4, B);
-        FbKernel hk; fb_gaussian_kernel(smooth_sz, sigma, &hk);
-        for (int i = 0; i < 2; i++) {
-            const float *Ik = blur; int64_t bs_Ik = bs_n;
-            const double rsx = 1. / ((double)w / W), rsy = 1. / ((double)h / H);
-            const int irx = (int)(rsx + 0.5), iry = (int)(rsy + 0.5);
-            const bool same = (w == W && h == H);
-            const bool area2 = !same && fabs(rsx - irx) < DBL_EPSILON && fabs(rsy - iry) < DBL_EPSILON && irx == 2 && iry == 2;
-            if (area2 && hk.ksize == 3 && W >= 2 && H >= 2 && 2 * w <= W && 2 * h <= H) {
-                TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 4.0 * plane) * B, s);                   // u8 r + quarter-size f32 w
-                hipLaunchKernelGGL(k_fb_blur3_area2<uint8_t>, glev, block, 0, s, img[i], H, W, hk, I, h, w, img_stride, bs_n);
-                Ik = I;
-            } else if (same || area2) {
-                // levels are at least 32 px (fb_levels), so the scale here is within 1/64 of 1 or of 0.5: sigma <= 0.53, 3 taps
-                TF_REQUIRE(hk.ksize == 3, "tf_farneback: full-size or exact-2x level with a blur longer than 3 taps");
-                {
-                    TfProfScope ps(TFK_FB_BLUR, 5.0 * n * B, s);      // u8 r + f32 w
-                    hipLaunchKernelGGL(k_fb_blur3_fused<uint8_t>, dim3((W + 255) / 256, (H + 3) / 4, B), block, 0, s, img[i], H, W, hk, blur, img_stride, bs_n);
-                }
-                if (area2) {
-                    TfProfScope ps(TFK_FB_RESIZE, (4.0 * n + 4.0 * plane) * B, s);
-                    hipLaunchKernelGGL(k_fb_resize_area2, glev, block, 0, s, blur, W, I, h, w, bs_n, bs_n);
-                    Ik = I;
-                }
-            } else {
-                // blur + resize fused on the sampled columns / rows (tmp holds rowf: H * w float2, fb_full_tmp_floats)
-                TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 8.0 * (double)H * w * 2 + 4.0 * plane) * B, s);
-                FbResizeGeom rg; rg.sh = H; rg.sw = W; rg.dh = h; rg.dw = w; rg.scale_x = rsx; rg.scale_y = rsy;
-                // LDS-staged form when a workgroup's source segment fits (64 outputs * stride + ksize bytes per row)
-                const int64_t seg = (int64_t)(64 * rsx) + hk.ksize + 8;
-                // (measured at 5424^2, 8 images: stride 32 / 16: 958 -> 282 / 554 -> 322 us; stride 8 / 4: 355 -> 415 / 380 -> 673 us --
-                // short kernels gain nothing from staging and pay for the barrier: LDS form from stride 12 on)
-                if (hk.ksize > 5 && rsx >= 12. && seg <= FBL_ROW_BYTES && W >= hk.ksize) {
-                    int unit_shift = 2;                                 // pad unit = largest power of two <= stride, >= 8 bytes;
-                    while ((2 << unit_shift) <= (int)rsx) unit_shift++; // unit 4 (shift 2) would pad every word: then no padding
-                    if (unit_shift < 3) unit_shift = 30;
-                    hipLaunchKernelGGL(k_fb_blur_rows_sampled_lds, dim3((w + 63) / 64, (H + 3) / 4, B), block, 0, s, img[i], rg, hk,
-                                       (float2 *)tmp, img_stride, bs_tmp / 2, unit_shift);
-                } else
-                    hipLaunchKernelGGL(k_fb_blur_rows_sampled<uint8_t>, dim3((w + 63) / 64, (H + 3) / 4, B), block, 0, s, img[i], rg, hk,
-                                       (float2 *)tmp, img_stride, bs_tmp / 2);
-                hipLaunchKernelGGL(k_fb_blur_cols_resize, glev, block, 0, s, (const float2 *)tmp, rg, hk, I, bs_tmp / 2, bs_n);
+    const int64_t plane = (int64_t)w * h, img_stride = r.c.img_stride, bs_tmp = r.bs(FB_TMP), bs_n = r.bs(FB_BLUR);
+    float *tmp = r.a[FB_TMP], *blur = r.a[FB_BLUR], *I = r.a[FB_I];
+    hipStream_t s = r.c.s;
+    const double sigma = (1. / l.scale - 1) * 0.5;
+    int smooth_sz = (int)lrint(sigma * 5) | 1; if (smooth_sz < 3) smooth_sz = 3;
+    TF_REQUIRE(smooth_sz <= FB_MAX_KSIZE, "tf_farneback: blur kernel too large");
+    const dim3 block(64, 4), glev((w + 63) / 64, (h + 3) / 4, B);
+    FbKernel hk; fb_gaussian_kernel(smooth_sz, sigma, &hk);
+    for (int i = 0; i < 2; i++) {
+        const float *Ik = blur;
+        const double rsx = 1. / ((double)w / W), rsy = 1. / ((double)h / H);
+        const int irx = (int)(rsx + 0.5), iry = (int)(rsy + 0.5);
+        const bool same = (w == W && h == H);
+        const bool area2 = !same && fabs(rsx - irx) < DBL_EPSILON && fabs(rsy - iry) < DBL_EPSILON && irx == 2 && iry == 2;
+        if (area2 && hk.ksize == 3 && W >= 2 && H >= 2 && 2 * w <= W && 2 * h <= H) {
+            TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 4.0 * plane) * B, s);                   // u8 r + quarter-size f32 w
+            hipLaunchKernelGGL(k_fb_blur3_area2<uint8_t>, glev, block, 0, s, r.img[i], H, W, hk, I, h, w, img_stride, bs_n);
+            Ik = I;
+        } else if (same || area2) {
+            // levels are at least 32 px (fb_levels), so the scale here is within 1/64 of 1 or of 0.5: sigma <= 0.53, 3 taps
+            TF_REQUIRE(hk.ksize == 3, "tf_farneback: full-size or exact-2x level with a blur longer than 3 taps");
+            {
+                TfProfScope ps(TFK_FB_BLUR, 5.0 * n * B, s);      // u8 r + f32 w
+                hipLaunchKernelGGL(k_fb_blur3_fused<uint8_t>, dim3((W + 255) / 256, (H + 3) / 4, B), block, 0, s, r.img[i], H, W, hk, blur, img_stride, bs_n);
+            }
+            if (area2) {
+                TfProfScope ps(TFK_FB_RESIZE, (4.0 * n + 4.0 * plane) * B, s);
+                hipLaunchKernelGGL(k_fb_resize_area2, glev, block, 0, s, blur, W, I, h, w, bs_n, bs_n);
                 Ik = I;
             }
-            {
-                TfProfScope ps(TFK_FB_POLYEXP, 24.0 * plane * B, s);   // fused-ideal: 4 r + 20 w per level pixel
-                fb_launch_polyexp(Ik, h, w, pp, R[i], plane, bs_Ik, bs_R, B, s);
-            }
-        }
-        TF_CHECK_LAUNCH();
-        // level's initial flow
-        for (int q = 0; q < nd; q++) {
-            const int d = dirs[q];
-            if (cur[d] < 0) {
-                // choose the start slot so that the result of level 0 lands in slot 0 (the caller's buffer):
-                // every level flips the slot num_iters times (+1 for the upsample on all but the coarsest level);
-                // the unfused fallback iterates in place (no flips from iterations)
-                const int flips_per_level = (fused ? p->num_iters : 0) + 1;
-                const int total = (k + 1) * flips_per_level - 1;
-                cur[d] = (total % 2 == 0) ? 0 : 1;
-                hipLaunchKernelGGL(k_fb_zero, dim3((unsigned)((plane * 2 + 255) / 256), 1, B), dim3(256), 0, s,
-                                   slot[d][cur[d]], plane * 2, slot_bs[d][cur[d]]);
-            } else {
-                const int src = cur[d], dst = 1 - cur[d];
-                TfProfScope ps(TFK_FB_RESIZE, (8.0 * pw * ph + 8.0 * plane) * B, s);
-                const double sx = 1. / ((double)w / pw), sy = 1. / ((double)h / ph);
-                if (slot_bs[d][src] % 2 == 0 && slot_bs[d][dst] % 2 == 0)
-                    hipLaunchKernelGGL(k_fb_resize_linear2, glev, block, 0, s, (const float2 *)slot[d][src], ph, pw, (float2 *)slot[d][dst],
-                                       h, w, sx, sy, (float)(1. / p->pyr_scale), slot_bs[d][src] / 2, slot_bs[d][dst] / 2);
-                else                                          // odd caller stride: items are not 8-byte aligned
-                    hipLaunchKernelGGL(k_fb_resize_linear, glev, block, 0, s, slot[d][src], ph, pw, 2, slot[d][dst], h, w, sx, sy,
-                                       (float)(1. / p->pyr_scale), slot_bs[d][src], slot_bs[d][dst]);
-                cur[d] = dst;
-            }
-        }
-        TF_CHECK_LAUNCH();
-        if (fused) {
-            // whole columns per workgroup (k_fb_iter): parallelism = strips x directions x pairs
-            const int nx = (w + FBI_OW - 1) / FBI_OW;
-            FbIterArgs ia;
-            ia.R[0] = R[0]; ia.R[1] = R[1]; ia.bs_R = bs_R; ia.nd = nd; ia.nx = nx;
-            // The chain in two parts one row group apart (HP form; same flows) is the faster form alone on the GPU (level-0
-            // launch of 21 pairs: 18.0 against 19.7 ms), but its 39 KB of LDS per workgroup fill the CU (4 x 39 = 156 of
-            // 160 KB): in the pipelined benchmark the floods of the finished windows run beside the flow in what the one-lane
-            // form leaves free -- LDS: 160 KB - 4 x 27 KB; registers: 512 - 2 x 224 = 64 per lane and SIMD, which the
-            // connectivity-1 sweep kernels are built to fit (watershed.hip, tests/test_kernel_resources_cpu.py); a kernel that
-            // needs more than 64 cannot start on a SIMD before an iteration workgroup has left its CU -- and with the
-            // two-part form they displace iteration workgroups instead -- the kernel
-            // then reads 1 985 against 1 860 ms per config-F step, the step is the same (4.75 s either way, back to back on one
-            // box).  So it is chosen PER CALL (tf_farneback_params.chain_form): the host layer asks for the two-part form when
-            // nothing is going to run beside this call's flow; a process-wide switch, as in round 4, let one thread's plain
-            // create_flow turn it on under another thread's pipelined one.
-            const bool whole_chain = p->chain_form != TF_FB_CHAIN_TWO_PART;
-            // sequential row sums: the strips' hand-over words and the launches' ticket counters live in the blur scratch,
-            // idle from the polynomial expansion of this level to the blur of the next: [1 KB of counters][words] per pair
-            const size_t hand_words = (size_t)nd * (size_t)(nx - 1) * (size_t)h * FBI_HW;
-            {
-                // column groups: one per round of resident workgroups (four two-wave workgroups per CU, one direction each)
-                const int slots = fb_resident_slots();                       // of THIS device
-                const int rounds = (int)(((int64_t)nx * B * 2 + slots - 1) / slots);
-                const int n_groups = std::min(rounds, nx);
-                ia.nb = B; ia.nxg = (nx + n_groups - 1) / n_groups;
-            }
-            ia.hand = (unsigned long long *)((char *)tmp + FBI_HDR); ia.bs_hand = bs_tmp / 2; ia.ticket = (int *)tmp; ia.epoch = 0;
-            const int starve_polls = fb_test_starve_polls();
-            ia.starve = starve_polls >= 0;
-            ia.poll_limit = ia.starve ? starve_polls : (1 << 22);
-            ia.starved = fb_starved_word(true, p->status_slot);
-            if (!ia.starved) { tf_set_error("tf_farneback: no pinned status word for the iteration kernel (hipHostMalloc failed)"); return TF_EHIP; }
-            TF_REQUIRE(FBI_HDR + hand_words * 8 <= (size_t)bs_tmp * sizeof(float), "tf_farneback: blur scratch too small for the strips' hand-over words");
-            TF_REQUIRE(p->num_iters <= 250, "tf_farneback: more than 250 iterations per level");
-            TF_CHECK_HIP(hipMemsetAsync(tmp, 0, FBI_HDR, s));
-            for (int b = 0; b < B && hand_words > 0; b++) TF_CHECK_HIP(hipMemsetAsync((char *)(tmp + (int64_t)b * bs_tmp) + FBI_HDR, 0, hand_words * 8, s));
-            const dim3 gi((unsigned)(nx * B * nd));
-            for (int it = 0; it < p->num_iters; it++) {
-                for (int q = 0; q < nd; q++) {
-                    const int d = dirs[q];
-                    ia.dir[q] = d;
-                    ia.fin[q] = slot[d][cur[d]]; ia.bs_fin[q] = slot_bs[d][cur[d]];
-                    ia.fout[q] = slot[d][1 - cur[d]]; ia.bs_fout[q] = slot_bs[d][1 - cur[d]];
-                }
-                {
-                    TfProfScope ps(TFK_FB_ITER, 56.0 * plane * nd * B, s);
-                    ia.epoch = (unsigned)(it + 1); ia.ticket = (int *)tmp + 16 * it;
-                    if (whole_chain) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0>), gi, dim3(FBI_T), 0, s, ia, h, w, plane);
-                    else hipLaunchKernelGGL((k_fb_iter<FBI_NB, 1>), gi, dim3(FBI_T), 0, s, ia, h, w, plane);
-                }
-                for (int q = 0; q < nd; q++) cur[dirs[q]] = 1 - cur[dirs[q]];
-            }
-            TF_CHECK_LAUNCH();
         } else {
-            // generic window size: separate UpdateMatrices / box-filter+solve kernels, one pair at a time, in place
-            const dim3 glev1((w + 63) / 64, (h + 3) / 4, 1);
-            const dim3 gt((w + FBT_W - 1) / FBT_W, (h + FBT_H - 1) / FBT_H);
-            for (int b = 0; b < B; b++)
-                for (int q = 0; q < nd; q++) {
-                    const int d = dirs[q];
-                    float *flow = slot[d][cur[d]] + (int64_t)b * slot_bs[d][cur[d]];
-                    const float *R0 = R[d] + (int64_t)b * bs_R, *R1 = R[1 - d] + (int64_t)b * bs_R;
-                    float *Mb = M + (int64_t)b * bs_R;
-                    {
-                        TfProfScope ps(TFK_FB_MATRICES, 68.0 * plane, s);
-                        hipLaunchKernelGGL(k_fb_update_matrices, glev1, block, 0, s, R0, R1, flow, h, w, plane, Mb);
-                    }
-                    for (int it = 0; it < p->num_iters; it++) {
-                        {
-                            TfProfScope ps(TFK_FB_BLUR_SOLVE, 28.0 * plane, s);
-                            hipLaunchKernelGGL(k_fb_blur_solve, gt, block, 0, s, Mb, h, w, plane, p->win_size / 2, flow);
-                        }
-                        if (it < p->num_iters - 1) {
-                            TfProfScope ps(TFK_FB_MATRICES, 68.0 * plane, s);
-                            hipLaunchKernelGGL(k_fb_update_matrices, glev1, block, 0, s, R0, R1, flow, h, w, plane, Mb);
-                        }
-                    }
-                }
-            TF_CHECK_LAUNCH();
+            // blur + resize fused on the sampled columns / rows (tmp holds rowf: H * w float2, fb_phase)
+            TfProfScope ps(TFK_FB_BLUR, (1.0 * n + 8.0 * (double)H * w * 2 + 4.0 * plane) * B, s);
+            FbResizeGeom rg; rg.sh = H; rg.sw = W; rg.dh = h; rg.dw = w; rg.scale_x = rsx; rg.scale_y = rsy;
+            // LDS-staged form when a workgroup's source segment fits (64 outputs * stride + ksize bytes per row)
+            const int64_t seg = (int64_t)(64 * rsx) + hk.ksize + 8;
+            // (measured at 5424^2, 8 images: stride 32 / 16: 958 -> 282 / 554 -> 322 us; stride 8 / 4: 355 -> 415 / 380 -> 673 us --
+            // short kernels gain nothing from staging and pay for the barrier: LDS form from stride 12 on)
+            if (hk.ksize > 5 && rsx >= 12. && seg <= FBL_ROW_BYTES && W >= hk.ksize) {
+                int unit_shift = 2;                                 // pad unit = largest power of two <= stride, >= 8 bytes;
+                while ((2 << unit_shift) <= (int)rsx) unit_shift++; // unit 4 (shift 2) would pad every word: then no padding
+                if (unit_shift < 3) unit_shift = 30;
+                hipLaunchKernelGGL(k_fb_blur_rows_sampled_lds, dim3((w + 63) / 64, (H + 3) / 4, B), block, 0, s, r.img[i], rg, hk,
+                                   (float2 *)tmp, img_stride, bs_tmp / 2, unit_shift);
+            } else
+                hipLaunchKernelGGL(k_fb_blur_rows_sampled<uint8_t>, dim3((w + 63) / 64, (H + 3) / 4, B), block, 0, s, r.img[i], rg, hk,
+                                   (float2 *)tmp, img_stride, bs_tmp / 2);
+            hipLaunchKernelGGL(k_fb_blur_cols_resize, glev, block, 0, s, (const float2 *)tmp, rg, hk, I, bs_tmp / 2, bs_n);
+            Ik = I;
         }
-        pw = w; ph = h;
+        {
+            TfProfScope ps(TFK_FB_POLYEXP, 24.0 * plane * B, s);   // fused-ideal: 4 r + 20 w per level pixel
+            fb_launch_polyexp(Ik, h, w, r.c.pp, r.a[FB_R0 + i], plane, bs_n, r.bs(FB_R0), B, s);
+        }
     }
-    *pw_io = pw; *ph_io = ph;
+    TF_CHECK_LAUNCH();
     return TF_OK;
 }
 
-// levels >= FB_SPLIT_LEVEL of a split batch run for all its pairs at once, the finer ones in parts
-#define FB_SPLIT_LEVEL 2
-extern "C" size_t tf_farneback_workspace_bytes_split(int64_t B, int64_t parts, int64_t H, int64_t W, const tf_farneback_params *p)
+// step 2: the level's initial flow -- zeros in the phase's start slot (fb_start_slot) at the top of the pyramid, else the
+// level above's flow, upsampled into the other slot
+static int fb_level_flow(FbRun &r, const FbLevel &l)
 {
-    if (B <= 0 || H <= 0 || W <= 0 || !p) return 0;
-    const int levels = fb_levels(H, W, p);
-    const bool fused = p->win_size == FBI_WIN;
-    if (parts <= 1 || levels < FB_SPLIT_LEVEL || B < 2 || p->pyr_scale != 0.5) return tf_farneback_workspace_bytes_batch(B, H, W, p);
-    if (parts > B) parts = B;
-    size_t t = 0, pl = 0;
-    fb_phase_sizes((int)H, (int)W, p, levels, FB_SPLIT_LEVEL, &t, &pl);
-    const size_t coarse = (size_t)B * fb_scratch_floats(t, pl, fused) * sizeof(float) + 8192;
-    const size_t fine = tf_farneback_workspace_bytes_batch((B + parts - 1) / parts, H, W, p);
-    return coarse > fine ? coarse : fine;
+    const int64_t plane = (int64_t)l.w * l.h;
+    const dim3 block(64, 4), glev((l.w + 63) / 64, (l.h + 3) / 4, r.B);
+    hipStream_t s = r.c.s;
+    for (int q = 0; q < r.nd; q++) {
+        const int d = r.dirs[q], src = r.cur, dst = 1 - r.cur;
+        if (r.pw == 0) {
+            hipLaunchKernelGGL(k_fb_zero, dim3((unsigned)((plane * 2 + 255) / 256), 1, r.B), dim3(256), 0, s, r.slot[d][src], plane * 2, r.slot_bs[d][src]);
+            continue;
+        }
+        TfProfScope ps(TFK_FB_RESIZE, (8.0 * r.pw * r.phh + 8.0 * plane) * r.B, s);
+        const double sx = 1. / ((double)l.w / r.pw), sy = 1. / ((double)l.h / r.phh);
+        const float gain = (float)(1. / r.c.p->pyr_scale);
+        if (r.slot_bs[d][src] % 2 == 0 && r.slot_bs[d][dst] % 2 == 0)
+            hipLaunchKernelGGL(k_fb_resize_linear2, glev, block, 0, s, (const float2 *)r.slot[d][src], r.phh, r.pw, (float2 *)r.slot[d][dst],
+                               l.h, l.w, sx, sy, gain, r.slot_bs[d][src] / 2, r.slot_bs[d][dst] / 2);
+        else                                          // odd caller stride: items are not 8-byte aligned
+            hipLaunchKernelGGL(k_fb_resize_linear, glev, block, 0, s, r.slot[d][src], r.phh, r.pw, 2, r.slot[d][dst], l.h, l.w, sx, sy,
+                               gain, r.slot_bs[d][src], r.slot_bs[d][dst]);
+    }
+    if (r.pw != 0) r.cur = 1 - r.cur;
+    TF_CHECK_LAUNCH();
+    return TF_OK;
 }
 
-extern "C" int tf_farneback_batch_split(const uint8_t *prev, const uint8_t *next, int64_t B64, int64_t parts64, int64_t img_stride,
-                                        int64_t H64, int64_t W64, const tf_farneback_params *p,
-                                        float *flow_fwd, float *flow_bwd, int64_t flow_stride,
-                                        void *ws, size_t ws_bytes, void *stream)
+// step 3, window size FBI_WIN: num_iters launches of the fused iteration kernel, each from the current slot into the other.
+// Whole columns per workgroup (k_fb_iter): parallelism = strips x directions x pairs
+static int fb_iterate_fused(FbRun &r, const FbLevel &l)
+{
+    const tf_farneback_params *p = r.c.p;
+    const int B = r.B, nd = r.nd, h = l.h, w = l.w, nx = (int)fb_strips(w);
+    const int64_t plane = (int64_t)w * h, bs_tmp = r.bs(FB_TMP);
+    float *tmp = r.a[FB_TMP];
+    hipStream_t s = r.c.s;
+    FbIterArgs ia;
+    ia.R[0] = r.a[FB_R0]; ia.R[1] = r.a[FB_R1]; ia.bs_R = r.bs(FB_R0); ia.nd = nd; ia.nx = nx;
+    // The chain in two parts one row group apart (HP form; same flows) is the faster form alone on the GPU (level-0
+    // launch of 21 pairs: 18.0 against 19.7 ms), but its 39 KB of LDS per workgroup fill the CU (4 x 39 = 156 of
+    // 160 KB): in the pipelined benchmark the floods of the finished windows run beside the flow in what the one-lane
+    // form leaves free -- LDS: 160 KB - 4 x 27 KB; registers: 512 - 2 x 224 = 64 per lane and SIMD, which the
+    // connectivity-1 sweep kernels are built to fit (watershed.hip, tests/test_kernel_resources_cpu.py); a kernel that
+    // needs more than 64 cannot start on a SIMD before an iteration workgroup has left its CU -- and with the
+    // two-part form they displace iteration workgroups instead -- the kernel
+    // then reads 1 985 against 1 860 ms per config-F step, the step is the same (4.75 s either way, back to back on one
+    // box).  So it is chosen PER CALL (tf_farneback_params.chain_form): the host layer asks for the two-part form when
+    // nothing is going to run beside this call's flow; a process-wide switch, as in round 4, let one thread's plain
+    // create_flow turn it on under another thread's pipelined one.
+    const bool whole_chain = p->chain_form != TF_FB_CHAIN_TWO_PART;
+    // sequential row sums: the strips' hand-over words and the launches' ticket counters live in the blur scratch,
+    // idle from the polynomial expansion of this level to the blur of the next: [1 KB of counters][words] per pair
+    // (fb_hand_floats: the phase's tmp stride holds them for both directions at every level)
+    const size_t hand_words = (size_t)nd * (size_t)(nx - 1) * (size_t)h * FBI_HW;
+    // column groups: one per round of resident workgroups (four two-wave workgroups per CU, one direction each)
+    const int slots = fb_resident_slots();                           // of THIS device
+    const int rounds = (int)(((int64_t)nx * B * 2 + slots - 1) / slots), n_groups = std::min(rounds, nx);
+    ia.nb = B; ia.nxg = (nx + n_groups - 1) / n_groups;
+    ia.hand = (unsigned long long *)((char *)tmp + FBI_HDR); ia.bs_hand = bs_tmp / 2; ia.ticket = (int *)tmp; ia.epoch = 0;
+    const int starve_polls = fb_test_starve_polls();
+    ia.starve = starve_polls >= 0;
+    ia.poll_limit = ia.starve ? starve_polls : (1 << 22);
+    ia.starved = fb_starved_word(true, p->status_slot);
+    if (!ia.starved) { tf_set_error("tf_farneback: no pinned status word for the iteration kernel (hipHostMalloc failed)"); return TF_EHIP; }
+    TF_REQUIRE(fb_hand_floats(l) <= (size_t)bs_tmp, "tf_farneback: blur scratch too small for the strips' hand-over words");
+    TF_REQUIRE(p->num_iters <= 250, "tf_farneback: more than 250 iterations per level");
+    TF_CHECK_HIP(hipMemsetAsync(tmp, 0, FBI_HDR, s));
+    for (int b = 0; b < B && hand_words > 0; b++) TF_CHECK_HIP(hipMemsetAsync((char *)(tmp + (int64_t)b * bs_tmp) + FBI_HDR, 0, hand_words * 8, s));
+    const dim3 gi((unsigned)(nx * B * nd));
+    for (int it = 0; it < p->num_iters; it++) {
+        for (int q = 0; q < nd; q++) {
+            const int d = r.dirs[q];
+            ia.dir[q] = d;
+            ia.fin[q] = r.slot[d][r.cur]; ia.bs_fin[q] = r.slot_bs[d][r.cur];
+            ia.fout[q] = r.slot[d][1 - r.cur]; ia.bs_fout[q] = r.slot_bs[d][1 - r.cur];
+        }
+        {
+            TfProfScope ps(TFK_FB_ITER, 56.0 * plane * nd * B, s);
+            ia.epoch = (unsigned)(it + 1); ia.ticket = (int *)tmp + 16 * it;
+            if (whole_chain) hipLaunchKernelGGL((k_fb_iter<FBI_NB, 0>), gi, dim3(FBI_T), 0, s, ia, h, w, plane);
+            else hipLaunchKernelGGL((k_fb_iter<FBI_NB, 1>), gi, dim3(FBI_T), 0, s, ia, h, w, plane);
+        }
+        r.cur = 1 - r.cur;
+    }
+    TF_CHECK_LAUNCH();
+    return TF_OK;
+}
+
+// step 3, any other window size: separate UpdateMatrices / box-filter+solve kernels, one pair at a time, in place
+static int fb_iterate_generic(const FbRun &r, const FbLevel &l)
+{
+    const int h = l.h, w = l.w, num_iters = r.c.p->num_iters, m = r.c.p->win_size / 2;
+    const int64_t plane = (int64_t)w * h, bs_R = r.bs(FB_R0);
+    hipStream_t s = r.c.s;
+    const dim3 block(64, 4), glev1((w + 63) / 64, (h + 3) / 4, 1), gt((w + FBT_W - 1) / FBT_W, (h + FBT_H - 1) / FBT_H);
+    for (int b = 0; b < r.B; b++)
+        for (int q = 0; q < r.nd; q++) {
+            const int d = r.dirs[q];
+            float *flow = r.slot[d][r.cur] + (int64_t)b * r.slot_bs[d][r.cur];
+            const float *R0 = r.a[FB_R0 + d] + (int64_t)b * bs_R, *R1 = r.a[FB_R0 + 1 - d] + (int64_t)b * bs_R;
+            float *Mb = r.a[FB_M] + (int64_t)b * bs_R;
+            {
+                TfProfScope ps(TFK_FB_MATRICES, 68.0 * plane, s);
+                hipLaunchKernelGGL(k_fb_update_matrices, glev1, block, 0, s, R0, R1, flow, h, w, plane, Mb);
+            }
+            for (int it = 0; it < num_iters; it++) {
+                {
+                    TfProfScope ps(TFK_FB_BLUR_SOLVE, 28.0 * plane, s);
+                    hipLaunchKernelGGL(k_fb_blur_solve, gt, block, 0, s, Mb, h, w, plane, m, flow);
+                }
+                if (it < num_iters - 1) {
+                    TfProfScope ps(TFK_FB_MATRICES, 68.0 * plane, s);
+                    hipLaunchKernelGGL(k_fb_update_matrices, glev1, block, 0, s, R0, R1, flow, h, w, plane, Mb);
+                }
+            }
+        }
+    TF_CHECK_LAUNCH();
+    return TF_OK;
+}
+
+// the levels of phase ph, coarse to fine, for the pairs b0 .. b0 + B - 1 of a call; their scratch is carved from the front of
+// the call's workspace (that of an earlier phase or part is dead by then: stream order)
+static int fb_run_levels(const FbCall &c, const FbPhase &ph, int b0, int B)
+{
+    FbRun r = {c, ph, B};
+    size_t off[FB_ARRAYS];
+    if (fb_carve_offsets(ph, B, off) > c.ws_bytes) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
+    for (int i = 0; i < FB_ARRAYS; i++) r.a[i] = ph.stride[i] ? (float *)((char *)c.ws + off[i]) : nullptr;
+    for (int d = 0; d < 2; d++) {
+        r.img[d] = c.img[d] + (int64_t)b0 * c.img_stride;
+        if (c.out[d]) r.dirs[r.nd++] = d;
+        r.slot[d][0] = c.out[d] ? c.out[d] + (int64_t)b0 * c.flow_stride : nullptr; r.slot_bs[d][0] = c.flow_stride;
+        r.slot[d][1] = r.a[FB_F0 + d]; r.slot_bs[d][1] = r.bs(FB_F0);
+    }
+    r.cur = ph.slot; r.pw = ph.pw; r.phh = ph.ph;
+    for (int k = ph.k_hi; k >= ph.k_lo; k--) {
+        const FbLevel l = fb_level(c.H, c.W, c.p, k);
+        int rc;
+        if ((rc = fb_level_images(r, l)) || (rc = fb_level_flow(r, l)) || (rc = ph.fused ? fb_iterate_fused(r, l) : fb_iterate_generic(r, l))) return rc;
+        r.pw = l.w; r.phh = l.h;
+    }
+    // a phase ends on level 0 or on FB_SPLIT_LEVEL: either way its flow has to sit in slot 0, the caller's frames
+    if (r.cur != 0) { tf_set_error("tf_farneback: internal slot parity error"); return TF_EINVAL; }
+    return TF_OK;
+}
+
+// ---- entry points ----------------------------------------------------------------------------------------------------------
+// The argument checks of every driver (batch_ok / bad_batch: what the entry point asks of its own extra argument; must_split:
+// it runs half a split batch; need_bytes: its size function's figure) and, once they pass, what every call begins with: the
+// one report of a starved word that an earlier call's launches left behind, and the expansion's coefficients.
+static int fb_check_args(FbCall *c, const uint8_t *prev, const uint8_t *next, int64_t B64, int64_t img_stride, int64_t H64, int64_t W64,
+                         const tf_farneback_params *p, float *flow_fwd, float *flow_bwd, int64_t flow_stride, void *ws, size_t ws_bytes, void *stream,
+                         bool batch_ok, const char *bad_batch, bool must_split, size_t need_bytes)
 {
     TF_REQUIRE(prev && next && p && ws, "tf_farneback: null pointer");
     TF_REQUIRE(flow_fwd || flow_bwd, "tf_farneback: both outputs are NULL");
-    TF_REQUIRE(B64 >= 1 && B64 <= 1024 && parts64 >= 1, "tf_farneback: bad batch size");
+    TF_REQUIRE(B64 >= 1 && B64 <= 1024 && batch_ok, bad_batch);
     TF_REQUIRE(H64 > 0 && W64 > 0 && H64 < (1 << 15) && W64 < (1 << 15), "tf_farneback: bad shape");
     TF_REQUIRE(img_stride >= H64 * W64 && flow_stride >= H64 * W64 * 2, "tf_farneback: strides smaller than one frame");
     TF_REQUIRE(p->poly_n >= 1 && p->poly_n <= FB_MAX_POLY_N, "tf_farneback: poly_n out of range");
     TF_REQUIRE(p->win_size >= 1 && p->win_size / 2 <= FB_MAX_M, "tf_farneback: win_size out of range");
     TF_REQUIRE(p->num_iters >= 1 && p->num_levels >= 0 && p->pyr_scale > 0 && p->pyr_scale < 1, "tf_farneback: bad params");
-    if (ws_bytes < tf_farneback_workspace_bytes_split(B64, parts64, H64, W64, p)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-    if (const int rc0 = fb_report_starved("tf_farneback (an earlier call's launches)", p->status_slot)) return rc0;
-    const int H = (int)H64, W = (int)W64, B = (int)B64;
-    hipStream_t s = (hipStream_t)stream;
-    const bool fused = p->win_size == FBI_WIN;
-    FbPoly pp; fb_prepare_poly(p->poly_n, p->poly_sigma, &pp);
-    const int levels = fb_levels(H, W, p);
-    float *const out[2] = {flow_fwd, flow_bwd};
-    int cur[2] = {-1, -1};                       // slot index that holds the current flow of direction d
-    int pw = 0, ph = 0;
-    int parts = (int)(parts64 > B ? B : parts64);
-    if (levels < FB_SPLIT_LEVEL || B < 2 || p->pyr_scale != 0.5) parts = 1;     // (only then is every coarse level a sampled blur: no full-size plane)
-    if (parts == 1) {
-        TfArena ar(ws, ws_bytes);
-        FbScratch S;
-        if (!fb_carve(ar, B, fb_full_tmp_floats(H, W, p), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-        const int rc = fb_run_levels(prev, next, B, img_stride, H, W, p, out, flow_stride, S, levels, 0, cur, &pw, &ph, pp, s);
-        if (rc) return rc;
-    } else {
-        // SPLIT BATCH (round 4).  A launch of the iteration kernel costs whole rounds of resident workgroups; at the coarse
-        // levels a round holds the strips of ~40 pairs, at full resolution those of ~10 -- but the scratch of a pair is sized by
-        // its full-resolution planes.  So the levels >= 2 run for ALL pairs of the batch at once, with scratch strides of the
-        // level-2 plane (1 / 16 of a full one), and leave their flow in the caller's output frames; the two finest levels then
-        // run part by part on full-size scratch for B / parts pairs.  Same kernels on the same data: the results are those
-        // of the unsplit batch.  (Every level flips the ping-pong slot num_iters + 1 times, and two levels remain: the flow
-        // of level 2 is in slot 0, the caller's buffer, whatever the parity of num_iters.)
-        {
-            size_t t = 0, pl = 0;
-            fb_phase_sizes(H, W, p, levels, FB_SPLIT_LEVEL, &t, &pl);
-            TfArena ar(ws, ws_bytes);
-            FbScratch S;
-            if (!fb_carve(ar, B, t, pl, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-            const int rc = fb_run_levels(prev, next, B, img_stride, H, W, p, out, flow_stride, S, levels, FB_SPLIT_LEVEL, cur, &pw, &ph, pp, s);
-            if (rc) return rc;
-            for (int d = 0; d < 2; d++) if (out[d] && cur[d] != 0) { tf_set_error("tf_farneback: internal slot parity error (split)"); return TF_EINVAL; }
-        }
-        const int per = (B + parts - 1) / parts;
-        for (int b0 = 0; b0 < B; b0 += per) {
-            const int Bp = B - b0 < per ? B - b0 : per;
-            TfArena ar(ws, ws_bytes);                                 // (the coarse phase's scratch is dead: stream order)
-            FbScratch S;
-            if (!fb_carve(ar, Bp, fb_full_tmp_floats(H, W, p), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-            float *const outp[2] = {flow_fwd ? flow_fwd + (int64_t)b0 * flow_stride : nullptr, flow_bwd ? flow_bwd + (int64_t)b0 * flow_stride : nullptr};
-            int curp[2] = {cur[0], cur[1]}, pwp = pw, php = ph;
-            const int rc = fb_run_levels(prev + (int64_t)b0 * img_stride, next + (int64_t)b0 * img_stride, Bp, img_stride, H, W, p, outp, flow_stride, S,
-                                         FB_SPLIT_LEVEL - 1, 0, curp, &pwp, &php, pp, s);
-            if (rc) return rc;
-            if (b0 + per >= B) { cur[0] = curp[0]; cur[1] = curp[1]; }
-        }
-    }
-    for (int d = 0; d < 2; d++)
-        if (out[d] && cur[d] != 0) { tf_set_error("tf_farneback: internal slot parity error"); return TF_EINVAL; }
+    TF_REQUIRE(!must_split || fb_can_split(H64, W64, p), "tf_farneback_batch_phase: this geometry does not split (tf_farneback_can_split)");
+    if (ws_bytes < need_bytes) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
+    if (const int rc = fb_report_starved("tf_farneback (an earlier call's launches)", p->status_slot)) return rc;
+    *c = FbCall{{prev, next}, {flow_fwd, flow_bwd}, (int)B64, img_stride, flow_stride, (int)H64, (int)W64, p, ws, ws_bytes, (hipStream_t)stream, {}};
+    fb_prepare_poly(p->poly_n, p->poly_sigma, &c->pp);
+    return TF_OK;
+}
+
+// one whole phase, or (split batch, fb_plan.h) the coarse phase for all pairs and then the fine phase part by part
+extern "C" int tf_farneback_batch_split(const uint8_t *prev, const uint8_t *next, int64_t B64, int64_t parts64, int64_t img_stride,
+                                        int64_t H64, int64_t W64, const tf_farneback_params *p,
+                                        float *flow_fwd, float *flow_bwd, int64_t flow_stride,
+                                        void *ws, size_t ws_bytes, void *stream)
+{
+    FbCall c; int rc;
+    if ((rc = fb_check_args(&c, prev, next, B64, img_stride, H64, W64, p, flow_fwd, flow_bwd, flow_stride, ws, ws_bytes, stream,
+                            parts64 >= 1, "tf_farneback: bad batch size", false, fb_bytes_split(B64, parts64, H64, W64, p)))) return rc;
+    const int parts = (int)fb_parts(c.B, parts64, c.H, c.W, p);
+    if (parts == 1) return fb_run_levels(c, fb_phase(c.H, c.W, p, FB_WHOLE), 0, c.B);
+    if ((rc = fb_run_levels(c, fb_phase(c.H, c.W, p, FB_COARSE), 0, c.B))) return rc;
+    const FbPhase fine = fb_phase(c.H, c.W, p, FB_FINE);
+    const int per = (c.B + parts - 1) / parts;
+    for (int b0 = 0; b0 < c.B; b0 += per)
+        if ((rc = fb_run_levels(c, fine, b0, std::min(per, c.B - b0)))) return rc;
     return TF_OK;
 }
 
@@ -2010,62 +1901,18 @@ extern "C" int tf_farneback_batch(const uint8_t *prev, const uint8_t *next, int6
 }
 
 // The two halves of a split batch as calls of their own, for a caller that does something between the parts (create_flow
-// refines and smooths a part and hands its frames out before the next part's finest levels run):
-//   phase 1  pyramid levels >= 2 for B pairs; their flow is left in the output frames
-//   phase 2  levels 1 and 0 for B pairs whose output frames hold the flow of level 2 (a part of the pairs of phase 1)
-extern "C" int tf_farneback_can_split(int64_t H, int64_t W, const tf_farneback_params *p)
-{
-    return (p && H > 0 && W > 0 && fb_levels(H, W, p) >= FB_SPLIT_LEVEL && p->pyr_scale == 0.5) ? 1 : 0;
-}
-extern "C" size_t tf_farneback_workspace_bytes_phase(int64_t B, int64_t H, int64_t W, const tf_farneback_params *p, int phase)
-{
-    if (B <= 0 || H <= 0 || W <= 0 || !p || !tf_farneback_can_split(H, W, p)) return 0;
-    if (phase == 2) return tf_farneback_workspace_bytes_batch(B, H, W, p);
-    size_t t = 0, pl = 0;
-    fb_phase_sizes((int)H, (int)W, p, fb_levels(H, W, p), FB_SPLIT_LEVEL, &t, &pl);
-    return (size_t)B * fb_scratch_floats(t, pl, p->win_size == FBI_WIN) * sizeof(float) + 8192;
-}
+// refines and smooths a part and hands its frames out before the next part's finest levels run): phase 1 = FB_COARSE for B
+// pairs, phase 2 = FB_FINE for B pairs whose output frames hold the flow of level 2 (a part of the pairs of phase 1)
 extern "C" int tf_farneback_batch_phase(const uint8_t *prev, const uint8_t *next, int64_t B64, int64_t img_stride,
                                         int64_t H64, int64_t W64, const tf_farneback_params *p,
                                         float *flow_fwd, float *flow_bwd, int64_t flow_stride,
                                         void *ws, size_t ws_bytes, void *stream, int phase)
 {
-    TF_REQUIRE(prev && next && p && ws, "tf_farneback: null pointer");
-    TF_REQUIRE(flow_fwd || flow_bwd, "tf_farneback: both outputs are NULL");
-    TF_REQUIRE(B64 >= 1 && B64 <= 1024 && (phase == 1 || phase == 2), "tf_farneback: bad batch size / phase");
-    TF_REQUIRE(H64 > 0 && W64 > 0 && H64 < (1 << 15) && W64 < (1 << 15), "tf_farneback: bad shape");
-    TF_REQUIRE(img_stride >= H64 * W64 && flow_stride >= H64 * W64 * 2, "tf_farneback: strides smaller than one frame");
-    TF_REQUIRE(p->poly_n >= 1 && p->poly_n <= FB_MAX_POLY_N, "tf_farneback: poly_n out of range");
-    TF_REQUIRE(p->win_size >= 1 && p->win_size / 2 <= FB_MAX_M, "tf_farneback: win_size out of range");
-    TF_REQUIRE(p->num_iters >= 1 && p->num_levels >= 0 && p->pyr_scale > 0 && p->pyr_scale < 1, "tf_farneback: bad params");
-    TF_REQUIRE(tf_farneback_can_split(H64, W64, p), "tf_farneback_batch_phase: this geometry does not split (tf_farneback_can_split)");
-    if (ws_bytes < tf_farneback_workspace_bytes_phase(B64, H64, W64, p, phase)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-    if (const int rc0 = fb_report_starved("tf_farneback (an earlier call's launches)", p->status_slot)) return rc0;
-    const int H = (int)H64, W = (int)W64, B = (int)B64;
-    hipStream_t s = (hipStream_t)stream;
-    const bool fused = p->win_size == FBI_WIN;
-    FbPoly pp; fb_prepare_poly(p->poly_n, p->poly_sigma, &pp);
-    const int levels = fb_levels(H, W, p);
-    float *const out[2] = {flow_fwd, flow_bwd};
-    TfArena ar(ws, ws_bytes);
-    FbScratch S;
-    if (phase == 1) {
-        size_t t = 0, pl = 0;
-        fb_phase_sizes(H, W, p, levels, FB_SPLIT_LEVEL, &t, &pl);
-        if (!fb_carve(ar, B, t, pl, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-        int cur[2] = {-1, -1}, pw = 0, ph = 0;
-        const int rc = fb_run_levels(prev, next, B, img_stride, H, W, p, out, flow_stride, S, levels, FB_SPLIT_LEVEL, cur, &pw, &ph, pp, s);
-        if (rc) return rc;
-        for (int d = 0; d < 2; d++) if (out[d] && cur[d] != 0) { tf_set_error("tf_farneback: internal slot parity error (phase 1)"); return TF_EINVAL; }
-        return TF_OK;
-    }
-    if (!fb_carve(ar, B, fb_full_tmp_floats(H, W, p), (size_t)H * W, fused, &S)) { tf_set_error("tf_farneback: workspace too small"); return TF_ENOMEM; }
-    int cur[2] = {0, 0}, pw = 0, ph = 0;                              // the flow of level FB_SPLIT_LEVEL sits in slot 0 = the output frames
-    fb_level_size(H, W, p, FB_SPLIT_LEVEL, &ph, &pw);
-    const int rc = fb_run_levels(prev, next, B, img_stride, H, W, p, out, flow_stride, S, FB_SPLIT_LEVEL - 1, 0, cur, &pw, &ph, pp, s);
-    if (rc) return rc;
-    for (int d = 0; d < 2; d++) if (out[d] && cur[d] != 0) { tf_set_error("tf_farneback: internal slot parity error (phase 2)"); return TF_EINVAL; }
-    return TF_OK;
+    FbCall c; int rc;
+    if ((rc = fb_check_args(&c, prev, next, B64, img_stride, H64, W64, p, flow_fwd, flow_bwd, flow_stride, ws, ws_bytes, stream,
+                            phase == 1 || phase == 2, "tf_farneback: bad batch size / phase", true,
+                            tf_farneback_workspace_bytes_phase(B64, H64, W64, p, phase)))) return rc;
+    return fb_run_levels(c, fb_phase(c.H, c.W, p, phase == 1 ? FB_COARSE : FB_FINE), 0, c.B);
 }
 
 extern "C" int tf_farneback_pair(const uint8_t *prev, const uint8_t *next, int64_t H, int64_t W,
@@ -2098,3 +1945,4 @@ extern "C" int tf_farneback_expansion(const uint8_t *img, int64_t H64, int64_t W
     if (!blur_out) TF_CHECK_HIP(hipFreeAsync(blur, s));
     return TF_OK;
 }
+
