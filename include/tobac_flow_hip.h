@@ -47,7 +47,7 @@ extern "C" {
 #define TF_F32 0
 #define TF_F64 1
 #define TF_I32 2
-#define TF_U8 3          /* tf_edt2d_frames, tf_label_nanmin, tf_label_filter only (bool arrays have these bytes) */
+#define TF_U8 3          /* tf_edt2d_frames, tf_label_nanmin, tf_label_filter, tf_label_reduce, tf_label_order only (bool arrays have these bytes) */
 #define TF_I16 4         /* tf_prepare_fields only: a packed channel */
 #define TF_I8 5          /* tf_stripe_deviation, tf_prepare_fields only: a DQF plane */
 
@@ -726,6 +726,43 @@ size_t tf_label_proportions_workspace_bytes(int64_t n_labels, int n_flags);
 int tf_label_proportions(const int32_t *labels, const int32_t *flags, const float *weights, int64_t T, int64_t hw,
                          int weights_plane, int64_t n_labels, const int32_t *flag_values_host, int n_flags, double *out,
                          void *ws, size_t ws_bytes, void *stream);
+/* tf_label_reduce (version 110): what tobac_flow/utils/label_utils.py:8-55 (`labeled_comprehension`) and :58-140
+ *   (`apply_func_to_labels`) need of a region when `func` is a plain NumPy reducer, for every label id of the span
+ *   [id_lo, id_hi] in one read of the volume.  labels: int32 (T * hw,); ids outside the span are background, 0 and
+ *   negative ids inside it are regions like any other (ndi.labeled_comprehension accepts them in `index`).  field: TF_U8
+ *   (bool), TF_I32, TF_F32 or TF_F64, nothing is cast down, in one of three layouts that are never materialised:
+ *     layout 0  a volume (T * hw,)      layout 1  ONE (hw,) plane shared by every frame (area[None])
+ *     layout 2  ONE value per frame, (T,) (bt.t.data[:, None, None])
+ *   records: (id_hi - id_lo + 1) records of eight 64-bit words (64 B, one line) on the device, record id - id_lo:
+ *     0  int64 number of voxels            1  int64 number of voxels whose value is not NaN
+ *     2  int64 number of voxels whose value is != 0 (NaN counts, as np.any / np.count_nonzero see it)
+ *     3  sum of the non-NaN values: double for TF_F32 / TF_F64, int64 for TF_U8 / TF_I32
+ *     4  key of the smallest non-NaN value, 5 of the largest: k(x) = bits of (x + 0.0) as double, all bits inverted where
+ *        the sign is set, else the sign bit set; unsigned order = order of the values, +-inf take part, -0.0 and +0.0 share
+ *        a key.  Without a non-NaN value slot 4 is 2^64 - 1 and slot 5 is 0
+ *     6  sum of (x - mean)^2 over the non-NaN values, double, mean = slot 3 / slot 1; written only with want & 1 (a finish
+ *        per label and a second read of labels and field: NumPy's two-pass form), else 0        7  spare, 0
+ *   Exact and independent of arrival order: slots 0, 1, 2, 4, 5 and the int64 slot 3 (integer atomics).  The double slot 3
+ *   and slot 6 are double atomics, one per run of equal labels a lane meets, so their last bits depend on arrival order:
+ *   N terms differ from the exactly rounded sum by at most N * 2^-53 * sum |term|.  inf + (-inf) gives NaN as in NumPy.
+ *   16 voxels per lane, background lanes load the labels only, wide loads where base and layout are 16-byte aligned,
+ *   64-bit indexing throughout.  Limits: id_hi - id_lo < 2^27 (8 GiB of records), INT32_MIN < id_lo <= id_hi <= INT32_MAX;
+ *   beyond them TF_EINVAL before any launch.  The workspace (needed with want & 1 only) holds one double per id.
+ * tf_label_order (version 110): the order statistics np.median / np.nanmedian need, same operands and span.  records:
+ *   what tf_label_reduce left for these operands; n_keys: the sum of their slot 1 (the caller has downloaded them).
+ *   out[2 * (id - id_lo)], out[.. + 1] (double, device) = the two middle values of the id's non-NaN values in ascending
+ *   order, elements (c - 1) / 2 and c / 2 of c; equal for an odd c, NaN for c = 0.  Exact.  Slot-1 counts -> exclusive scan
+ *   -> every non-NaN voxel of the span puts a 32-bit order key (64-bit for TF_F64) into its label's segment through one
+ *   atomic cursor per label -> rocPRIM segmented radix sort -> pick.  A zero comes back as +0.0.  Records that do not
+ *   belong to the operands are not trusted for any address: places beyond a segment or n_keys are not written or read.
+ *   n_keys <= 2^31 - 1.  The workspace scales with n_keys and the span, not with the volume (a span that contains 0
+ *   makes the background a region and n_keys the volume). */
+size_t tf_label_reduce_workspace_bytes(int64_t id_lo, int64_t id_hi);
+int tf_label_reduce(const int32_t *labels, const void *field, int dtype, int layout, int64_t T, int64_t hw, int64_t id_lo,
+                    int64_t id_hi, int want, void *records, void *ws, size_t ws_bytes, void *stream);
+size_t tf_label_order_workspace_bytes(int64_t id_lo, int64_t id_hi, int64_t n_keys, int dtype);
+int tf_label_order(const int32_t *labels, const void *field, int dtype, int layout, int64_t T, int64_t hw, int64_t id_lo,
+                   int64_t id_hi, const void *records, int64_t n_keys, double *out, void *ws, size_t ws_bytes, void *stream);
 size_t tf_slice_labels_workspace_bytes(int64_t T, int64_t id_capacity);
 int tf_slice_labels(const int32_t *labels, int64_t T, int64_t hw, int32_t *out, int64_t *n_step_labels_host,
                     void *ws, size_t ws_bytes, void *stream);

@@ -187,6 +187,12 @@ _PROTOS = {
     "tf_label_wstats": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_proportions_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int]),
     "tf_label_proportions": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
+    "tf_label_reduce_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    "tf_label_reduce": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _P,
+                                   _c.c_size_t, _P]),
+    "tf_label_order_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64, _c.c_int]),
+    "tf_label_order": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P,
+                                  _P, _c.c_size_t, _P]),
     "tf_edt2d_frames_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64]),
     "tf_edt2d_frames": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
     "tf_edt_cylinder": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P]),

@@ -1,5 +1,6 @@
 // What the per-label reduction kernels share: the work layouts, the vector loads, and the two walkers that take a lane
-// through its voxels as runs of equal labels.  Users: wstats_kernels.h, edt_kernels.h (tf_label_nanmin), props.hip;
+// through its voxels as runs of equal labels.  Users: wstats_kernels.h, edt_kernels.h (tf_label_nanmin), props.hip,
+// label_reduce_kernels.h (the span form of the raveled walker);
 // label_filter.hip takes the row-chunk layout and its launch geometry and keeps its own loop (see there); bin_kernels.h
 // and subseg.hip take the loads and the alignment predicate only.  The same text compiles
 // for the host (tools/*_host_check.cpp supply blockIdx-free bodies, the vector types and the atomics).  Nothing here
@@ -106,13 +107,14 @@ __host__ __device__ __forceinline__ void lr_load_weights(const F *__restrict__ w
 //   void open(l, in, j) start a run of id l at voxel j; `in`: l is in [1, n_labels].  Called for other ids too: such a run
 //                       gathers nothing, so its close issues nothing
 //   void add(i, j)      voxel j of the step (raveled index i + j), called for ids in [1, n_labels] only
-template <int N, typename V>
-__device__ __forceinline__ void lr_runs(const int32_t (&lv)[N], int64_t i, int64_t n_labels, int32_t &cur, V &v)
+// The ids that count are those of the span [lo, hi] (lr_runs: [1, n_labels]); every other id is background.
+template <int N, typename V, typename Lo>
+__device__ __forceinline__ void lr_runs_span(const int32_t (&lv)[N], int64_t i, Lo lo, int64_t hi, int32_t &cur, V &v)
 {
 #pragma unroll
     for (int j = 0; j < N; j++) {
         const int32_t l = lv[j];
-        const bool in = l >= 1 && l <= n_labels;
+        const bool in = l >= lo && l <= hi;
         if (l != cur || v.ends(j)) {
             v.close(cur);
             cur = l;
@@ -122,17 +124,25 @@ __device__ __forceinline__ void lr_runs(const int32_t (&lv)[N], int64_t i, int64
     }
 }
 
+template <int N, typename V>
+__device__ __forceinline__ void lr_runs(const int32_t (&lv)[N], int64_t i, int64_t n_labels, int32_t &cur, V &v)
+{
+    lr_runs_span<N>(lv, i, 1, n_labels, cur, v);                  // lo as the int it is: the code of before the span form
+}
+
 // ---- the raveled walker ----------------------------------------------------------------------------------------------
 // One lane's 16 voxels of the raveled layout above.  Besides the hooks of lr_runs the visitor supplies
 //   void load(i, m, full)  the other operands of the step's voxels i .. i + m - 1 (full: m == 4), called only for steps
 //                          that hold an id in [1, n_labels]
 //   void last(tid, id)     the run still open after the last step (a plain close for all but tf_label_nanmin)
 // vec: `labels` is 16-byte aligned.  Every lane of the workgroup reaches `last` (no early return).
-template <typename V>
-__device__ __forceinline__ void lr_walk(int64_t block, int tid, const int32_t *__restrict__ labels, int64_t n, bool vec,
-                                        int64_t n_labels, V &v)
+// lr_walk_span: the ids of the span [lo, hi] count instead (tf_label_reduce: 0 and negative ids are regions like any
+// other there); `none` is an id OUTSIDE the span that stands for "no open run".
+template <typename V, typename Lo>
+__device__ __forceinline__ void lr_walk_span(int64_t block, int tid, const int32_t *__restrict__ labels, int64_t n, bool vec,
+                                             Lo lo, int64_t hi, int32_t none, V &v)
 {
-    int32_t cur = 0;
+    int32_t cur = none;
 #pragma unroll
     for (int step = 0; step < LR_ITERS; step++) {
         const int64_t i = lr_first_voxel(block, tid, step);
@@ -140,15 +150,22 @@ __device__ __forceinline__ void lr_walk(int64_t block, int tid, const int32_t *_
         const int m = n - i < LR_VEC ? (int)(n - i) : LR_VEC;
         const bool full = m == LR_VEC;
         int32_t lv[LR_VEC];
-        lr_load4<int32_t>(labels, i, m, vec && full, lv, 0);
+        lr_load4<int32_t>(labels, i, m, vec && full, lv, none);
         bool any = false;
 #pragma unroll
-        for (int j = 0; j < LR_VEC; j++) any |= lv[j] >= 1 && lv[j] <= n_labels;
-        if (!any) { v.close(cur); cur = 0; continue; }            // background costs nothing more
+        for (int j = 0; j < LR_VEC; j++) any |= lv[j] >= lo && lv[j] <= hi;
+        if (!any) { v.close(cur); cur = none; continue; }         // background costs nothing more
         v.load(i, m, full);
-        lr_runs<LR_VEC>(lv, i, n_labels, cur, v);
+        lr_runs_span<LR_VEC>(lv, i, lo, hi, cur, v);
     }
     v.last(tid, cur);
+}
+
+template <typename V>
+__device__ __forceinline__ void lr_walk(int64_t block, int tid, const int32_t *__restrict__ labels, int64_t n, bool vec,
+                                        int64_t n_labels, V &v)
+{
+    lr_walk_span(block, tid, labels, n, vec, 1, n_labels, 0, v);
 }
 
 // ---- the row-chunk walker --------------------------------------------------------------------------------------------

@@ -540,3 +540,138 @@ def label_nanmin(labels, field, ids):
                                  _lib.ptr(mins), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                "tf_label_nanmin")
     return mins, counts
+
+
+# ---- generic per-label reductions (tf_label_reduce, tf_label_order) ----------------------------------------------------
+LABEL_REDUCE_OPS = ("size", "count", "nonzero", "sum", "min", "max", "ssd")
+_INT32_MIN, _INT32_MAX, _LABEL_REDUCE_MAX_SPAN = -2 ** 31, 2 ** 31 - 1, 2 ** 27
+
+
+def _reduce_operands(labels, field):
+    """(labels int32 (n,), field, TF dtype, layout, T, hw) for tf_label_reduce / tf_label_order.  The field keeps its
+    dtype where the kernels take it (bool as its bytes; narrower integers and floats are widened exactly to int32 /
+    float32) and its layout: a volume, one plane that every frame shares (leading axes of length 1) or one value per
+    frame (trailing axes of length 1); any other broadcast is materialised."""
+    t = _lib.torch()
+    if field.dtype == t.bool:
+        field = field.view(t.uint8) if field.is_contiguous() else field.to(t.uint8)
+    elif field.dtype in (t.int8, t.int16):
+        field = field.to(t.int32)
+    elif field.dtype in (t.float16, t.bfloat16):
+        field = field.to(t.float32)
+    elif field.dtype not in (t.uint8, t.int32, t.float32, t.float64):
+        raise TypeError(f"per-label reductions on the GPU take bool, (u)int8, int16, int32, float16, float32 and float64 "
+                        f"fields, not {field.dtype}: pass NumPy arrays for the host path")
+    shape = tuple(t.broadcast_shapes(tuple(labels.shape), tuple(field.shape)))
+    if tuple(labels.shape) != shape:
+        labels = labels.expand(shape)
+    lab = labels.to(t.int32).contiguous().reshape(-1)
+    n = lab.numel()
+    fs = (1,) * (len(shape) - field.dim()) + tuple(field.shape)
+    code = {t.uint8: _lib.TF_U8, t.int32: _lib.TF_I32, t.float32: _lib.TF_F32, t.float64: _lib.TF_F64}[field.dtype]
+    if fs != shape and n:
+        for k in range(1, len(shape)):
+            hw = int(np.prod(shape[k:]))
+            if all(s == 1 for s in fs[:k]) and fs[k:] == shape[k:]:
+                return lab, field.contiguous().reshape(-1), code, 1, n // hw, hw
+            if fs[:k] == shape[:k] and all(s == 1 for s in fs[k:]):
+                return lab, field.contiguous().reshape(-1), code, 2, n // hw, hw
+        field = field.expand(shape)
+    return lab, field.contiguous().reshape(-1), code, 0, 1, n
+
+
+def _id_span(ids):
+    """(ids as int64, lo, hi) of the ids a label volume can hold; (ids, None, None) when there is none"""
+    ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+    if (ids == _INT32_MIN).any():
+        raise ValueError("per-label reductions on the GPU take label ids above INT32_MIN")
+    held = ids[(ids > _INT32_MIN) & (ids <= _INT32_MAX)]
+    return (ids, int(held.min()), int(held.max())) if held.size else (ids, None, None)
+
+
+def label_records(labels, field, lo, hi, var=False, order=False):
+    """tf_label_reduce over the id span [lo, hi]: the (hi - lo + 1, 8) int64 device tensor of 64-byte records of
+    include/tobac_flow_hip.h (slot 3 of a float field and slot 6 hold the bits of doubles: .view(torch.float64)); with
+    `var` slot 6 is filled (a second read of the volume).  With `order` also tf_label_order's (hi - lo + 1, 2) float64
+    tensor of the two middle values.  A span of 2^27 ids or more is refused by the library before anything is allocated
+    or launched (ValueError)."""
+    t = _lib.torch()
+    L = _lib.lib()
+    lab, f, code, layout, T, hw = _reduce_operands(labels, field)
+    if lab.numel() == 0:
+        raise ValueError("per-label reductions need at least one voxel")
+    want = 1 if var else 0
+    args = (_lib.ptr(lab), _lib.ptr(f), code, layout, T, hw, lo, hi)
+    if hi - lo >= _LABEL_REDUCE_MAX_SPAN or lo <= _INT32_MIN or hi > _INT32_MAX or lo > hi:
+        _lib.check(L.tf_label_reduce(*args, want, None, None, 0, _lib.stream_ptr()), "tf_label_reduce")
+        raise ValueError("tf_label_reduce: bad span")                  # not reached: the library refuses such a span
+    rec = _lib.empty((hi - lo + 1, 8), t.int64)
+    ws = _lib.workspace(L.tf_label_reduce_workspace_bytes(lo, hi), "label_reduce") if var else None
+    _lib.check(L.tf_label_reduce(*args, want, _lib.ptr(rec), _lib.ptr(ws), ws.numel() if var else 0, _lib.stream_ptr()),
+               "tf_label_reduce")
+    if not order:
+        return rec
+    n_keys = int(rec[:, 1].sum())
+    mid = _lib.empty((hi - lo + 1, 2), t.float64)
+    ws = _lib.workspace(L.tf_label_order_workspace_bytes(lo, hi, n_keys, code), "label_order")
+    _lib.check(L.tf_label_order(*args, _lib.ptr(rec), n_keys, _lib.ptr(mid), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "tf_label_order")
+    return rec, mid
+
+
+def _unkey(k):
+    """the double behind an order key of slots 4 / 5 (int64 view of the unsigned key)"""
+    t = _lib.torch()
+    return t.where(k < 0, k & 0x7fffffffffffffff, ~k).view(t.float64)
+
+
+def label_reduce(labels, field, ids, ops=("size", "sum")):
+    """tf_label_reduce: per label id of `ids` (any int64 sequence: unsorted, with duplicates, with ids that do not occur;
+    0 and negative ids are regions like any other) the quantities named in `ops`, as a dict of device tensors (len(ids),):
+      "size" voxels, "count" voxels whose value is not NaN, "nonzero" voxels whose value is != 0 (NaN among them): int64
+      "sum"  of the non-NaN values: float64 for a float field (last bits depend on arrival order), int64 (exact) otherwise
+      "min", "max" of the non-NaN values, exact: float64, NaN where there is none
+      "ssd"  sum of (x - mean)^2 over the non-NaN values about mean = sum / count, float64 (a second read of the volume)
+    `labels` is an integer device tensor, `field` a device tensor that broadcasts against it (_reduce_operands).  The
+    library works on the span [min(ids), max(ids)]: 64 B per id of it, below 2^27 ids (ValueError beyond)."""
+    t = _lib.torch()
+    ops = tuple(ops)
+    unknown = [o for o in ops if o not in LABEL_REDUCE_OPS]
+    if unknown:
+        raise ValueError(f"unknown ops {unknown}: one of {LABEL_REDUCE_OPS}")
+    ids, lo, hi = _id_span(ids)
+    integer = not field.dtype.is_floating_point
+    kinds = {"size": t.int64, "count": t.int64, "nonzero": t.int64, "sum": t.int64 if integer else t.float64}
+    out = {o: t.zeros((ids.size,), dtype=kinds.get(o, t.float64), device=labels.device) for o in ops}
+    for o in ("min", "max"):
+        if o in out:
+            out[o] += float("nan")
+    if lo is None:
+        return out
+    rec = label_records(labels, field, lo, hi, var="ssd" in ops)
+    held = (ids > _INT32_MIN) & (ids <= _INT32_MAX)
+    at = t.from_numpy(np.where(held, ids - lo, 0)).to(rec.device)
+    r = rec[at] * t.from_numpy(held.astype(np.int64)).to(rec.device)[:, None]          # ids no volume can hold: zeros
+    some = r[:, 1] > 0
+    nan = t.full((ids.size,), float("nan"), dtype=t.float64, device=rec.device)
+    take = {"size": lambda: r[:, 0], "count": lambda: r[:, 1], "nonzero": lambda: r[:, 2],
+            "sum": lambda: r[:, 3] if integer else r[:, 3].contiguous().view(t.float64),
+            "min": lambda: t.where(some, _unkey(r[:, 4].contiguous()), nan),
+            "max": lambda: t.where(some, _unkey(r[:, 5].contiguous()), nan),
+            "ssd": lambda: r[:, 6].contiguous().view(t.float64)}
+    return {o: take[o]() for o in ops}
+
+
+def label_order(labels, field, ids):
+    """tf_label_order: (len(ids), 2) float64 device tensor of the two middle values of each label's non-NaN values in
+    ascending order (equal for an odd count, NaN for a label without such a value): np.median's operands.  Exact; a zero
+    comes back as +0.0.  Operands and limits as label_reduce."""
+    t = _lib.torch()
+    ids, lo, hi = _id_span(ids)
+    out = t.full((ids.size, 2), float("nan"), dtype=t.float64, device=labels.device)
+    if lo is None:
+        return out
+    _, mid = label_records(labels, field, lo, hi, order=True)
+    held = (ids > _INT32_MIN) & (ids <= _INT32_MAX)
+    got = mid[t.from_numpy(np.where(held, ids - lo, 0)).to(mid.device)]
+    return t.where(t.from_numpy(held).to(mid.device)[:, None], got, out)

@@ -10,7 +10,7 @@ from tobac_flow_amd.utils.label_utils import (apply_func_to_labels, find_overlap
                                               relabel_objects, remap_labels, slice_labels)
 from tobac_flow_amd.utils.normalisation_utils import (inverse_log_norm, linear_norm, linearise_field, local_linear_norm,
                                                       log_norm, select_normalisation_method, to_8bit, uniform_norm, z_norm)
-from tobac_flow_amd.utils.stats_utils import (get_weighted_proportions, mse, n_unique_along_axis, weighted_average_and_std,
+from tobac_flow_amd.utils.stats_utils import (find_overlap_mode, get_weighted_proportions, mse, n_unique_along_axis, weighted_average_and_std,
                                               weighted_average_uncertainty, weighted_stats,
                                               weighted_stats_and_uncertainties, weighted_uncertainties)
 from tobac_flow_amd.utils.xarray_utils import get_coord_bin_edges
@@ -22,7 +22,7 @@ __all__ = (
     "labeled_comprehension", "make_step_labels", "relabel_objects", "remap_labels", "slice_labels",
     "inverse_log_norm", "linear_norm", "linearise_field", "local_linear_norm", "log_norm",
     "select_normalisation_method", "to_8bit", "uniform_norm", "z_norm",
-    "mse", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
+    "mse", "find_overlap_mode", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
     "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions",
     "get_coord_bin_edges",
 )

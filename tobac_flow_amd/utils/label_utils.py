@@ -1,5 +1,46 @@
-"""Label bookkeeping helpers (host glue in numpy; mirrors
-/root/reference/tobac_flow/utils/label_utils.py -- same names, arguments and results)."""
+"""Label bookkeeping helpers (mirrors the reference's tobac_flow/utils/label_utils.py -- same names, arguments and
+results).  Host glue in numpy, except that `labeled_comprehension` and `apply_func_to_labels` run on the GPU when they are
+handed device tensors and a reducer they recognise.
+
+The device path of the two functions
+------------------------------------
+Taken when `labels` or the field is a torch tensor, `func` is one of the reducers below (recognised by identity, also as
+`functools.partial(f)` with nothing bound), there is exactly one field and `pass_positions` is false.  NumPy inputs keep
+the host code below exactly as it is, whatever `func` is.  Tensors with anything else -- a lambda, np.percentile,
+np.argmin / np.argmax, several fields, a multi-valued function, pass_positions=True -- raise a TypeError that says so:
+those stay on the host path, pass NumPy arrays for it.
+
+    np.sum np.nansum np.mean np.nanmean np.std np.nanstd np.var np.nanvar np.min np.max np.nanmin np.nanmax np.ptp
+    np.any np.all np.count_nonzero np.size len np.median np.nanmedian
+    stats_utils.find_overlap_mode, also partial(find_overlap_mode, background=b)
+
+The volume is read once (twice for var / std) by tf_label_reduce into one 64-byte record per label id, nothing is sorted;
+the medians sort the labelled voxels' keys only (tf_label_order); the mode is tf_pair_counts and a host reduction over the
+distinct (label, value) pairs.  The field may broadcast against the labels: (T, 1, 1), (H, W) and (1, H, W) fields are
+read in place.  The finish -- records to values, the NaN rules, `default`, the cast to `dtype` -- is NumPy on the
+downloaded records, so the cast is NumPy's own.  The result is a device tensor when `labels` was one (a NumPy array when
+torch cannot hold `dtype`), else a NumPy array.  The reference's semantics are kept: `index=None`, `default` for ids
+without voxels, ids that are 0 or negative in `index`, the `.squeeze()` and the IndexError of apply_func_to_labels.
+apply_func_to_labels raises ValueError for negative labels on this path (the reference's min_label arithmetic changes
+its default index there), find_overlap_mode for a negative or non-integer field and for ids below 1.
+
+Contract ("NumPy's result" = func applied to the region's values in C order):
+  exact    len, np.size, np.count_nonzero, np.any, np.all; np.min, np.max, np.nanmin, np.nanmax, np.ptp (NaN where NumPy
+           gives NaN; a zero is returned as +0.0 where NumPy may return -0.0); every sum, mean and median of an integer or
+           bool field (int64 sums, one float64 division); np.median / np.nanmedian of float fields (for an even count
+           NumPy's own midpoint in the field's dtype, fl(fl(a + b) / 2)); find_overlap_mode.
+  bounded  for float fields, against NumPy on the values upcast to float64, u = 2^-53, n = the region's size:
+           np.sum, np.nansum, np.mean, np.nanmean differ by at most n u sum|x| (divided by n for the means) before the one
+           rounding to `dtype`, and from run to run within that (double atomics, one per run of equal labels a lane meets).
+           np.var, np.std and their nan forms are NumPy's two passes: with the device mean m' (|m' - m| <= d = u sum|x|)
+           the identity sum (x - m')^2 = sum (x - m)^2 + n (m' - m)^2 holds exactly, each term carries 3 roundings and the
+           n non-negative terms are added with at most n u relative error, NumPy's own pass as much again:
+           |var' - var| <= (2 n + 8) u var + d^2.  d^2 is below 22 n u var unless var < n u mean|x|^2 / 22 (values that
+           agree to 2^-24 of their magnitude; equal values give exactly 0), which is the 32 n u relative the tests use.
+  NumPy's float32 results (pairwise float32 accumulation) are NOT reproduced bit for bit: the device result is the more
+  accurate one.  np.nansum of an all-NaN region is 0.0, np.nanmean / np.nanmedian / np.nanmin of one NaN; inf + (-inf) is
+  NaN."""
+import functools
 from typing import Callable, Optional
 
 import numpy as np
@@ -12,7 +53,10 @@ def _groups(flat):
 
 
 def labeled_comprehension(field, labels, func, index=None, dtype=None, default=None, pass_positions=False):
-    """ndi.labeled_comprehension with defaults filled in (reference: label_utils.py:8-55)."""
+    """ndi.labeled_comprehension with defaults filled in (reference: label_utils.py:8-55).  Device tensors take the
+    device path of the module docstring."""
+    if _is_tensor(labels) or _is_tensor(field):
+        return _labeled_comprehension_dev(field, labels, func, index, dtype, default, pass_positions)
     if not dtype:
         dtype = field.dtype
     if index is None:
@@ -36,7 +80,10 @@ def apply_func_to_labels(labels, *fields, func: Callable = np.mean, index=None, 
     axis and squeezed; `fields` are broadcast against `labels`.  Labels without pixels give `default`, shaped like what
     func returns (a scalar default is repeated for a multi-valued func; a one-element sequence stands for its element).
     Behaviour of the reference's function of the same name (label_utils.py:58-140); the grouping below is a stable sort
-    of the label image with searchsorted boundaries, so the values of a region reach func in C order."""
+    of the label image with searchsorted boundaries, so the values of a region reach func in C order.  Device tensors take
+    the device path of the module docstring."""
+    if _is_tensor(labels) or any(_is_tensor(f) for f in fields):
+        return _apply_func_to_labels_dev(labels, fields, func, index, default)
     arrays = np.broadcast_arrays(labels, *fields)
     flat_labels = arrays[0].ravel()
     flat_fields = [f.ravel() for f in arrays[1:]]
@@ -166,6 +213,265 @@ def find_overlapping_labels(labels, locs, bins, overlap: float = 0, absolute_ove
     return [lab for lab in np.unique(hit)
             if lab != 0 and counts[lab] > absolute_overlap
             and counts[lab] >= overlap * np.minimum(n_locs, bins[lab] - bins[lab - 1])]
+
+
+# ---- the device path of labeled_comprehension and apply_func_to_labels (module docstring) -----------------------------
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _find_overlap_mode():
+    from tobac_flow_amd.utils.stats_utils import find_overlap_mode
+    return find_overlap_mode
+
+
+def _device_reducers():
+    """{function object: name}: what the device path recognises, by identity"""
+    table = {np.sum: "sum", np.nansum: "nansum", np.mean: "mean", np.nanmean: "nanmean", np.std: "std",
+             np.nanstd: "nanstd", np.var: "var", np.nanvar: "nanvar", np.min: "min", np.max: "max", np.nanmin: "nanmin",
+             np.nanmax: "nanmax", np.ptp: "ptp", np.any: "any", np.all: "all", np.count_nonzero: "count_nonzero",
+             np.size: "size", len: "size", np.median: "median", np.nanmedian: "nanmedian", _find_overlap_mode(): "mode"}
+    return table
+
+
+DEVICE_REDUCERS = ("np.sum", "np.nansum", "np.mean", "np.nanmean", "np.std", "np.nanstd", "np.var", "np.nanvar", "np.min",
+                   "np.max", "np.nanmin", "np.nanmax", "np.ptp", "np.any", "np.all", "np.count_nonzero", "np.size", "len",
+                   "np.median", "np.nanmedian", "find_overlap_mode")
+
+
+def _recognise(func):
+    """(name, background) of a reducer of the device path, None for any other callable"""
+    bound = {}
+    if isinstance(func, functools.partial):
+        if func.args or (func.keywords and (func.func is not _find_overlap_mode() or set(func.keywords) != {"background"})):
+            return None
+        func, bound = func.func, func.keywords
+    try:
+        name = _device_reducers().get(func)
+    except TypeError:                                             # unhashable callable
+        return None
+    return None if name is None else (name, bound.get("background", 0))
+
+
+def _refuse(why):
+    return TypeError(f"{why}: on device tensors labeled_comprehension and apply_func_to_labels take one field and one of "
+                     f"the reducers {', '.join(DEVICE_REDUCERS)} (the function objects themselves, or functools.partial of "
+                     "them without bound arguments; find_overlap_mode also with background=); pass NumPy arrays for the "
+                     "host path")
+
+
+def _field_numpy_dtype(field):
+    from tobac_flow_amd import _lib
+    if not _is_tensor(field):
+        return np.asarray(field).dtype
+    t = _lib.torch()
+    if field.dtype == t.bfloat16:
+        return np.dtype(np.float32)
+    return np.dtype(str(field.dtype).split(".")[-1])
+
+
+def _finish(name, rec, mid, fdtype):
+    """(values, present) per id from the downloaded records (n_ids, 8) int64 and, for the medians, the middle values
+    (n_ids, 2) float64: the reducer `name` as a NumPy expression of the slots, in the dtype NumPy's own result has"""
+    size, count, nonzero = rec[:, 0], rec[:, 1], rec[:, 2]
+    floating = fdtype.kind == "f"
+    total = rec[:, 3].copy().view(np.float64) if floating else rec[:, 3]
+    has_nan, none = size != count, count == 0
+    present = size > 0
+    nan = np.float64("nan")
+
+    def extreme(slot):
+        k = rec[:, slot]
+        return np.where(k < 0, k & np.int64(0x7fffffffffffffff), ~k).view(np.float64)
+
+    def spoil(values, where):                                     # NaN where NumPy's result is NaN (float fields only)
+        return np.where(where, nan, values) if floating else values
+
+    with np.errstate(all="ignore"):
+        if name == "size":
+            return size.astype(np.intp), present
+        if name == "count_nonzero":
+            return nonzero.astype(np.intp), present
+        if name == "any":
+            return nonzero > 0, present
+        if name == "all":
+            return nonzero == size, present
+        if name in ("sum", "nansum"):
+            if not floating:
+                return total.astype(np.uint64 if fdtype.kind == "u" else np.int64), present
+            return spoil(total, has_nan & (name == "sum")), present
+        if name in ("mean", "nanmean"):
+            mean = total.astype(np.float64) / count
+            return np.where(has_nan & (name == "mean"), nan, mean), present
+        if name in ("var", "nanvar", "std", "nanstd"):
+            var = rec[:, 6].copy().view(np.float64) / count
+            var = np.where(has_nan & (name in ("var", "std")), nan, var)
+            return (np.sqrt(var) if name.endswith("std") else var), present
+        if name in ("min", "max", "nanmin", "nanmax", "ptp"):
+            lo, hi = extreme(4), extreme(5)
+            plain = not name.startswith("nan")
+            if name == "ptp":
+                with np.errstate(over="ignore"):
+                    values = np.where(none, 0, hi).astype(fdtype) - np.where(none, 0, lo).astype(fdtype)
+            else:
+                values = np.where(none, 0, lo if name.endswith("min") else hi).astype(fdtype)
+            if floating:
+                values = np.where(none | (has_nan & plain), fdtype.type("nan"), values)
+            return values, present
+        if name in ("median", "nanmedian"):
+            mdtype = fdtype if floating else np.dtype(np.float64)
+            a, b = mid[:, 0].astype(mdtype), mid[:, 1].astype(mdtype)
+            values = np.where(a == b, a, (a + b) / mdtype.type(2))
+            return np.where(none | (has_nan & (name == "median")), mdtype.type("nan"), values).astype(mdtype), present
+    raise AssertionError(name)
+
+
+def _mode_on_device(lab, fld, ids, background, fdtype):
+    """find_overlap_mode per id: tf_pair_counts of (label, value) and, per label, the most frequent value that is not the
+    background, the smallest among ties; the background where there is no other value"""
+    from tobac_flow_amd import _lib
+    from tobac_flow_amd import label as _label
+    t = _lib.torch()
+    if fld.dtype.is_floating_point or fld.dtype == t.bool:
+        raise ValueError("find_overlap_mode on the GPU takes a non-negative integer field")
+    if fld.numel() and int(fld.min()) < 0:
+        raise ValueError("find_overlap_mode on the GPU takes a non-negative integer field: the field has negative values")
+    if ids.size and ids.min() < 1:
+        raise ValueError("find_overlap_mode on the GPU takes label ids >= 1")
+    shape = tuple(t.broadcast_shapes(tuple(lab.shape), tuple(fld.shape)))
+    a, b, c = _label.pair_counts(lab.expand(shape).contiguous(), fld.expand(shape).contiguous(), include_b_zero=True)
+    present = np.isin(ids, a)
+    keep = b != background
+    a, b, c = a[keep], b[keep], c[keep]
+    order = np.lexsort((b, -c, a))                                # per label: the largest count first, then the smallest value
+    a, b = a[order], b[order]
+    first = np.ones(a.size, bool)
+    first[1:] = a[1:] != a[:-1]
+    a, b = a[first], b[first]
+    values = np.full(ids.size, background, dtype=np.result_type(fdtype, np.min_scalar_type(background)))
+    at = np.searchsorted(a, ids)
+    hit = (at < a.size) & (a[np.minimum(at, max(a.size - 1, 0))] == ids) if a.size else np.zeros(ids.size, bool)
+    values[hit] = b[at[hit]]
+    return values, present
+
+
+def _to_device(x):
+    from tobac_flow_amd import _lib
+    return _lib.to_dev(x, share=True)
+
+
+def _reduce_on_device(labels, fields, func, pass_positions):
+    """the checks both functions share: (labels tensor, field tensor, reducer name, background, field dtype)"""
+    from tobac_flow_amd import _lib
+    if pass_positions:
+        raise _refuse("pass_positions=True")
+    if len(fields) != 1:
+        raise _refuse(f"{len(fields)} fields")
+    known = _recognise(func)
+    if known is None:
+        raise _refuse(f"{getattr(func, '__name__', func)!r} is not recognised")
+    t = _lib.torch()
+    fdtype = _field_numpy_dtype(fields[0])
+    lab = _to_device(labels)
+    if lab.dtype.is_floating_point or lab.dtype == t.bool:
+        raise TypeError("labels must be an integer volume")
+    return lab, _to_device(fields[0]), known[0], known[1], fdtype
+
+
+def _records(lab, fld, name, ids):
+    """the library pass: per id the downloaded record (n_ids, 8) int64 and, for the medians, tf_label_order's two middle
+    values (n_ids, 2) float64; zeros / NaN for ids no int32 volume can hold"""
+    from tobac_flow_amd import _lib
+    from tobac_flow_amd import ndimage_dev as nd
+    ids, lo, hi = nd._id_span(ids)
+    rec, mid = np.zeros((ids.size, 8), np.int64), np.full((ids.size, 2), np.nan)
+    if lo is not None and lab.numel():
+        t = _lib.torch()
+        held = (ids > nd._INT32_MIN) & (ids <= nd._INT32_MAX)
+        at = t.from_numpy(np.where(held, ids - lo, 0)).to(lab.device)
+        got = nd.label_records(lab, fld, lo, hi, var=name in ("var", "nanvar", "std", "nanstd"),
+                               order=name in ("median", "nanmedian"))
+        if isinstance(got, tuple):
+            mid = np.where(held[:, None], got[1][at].cpu().numpy(), np.nan)
+            got = got[0]
+        rec = got[at].cpu().numpy() * held[:, None]
+    return rec, mid
+
+
+def _values_per_id(lab, fld, name, background, fdtype, ids):
+    """(values, present) for the int64 ids: one library pass and the NumPy finish"""
+    ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+    if name == "mode":
+        return _mode_on_device(lab, fld, ids, background, fdtype)
+    return _finish(name, *_records(lab, fld, name, ids), fdtype)
+
+
+def _to_caller(out, like):
+    """a device tensor when `like` (the caller's labels) was a tensor and torch can hold the dtype, else the array"""
+    if not _is_tensor(like):
+        return out
+    from tobac_flow_amd import _lib
+    try:
+        return _lib.torch().from_numpy(np.array(out)).to(like.device if like.is_cuda else _lib.device())
+    except TypeError:
+        return out
+
+
+def _labeled_comprehension_dev(field, labels, func, index, dtype, default, pass_positions):
+    lab, fld, name, background, fdtype = _reduce_on_device(labels, (field,), func, pass_positions)
+    if not dtype:
+        dtype = fdtype
+    scalar = index is not None and np.isscalar(index)
+    if index is None:
+        ids = lab[lab != 0].unique().cpu().numpy().astype(np.int64)
+    else:
+        ids = np.asarray([index] if scalar else index)
+        if ids.size and ids.dtype.kind not in "iub":
+            raise ValueError("index must be integer label ids")
+        ids = ids.astype(np.int64)
+    if ids.size == 0:
+        raise ValueError("labeled_comprehension: empty index (scipy.ndimage refuses it as well)")
+    values, present = _values_per_id(lab, fld, name, background, fdtype, ids.reshape(-1))
+    out = np.empty(ids.size, dtype)
+    out[:] = default
+    with np.errstate(invalid="ignore"):
+        if np.can_cast(values.dtype, out.dtype, "safe") or (values.dtype.kind == "f" and out.dtype.kind == "f"):
+            out[present] = values[present]
+        else:                                                     # NumPy's own scalar cast, OverflowError included
+            for k in np.flatnonzero(present):
+                out[k] = values[k]
+    out = out.reshape(ids.shape)
+    return _to_caller(out[0] if scalar else out, labels)
+
+
+def _apply_func_to_labels_dev(labels, fields, func, index, default):
+    lab, fld, name, background, fdtype = _reduce_on_device(labels, fields, func, False)
+    low, top = (int(lab.min()), int(lab.max())) if lab.numel() else (0, 0)
+    if low < 0:
+        raise ValueError("apply_func_to_labels on device tensors takes labels >= 0 (negative labels shift the reference's "
+                         "default index); pass NumPy arrays for the host path")
+    ids = np.arange(1, max(top, 0) + 1) if index is None else np.asarray(list(index), np.int64)
+    if _is_sequence(default):
+        if len(default) != 1:
+            raise _refuse("a multi-valued default")
+        empty_value = default[0]
+    else:
+        if top < 1:
+            raise IndexError("apply_func_to_labels: no labelled region to infer the shape of func's result from")
+        empty_value = default
+    values, present = _values_per_id(lab, fld, name, background, fdtype, ids)
+    if fdtype.kind == "f" and values.dtype == np.float64:
+        values = values.astype(fdtype)                            # the dtype NumPy's own result has: one rounding
+    if ids.size == 0:
+        raise ValueError("apply_func_to_labels: empty index, nothing to stack")
+    if present.all():
+        out = values.squeeze()
+    else:                                                         # np.stack of the values and the defaults: its promotion
+        out = np.empty(ids.size, np.result_type(values.dtype, np.asarray(empty_value).dtype))
+        out[:] = empty_value
+        out[present] = values[present]
+        out = out.squeeze()
+    return _to_caller(out, labels)
 
 
 __all__ = ("labeled_comprehension", "apply_func_to_labels", "flat_label", "make_step_labels",

@@ -1,4 +1,4 @@
-"""The statistics helpers the drop-in scripts reach (reference: utils/stats_utils.py:23-30, :33-168 and :366-367).
+"""The statistics helpers the drop-in scripts reach (reference: utils/stats_utils.py:11-30, :33-168 and :366-367).
 
 The weighted_* functions and get_weighted_proportions are the per-region host forms: one region's values in, scalars
 out.  tobac_flow_amd.postprocess evaluates them for all labels at once on the GPU (tf_label_wstats,
@@ -24,6 +24,19 @@ def _stamps_fit(lo, hi, size):
     non-negative and the table no larger than the data itself (dense label ids never exceed the voxel count; one stray
     huge id must not buy a table of its size)"""
     return lo >= 0 and hi <= size
+
+
+def find_overlap_mode(x, background=0):
+    """The most frequent value of `x` that is not `background`, the smallest among equally frequent ones (what
+    scipy.stats.mode returns); `background` itself where there is no other value (reference: stats_utils.py:11-20).
+    Passed as `func` to labeled_comprehension / apply_func_to_labels with device tensors it is recognised and evaluated
+    for all labels at once on the GPU (utils/label_utils.py)."""
+    x = np.asarray(x)
+    kept = x[x != background]
+    if kept.size == 0:
+        return background
+    values, counts = np.unique(kept, return_counts=True)
+    return values[np.argmax(counts)]
 
 
 def n_unique_along_axis(a, axis: int = 0):
@@ -145,5 +158,5 @@ def get_weighted_proportions(data, weights, flag_values):
         return np.array([np.nansum(np.where(data == f, counted, 0.0)) for f in flag_values]) / total
 
 
-__all__ = ("mse", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
+__all__ = ("mse", "find_overlap_mode", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
            "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions")
