@@ -584,6 +584,28 @@ int tf_label_filter(const int32_t *labels, int64_t T, int64_t H, int64_t W, int6
 /* the same gather with ids <= 0 passed through (window stitch, tobac_flow/linking.py:153-161: background -1 and 0 keep
  * their value while the positive ids are renumbered) */
 int tf_apply_lut_keep_nonpositive(const int32_t *labels, int64_t n, const int32_t *lut, int n_lut, int32_t *out, void *stream);
+/* tf_relabel_merge (version 111): tobac_flow/linking.py:246-334 -- relabel_cores_and_anvils of a window product, of the
+ *   frames it shares with the previous and the next product, and the two combine_labels, in one read of each source and one
+ *   write.  For output frame t and pixel p of the int32 (T, hw) volume `own`:
+ *     v = own[t, p]                        r = (v == 0) ? 0 : lut_own[v]
+ *     if r == 0 and prev_frame[t] >= 0:    u = prev[prev_frame[t], p];   r = (u == 0) ? 0 : lut_prev[u]
+ *     if r == 0 and next_frame[t] >= 0:    u = next[next_frame[t], p];   r = (u == 0) ? 0 : lut_next[u]
+ *     out[t, p] = r
+ *   Everything is device memory.  The tables are indexed by local id (n_* entries, entry 0 is 0).  prev_frame / next_frame:
+ *   int32[T], the frame of the neighbour's (T_prev, hw) / (T_next, hw) volume that shows output frame t, or -1; any order,
+ *   repeats allowed.  prev or next may be NULL (its other arguments are then ignored).  out == own (in place) is allowed; out
+ *   must not overlap own otherwise, nor prev or next.  Any alignment: 16-byte accesses where own and out are 16-byte aligned,
+ *   element accesses otherwise.
+ *   status: two uint64 words, zeroed by the call.  status[0] counts the voxels whose CONSULTED id was negative or >= its
+ *   table's size (they give 0 and the next source is asked); a neighbour voxel is consulted only where the result so far is
+ *   0, so ids under voxels that are never consulted are not checked.  status[1] counts the voxels that asked a frame-table
+ *   entry >= T_prev / T_next (treated as -1; nothing is read through it).
+ *   TF_EINVAL before any launch: null pointers, T outside 1 .. 65535, hw outside 1 .. 2^30 - 1, more than 2^38 voxels,
+ *   an empty table, overlapping buffers. */
+int tf_relabel_merge(const int32_t *own, int64_t T, int64_t hw, const int32_t *lut_own, int n_own,
+                     const int32_t *prev, int64_t T_prev, const int32_t *prev_frame, const int32_t *lut_prev, int n_prev,
+                     const int32_t *next, int64_t T_next, const int32_t *next_frame, const int32_t *lut_next, int n_next,
+                     int32_t *out, uint64_t *status, void *stream);
 /* The elementwise glue of detect_anvils' seeds (tobac_flow/detection.py:547-561, 590-617) in two passes:
  * tf_field_masks: ge1 = field >= 1, le0_or_nan = (field <= 0) | isnan(field), isnan_out = isnan(field) as 0 / 1 bytes;
  * tf_merge_seeds: seeds = (bg | isnan) ? -1 : comp. */

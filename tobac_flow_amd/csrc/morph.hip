@@ -208,12 +208,7 @@ k_linearise(const float *__restrict__ f, int64_t n, float lo, float span, int fl
 // Four elements per thread (16-byte accesses) for the one-pass elementwise kernels of this file: with one 4-byte
 // element per thread they moved ~3.5 TB/s.  tf_vec4_ok: every 4-byte-element array 16-byte aligned, every byte array
 // 4-byte aligned; the last thread handles the n % 4 tail element by element.
-static bool tf_vec4_ok(std::initializer_list<const void *> words, std::initializer_list<const void *> bytes)
-{
-    for (const void *p : words) if ((uintptr_t)p % 16) return false;
-    for (const void *p : bytes) if ((uintptr_t)p % 4) return false;
-    return true;
-}
+// (the predicate itself lives in tf_common.h: relabel_merge.hip uses it too)
 
 __global__ void __launch_bounds__(256)
 k_linearise4(const float *__restrict__ f, int64_t n, float lo, float span, int flip, float *__restrict__ out)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include "../../include/tobac_flow_hip.h"
 
 void tf_set_error(const char *fmt, ...);
@@ -32,6 +33,15 @@ void tf_set_error(const char *fmt, ...);
     } while (0)
 
 static inline size_t tf_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the 16-byte forms of the one-pass elementwise kernels (morph.hip, relabel_merge.hip) apply when every 4-byte-element
+// array is 16-byte aligned and every byte array 4-byte aligned
+static inline bool tf_vec4_ok(std::initializer_list<const void *> words, std::initializer_list<const void *> bytes)
+{
+    for (const void *p : words) if ((uintptr_t)p % 16) return false;
+    for (const void *p : bytes) if ((uintptr_t)p % 4) return false;
+    return true;
+}
 
 // bump allocator over the caller's workspace
 struct TfArena {
