@@ -749,13 +749,13 @@ def test_the_three_host_replays_of_the_reference_heap_agree(tmp_path):
 
 
 def test_window_scheduler_shares_its_slots_between_stacks_and_delivers_them_in_order():
-    """host logic of parallel._WindowFloods / _SequenceFloods (detect_stack_windows, detect_stack_sequence) with the device
+    """host logic of parallel._WindowFloods / _FloodFamily (detect_stack_windows, detect_stack_sequence) with the device
     parts replaced by stand-ins: never more floods in flight than slots, whichever stack they belong to; a flood whose first
     finish ends in a late export is queued again and finished later; a stack is delivered once its flow has been enqueued,
     every window begun and every flood finished -- the stacks in order; set-ups precede sweeps within a hand-over."""
     import contextlib
     from concurrent.futures import ThreadPoolExecutor
-    from tobac_flow_amd.parallel import _SequenceFloods, _StackRun, _WindowFloods
+    from tobac_flow_amd.parallel import _Flood, _FloodFamily, _StackRun, _WindowFloods
     log, in_flight, peak = [], [0], [0]
     pool = ThreadPoolExecutor(4)
 
@@ -776,22 +776,20 @@ def test_window_scheduler_shares_its_slots_between_stacks_and_delivers_them_in_o
             log.append(("view", lo, hi))
             yield self
 
-    def make(stack, n_win, slots, late=()):
-        o = _StackRun()
-        o.bounds = [(4 * k, 4 * k + 6) for k in range(n_win)]
-        o.mark = lambda what: None
-        o.pool = pool
-        wf = _WindowFloods(o, list(range(4 * n_win + 2)), 0, slots, len(slots))
+    def make(stack, n_win, slots, late=(), family=None):
+        o = _StackRun(bounds=[(4 * k, 4 * k + 6) for k in range(n_win)], pool=pool)
+        wf = _WindowFloods(o, list(range(4 * n_win + 2)), 0, slots, family=family, index=stack)
 
         def begin(flow_w, w, scratch, wf=wf):
             in_flight[0] += 1
             peak[0] = max(peak[0], in_flight[0])
             job = Job((stack, wf.next), (stack, wf.next) in late)
             log.append(("setup", job.tag))
-            return job, pool.submit(job.replay), {}, scratch
+            return _Flood(job, pool.submit(job.replay), {}, scratch, wf.next)
 
-        def finish(job, fut, st, scratch):
-            fut.result()
+        def finish(flood):
+            job = flood.job
+            flood.future.result()
             assert job.swept, "finished before its sweeps"
             if job.late:
                 job.late = False
@@ -806,8 +804,8 @@ def test_window_scheduler_shares_its_slots_between_stacks_and_delivers_them_in_o
 
         def finish_one(block=True, wf=wf):
             for p in wf.pending:
-                if not p[0].swept:
-                    p[0].sweeps()
+                if not p.job.swept:
+                    p.job.sweeps()
             return real_finish_one(block)
         wf.finish_one = finish_one
         return wf
@@ -825,11 +823,10 @@ def test_window_scheduler_shares_its_slots_between_stacks_and_delivers_them_in_o
     del log[:]
     peak[0] = 0
     delivered = []
-    fam = _SequenceFloods(lambda w: delivered.append((w.index, list(w.wins))))
+    fam = _FloodFamily(lambda w: delivered.append((w.index, list(w.wins))))
     slots = [None, None, None]
-    a, b = make(0, 4, slots, late={(0, 3)}), make(1, 4, slots)
-    for k, w in enumerate((a, b)):
-        w.family, w.index, w.flow_enqueued = fam, k, False
+    a, b = make(0, 4, slots, late={(0, 3)}, family=fam), make(1, 4, slots, family=fam)
+    assert not a.flow_enqueued and not b.flow_enqueued
     fam.active.append(a)
     a.sweep(a.setup_up_to(FakeFlow(), 18))                               # all four windows of stack 0: three slots -> one finished on the way
     a.flow_enqueued = True
@@ -854,7 +851,7 @@ def test_flood_thread_never_begins_a_window_whose_last_frame_is_the_handovers_la
     Also: abandon_all gives every slot back (failure path)."""
     import contextlib
     from concurrent.futures import ThreadPoolExecutor
-    from tobac_flow_amd.parallel import _StackRun, _WindowFloods
+    from tobac_flow_amd.parallel import _Flood, _StackRun, _WindowFloods
     pool = ThreadPoolExecutor(2)
     views, abandoned = [], []
 
@@ -877,13 +874,9 @@ def test_flood_thread_never_begins_a_window_whose_last_frame_is_the_handovers_la
             yield self
 
     def make(own_stream, slots):
-        o = _StackRun()
-        o.bounds = [(0, 16), (12, 30)]
-        o.mark = lambda what: None
-        o.pool = pool
-        wf = _WindowFloods(o, list(range(30)), 0, slots, len(slots))
-        wf.own_stream = own_stream
-        wf._begin = lambda flow_w, w, scratch: (Job(), pool.submit(lambda: None), {}, scratch)
+        o = _StackRun(bounds=[(0, 16), (12, 30)], pool=pool)
+        wf = _WindowFloods(o, list(range(30)), 0, slots, own_stream=own_stream)
+        wf._begin = lambda flow_w, w, scratch: _Flood(Job(), pool.submit(lambda: None), {}, scratch, wf.next)
         return wf
     slots = [None, None, None]
     wf = make(True, slots)
@@ -898,6 +891,79 @@ def test_flood_thread_never_begins_a_window_whose_last_frame_is_the_handovers_la
     del views[:]
     wf = make(False, [None, None])                                       # calling thread: ordered by the stream, begun at once
     assert len(wf.setup_up_to(FakeFlow(), 16)) == 1 and views == [(0, 16)]
+
+
+def test_flood_thread_hands_items_over_in_order_and_reports_a_failure_without_blocking_the_caller():
+    """parallel._FloodThread, the one driver of detect_stack_windows' and detect_stack_sequence's flood thread, with stand-ins
+    (stream=None: no device).  Clean path: the items are handled in order, the callable behind the sentinel runs once, close()
+    returns.  Failure path: a handler that raises on the second item has the floods abandoned once, put() on the calling
+    thread returns or raises at once instead of blocking, check() and close() re-raise the very exception."""
+    import threading
+    import time
+    from tobac_flow_amd.parallel import _FloodThread
+    handled, after, abandoned, idles = [], [], [], []
+    flood = _FloodThread(handle=lambda box: handled.append((box.pop(), threading.current_thread().name)), abandon=lambda: abandoned.append(1),
+                         after=lambda: after.append(list(handled)))
+    for k in range(5):
+        flood.put(("item", k))
+    flood.close()
+    assert [h[0] for h in handled] == [("item", k) for k in range(5)] and {h[1] for h in handled} == {"tf-window-floods"}
+    assert len(after) == 1 and len(after[0]) == 5 and abandoned == [] and not flood.thread.is_alive()
+    # the idle callable is polled while it says so, and not before the first item
+    del handled[:]
+    polled = threading.Event()
+
+    def idle():
+        idles.append(len(handled))
+        if len(idles) == 3:
+            polled.set()
+        return len(idles) < 3
+    with _FloodThread(handle=lambda box: handled.append(box.pop()), abandon=lambda: abandoned.append(1), after=lambda: None, idle=idle) as flood:
+        flood.put("a")
+        assert polled.wait(5.0)
+        flood.put("b")
+    assert handled == ["a", "b"] and idles[:3] == [1, 1, 1] and abandoned == []
+    # failure on the second item
+    boom = KeyError("the handler failed")
+    del handled[:]
+    failed = threading.Event()
+
+    def handle(box):
+        handled.append(box.pop())
+        if len(handled) == 2:
+            failed.set()
+            raise boom
+    given_up = threading.Event()
+
+    def abandon():
+        abandoned.append(1)
+        given_up.set()
+    flood = _FloodThread(handle=handle, abandon=abandon, after=lambda: after.append("never"))
+    flood.put(0)
+    flood.put(1)
+    assert failed.wait(5.0)
+    t0 = time.monotonic()
+    raised = []
+    for k in (2, 3):
+        try:
+            flood.put(k)
+        except KeyError as exc:
+            raised.append(exc)
+    assert time.monotonic() - t0 < 1.0
+    assert given_up.wait(5.0)                                           # (the failure is recorded before the floods are given up)
+    with pytest.raises(KeyError) as caught:
+        flood.check()
+    assert caught.value is boom and all(exc is boom for exc in raised)
+    with pytest.raises(KeyError) as caught:
+        flood.close()
+    assert caught.value is boom and time.monotonic() - t0 < 5.0 and not flood.thread.is_alive()
+    assert abandoned == [1] and handled == [0, 1] and "never" not in after
+    # an exception of the calling thread is the one that is reported
+    with pytest.raises(ValueError, match="the caller's own"):
+        with _FloodThread(handle=handle, abandon=lambda: abandoned.append(1), after=lambda: None) as flood:
+            flood.put(2)
+            raise ValueError("the caller's own")
+    assert abandoned == [1] and not flood.thread.is_alive()
 
 
 def test_rank_windows_deals_the_windows_of_one_stack_out_to_the_ranks():

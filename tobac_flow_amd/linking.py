@@ -31,7 +31,9 @@ import numpy as np
 
 from tobac_flow_amd import _lib
 from tobac_flow_amd import dataset as _dataset
+from tobac_flow_amd import parallel
 from tobac_flow_amd.dataset import LabelDataset
+from tobac_flow_amd.parallel import LINK_ATOL, LINK_RTOL
 from tobac_flow_amd.utils.datetime_utils import get_dates_from_filename, trim_file_start_and_end
 from tobac_flow_amd.utils.label_utils import remap_labels
 
@@ -39,7 +41,6 @@ _VOLUMES = (("core_label", "core"), ("thick_anvil_label", "anvil"), ("thin_anvil
 _REQUIRED_VARS = ("goes_imager_projection", "lat", "lon", "area", "bt", "BT", "wvd", "swd", "core_label", "thick_anvil_label",
                   "thin_anvil_label")
 _LABEL_COORDS = ("core", "anvil", "core_step", "thick_anvil_step", "thin_anvil_step")
-LINK_ATOL, LINK_RTOL = 5, 0.5
 
 
 def _open(store, name):
@@ -87,7 +88,6 @@ def _find_overlap_between(current_ds, next_ds, coord, volume):
         return min_id, max_id, np.array([], dtype=index.dtype), np.array([], dtype=np.asarray(next_ds.coords[coord]).dtype)
     at_current, at_next = at_current[1:-1], at_next[1:-1]
     if on_device:
-        from tobac_flow_amd import parallel
         t = _lib.torch()
         left = _take_frames(_lib.to_dev(current, t.int32), at_current)
         right = _take_frames(_lib.to_dev(following, t.int32), at_next)

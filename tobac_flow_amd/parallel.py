@@ -11,7 +11,13 @@ the stitched objects are the connected components of those pairs (linking.py:153
 which every rank runs the same union-find and rewrites its own labels (tf_apply_lut).  Pair counting on the GPU is
 the library's tf_window_overlap_pairs; CPU tensors (the gloo rehearsals) take the numpy statement of the same rule.
 """
+import contextlib
 import os
+import queue
+import threading
+import time
+from collections import deque
+from typing import NamedTuple
 
 import numpy as np
 
@@ -147,13 +153,6 @@ def overlap_pairs(left, right, atol=LINK_ATOL, rtol=LINK_RTOL):
         break
     _lib.check(rc, "tf_window_overlap_pairs")
     return out[:n_out.value].astype(np.int64)
-
-
-def boundary_pairs(left_last, right_first, base=None, min_overlap=1):
-    """Pairs of positive labels that coincide in >= `min_overlap` pixels of one shared frame (the absolute criterion
-    alone: overlap_pairs with rtol = 0).  `base` is ignored (kept for callers of the round-1 signature)."""
-    import torch
-    return torch.from_numpy(overlap_pairs(left_last, right_first, atol=max(int(min_overlap), 1), rtol=0.0))
 
 
 DEFAULT_OVERLAP = 4                    # frames consecutive windows share (scripts/dcc_detect_goes.py:153 n_pad_files; bench.py)
@@ -349,14 +348,14 @@ def apply_global_lut(labels, lut, inplace=False):
 #   * floods are FINISHED out of order, whichever replay ends first, on a second stream (the main one is busy with the flow);
 #   * the label ids of all windows (of all ranks, with a process group) are made consistent by stitch_rank_windows.
 # Every window's labels equal Flow.watershed on create_flow(window) -- tests/test_gpu_windows.py compares voxel for voxel.
+FLOOD_SLOTS = 5                        # floods in flight at most beside the flow (7 measured: the same mean, more scatter)
 _REPLAY_POOL = None
 _SIDE_STREAMS = {}
 _BUDGET_MEMO = {}
 
 
-def _replay_pool(n):
+def _replay_pool():
     global _REPLAY_POOL
-    import os
     from concurrent.futures import ThreadPoolExecutor
     if _REPLAY_POOL is None:
         cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
@@ -366,9 +365,8 @@ def _replay_pool(n):
 
 def _side_stream():
     """the second stream of (device, calling stream) -- the floods of ready windows are finished on it while the calling
-    stream is busy with the flow.  (Round 5 could confine it to k CUs of every XCD or give it the lowest priority: both
-    measured slower than a plain stream, profiles/round5_scheduling_experiments.txt, and gone with round 6 --
-    tools/experiments/stream_experiments.hip.)"""
+    stream is busy with the flow.  (Confined to k CUs of every XCD, or with the lowest priority, it measured slower than a
+    plain stream: profiles/round5_scheduling_experiments.txt, tools/experiments/stream_experiments.hip.)"""
     import torch
     key = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
     if key not in _SIDE_STREAMS:
@@ -376,21 +374,112 @@ def _side_stream():
     return _SIDE_STREAMS[key]
 
 
+def _several_ranks(group):
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+
+
+def _bounds_ok(bounds, T=None):
+    """are `bounds` ascending (start, stop) windows -- and, given T, inside a stack of T frames?"""
+    ascending = all(b[1] >= a[1] and b[0] >= a[0] for a, b in zip(bounds[:-1], bounds[1:]))
+    return ascending and (T is None or all(0 <= lo < hi <= T for lo, hi in bounds))
+
+
+def _info(info):
+    info = info if info is not None else {}
+    info.setdefault("floods", [])
+    info.setdefault("reference_order", [])
+    return info
+
+
+def _timed(mark):
+    """the caller's mark(what, milliseconds since this call) as the one-argument form the scheduler calls"""
+    if mark is None:
+        return lambda what: None
+    t_start = time.perf_counter()
+    return lambda what: mark(what, (time.perf_counter() - t_start) * 1e3)
+
+
+def _flood_scratch_bytes(bounds, H, W):
+    """scratch of a flood in flight (~17 B per window voxel)"""
+    return 18 * max(hi - lo for lo, hi in bounds) * H * W
+
+
+def _room_beside_the_flow(T, H, W, bounds, n_fly, resident_channels, hand_out, several_channels):
+    """Bytes the device has left for the Farneback scratch beside the stack's flow vectors, the labels of all windows of
+    `resident_channels` channels (none in hand-out mode) and n_fly floods in flight (scratch + field + seeds ~ 1.5 x the
+    scratch each, and one window's transients); free memory counts whether the driver, the caching allocator or a workspace
+    of the library holds it."""
+    import torch
+    from tobac_flow_amd import _lib
+    free = torch.cuda.mem_get_info()[0] + (torch.cuda.memory_reserved() - torch.cuda.memory_allocated())
+    held = sum(int(v.numel()) for k, v in list(_lib._WS.items()) if v is not None and k[1] == torch.cuda.current_device())
+    resident = 0 if hand_out else resident_channels * 4 * sum(hi - lo for lo, hi in bounds) * H * W
+    # several channels: what the single-channel estimate leaves out is no longer small beside what is left -- the raw flow
+    # vectors and 8-bit frames of a batch, the refinement's and the labelling's scratch, the flood stream's cached transients
+    # (measured on config F3: 25 GB; the device ran out, the allocator flushed its cache -- a 4.4 s hole in the step)
+    other = int(0.08 * torch.cuda.mem_get_info()[1]) if several_channels else 0
+    return free + held - (2 * T * H * W * 8 + resident + (n_fly + 1) * (3 * _flood_scratch_bytes(bounds, H, W) // 2) + other)
+
+
+def _flow_budget_gb(entry, T, H, W, bounds, n_fly, resident_channels, hand_out, several_channels):
+    """(memo key, GB) -- the scratch budget of the Farneback batches while floods run beside them.
+    Floods in flight beside the flow need scratch of their own (the Farneback workspace is busy): the Farneback batches get
+    the room beside the flow with 30 % of it kept back: free memory that sits in the caching allocator as fragments cannot
+    serve the one block the Farneback scratch is, and a budget the device can only just hold costs allocator retries
+    (measured: 98.8 GB -> batches of 64 pairs, 268 GB at the peak, steps of 4.7 / 8.4 / 6.4 s instead of 4.6).  Memoised per
+    entry point and stack shape: the batches of every call of a sweep are then the same, whatever an earlier call left
+    cached.  Config F (144 x 5424^2, 12 windows) on 288 GB: 86 GB -- any budget from 65 to 98 GB gives the library's batch
+    hint 21 full-resolution pairs, i.e. 42-pair batches finished in two parts of 21."""
+    import torch
+    key = (entry, torch.cuda.current_device(), T, H, W, tuple(bounds), n_fly, resident_channels, hand_out)
+    if key not in _BUDGET_MEMO:
+        room = _room_beside_the_flow(T, H, W, bounds, n_fly, resident_channels, hand_out, several_channels)
+        _BUDGET_MEMO[key] = max(4.0, 0.7 * room / 1e9)
+    return key, _BUDGET_MEMO[key]
+
+
+class _Flood(NamedTuple):
+    """a flood in flight"""
+    job: object                        # the WatershedJob
+    future: object                     # its host replay on a worker thread (None: it needs none)
+    stats: dict
+    scratch: object                    # the flood slot it took: a piece of workspace, or None (it allocates its own)
+    window: int
+
+
+class _StackRun:
+    """What every flood of one stack is begun and finished with."""
+
+    def __init__(self, bounds, seeds_fn=None, nbr=None, chain_depth=3, on_ambiguous="reference", info=None, mark=None, pool=None,
+                 side=None, overlap=DEFAULT_OVERLAP, group=None):
+        self.bounds, self.seeds_fn, self.nbr, self.chain_depth, self.on_ambiguous = bounds, seeds_fn, nbr, chain_depth, on_ambiguous
+        self.info = _info(info)
+        self.mark = mark if mark is not None else (lambda what: None)
+        self.pool = pool if pool is not None else _replay_pool()
+        self.side = side                                     # stream the floods are finished on (None: the current one)
+        # the linking rule of the hand-out mode and of the stitch
+        self.overlap, self.group = int(overlap), group
+        self.atol, self.rtol, self.sel = LINK_ATOL, LINK_RTOL, compare_frames(self.overlap)
+        self.multi = _several_ranks(group)
+
+
 class _WindowFloods:
     """The floods of one channel of one stack: begun window by window (each with its seeds and edge field), their host
     replays on worker threads, finished -- out of order -- as soon as their replay has ended."""
 
-    def __init__(self, owner, bt, channel, pieces, n_fly):
-        from collections import deque
-        self.o, self.bt, self.c, self.pieces, self.n_fly = owner, bt, channel, pieces, n_fly
-        self.pending = deque()                               # floods in flight: (job, future, stats, scratch, window index)
+    def __init__(self, owner, bt, channel, pieces, on_window=None, own_stream=False, family=None, index=0):
+        self.o, self.bt, self.c, self.pieces = owner, bt, channel, pieces
+        self.pending = deque()                               # the floods in flight (_Flood)
         self.wins = [None] * len(owner.bounds)
         self.next = 0                                        # next window to begin
-        self.family = None                                   # detect_stack_sequence: the stacks in flight share the flood slots
-        self.own_stream = False                              # True: driven from a flood thread on a stream of its own (_ready)
+        self.family = family                                 # the _FloodFamily it shares the flood slots with (None: with nobody)
+        self.own_stream = own_stream                         # True: driven from a flood thread on a stream of its own (_ready)
+        # detect_stack_sequence: which stack this is; has the flood thread seen the end of its flow; has it set up the last window
+        self.index, self.flow_enqueued, self.setups_done = index, False, threading.Event()
         # hand-out mode (detect_stack_windows(on_window=...)): every window leaves as soon as it is finished, with window-local
         # ids; what stays are its label count and the pairs it forms with its neighbours (computed as soon as both exist)
-        self.on_window = None
+        self.on_window = on_window
         n = len(owner.bounds)
         self.handed, self.counts, self.pairs = [None] * n, [0] * n, [None] * max(n - 1, 0)
         self._heads, self._tails, self.first_head, self.last_tail = {}, {}, None, None
@@ -451,7 +540,7 @@ class _WindowFloods:
         return (not self.own_stream) or hi < n_frames or n_frames >= len(self.bt)
 
     def _finish_any(self, block=True):
-        """finish one ready flood -- of this stack, or (detect_stack_sequence) of any stack still in flight"""
+        """finish one ready flood -- of this channel of this stack, or of any member of its family"""
         return self.family.finish_any(block) if self.family is not None else self.finish_one(block)
 
     def _begin(self, flow, w, scratch):
@@ -469,19 +558,19 @@ class _WindowFloods:
         # (defer_sweeps: the call returns after the set-up and the export -- the parts that read the window's flow fields; phase
         # A and the chain levels are begin_up_to's second pass, when the replays of ALL windows of this hand-over are under way)
         job = watershed_begin(fw, bw, e, seeds, None, o.nbr, o.chain_depth, stats=st, on_ambiguous=o.on_ambiguous, workspace=scratch,
-                              defer_sweeps=os.environ.get("TF_WINDOWS_DEFER_SWEEPS", "1") == "1")     # (development switch: 0 = one pass)
+                              defer_sweeps=True)
         o.mark("begin: set up (replay %s)" % ("submitted" if job.needs_replay else "none"))
         fut = o.pool.submit(job.replay) if job.needs_replay else None
-        return job, fut, st, scratch
+        return _Flood(job, fut, st, scratch, self.next)
 
-    def _finish(self, job, fut, st, scratch):
+    def _finish(self, flood):
         """root phase (with the pop ranks), labels written: one label volume -- or None if the library had to export for a host
         replay after the root phase (no guessed tie value, or one that was too low): the caller queues the job again"""
-        o = self.o
-        if fut is not None:
-            fut.result()
+        o, st = self.o, flood.stats
+        if flood.future is not None:
+            flood.future.result()
         o.mark("finish: enter")
-        done, lab = job.step(stream=o.side)                  # (WatershedJob.step records the caller's stream on the labels)
+        done, lab = flood.job.step(stream=o.side)            # (WatershedJob.step records the caller's stream on the labels)
         o.mark("finish: %s" % ("done" if done else "exported again, replay pending"))
         if not done:
             return None
@@ -499,22 +588,22 @@ class _WindowFloods:
         with it the start of its long replay -- as early as possible)"""
         from concurrent.futures import FIRST_COMPLETED, wait
         pending = self.pending
-        ready = [p for p in pending if p[1] is None or p[1].done()]
+        ready = [p for p in pending if p.future is None or p.future.done()]
         if not ready and not block:
             return False
         if not ready:
-            wait([p[1] for p in pending], return_when=FIRST_COMPLETED)
-            ready = [p for p in pending if p[1] is None or p[1].done()]
+            wait([p.future for p in pending], return_when=FIRST_COMPLETED)
+            ready = [p for p in pending if p.future is None or p.future.done()]
         done = ready[0]
         pending.remove(done)
-        lab = self._finish(*done[:4])
+        lab = self._finish(done)
         if lab is None:                                      # exported after its root phase: the replay goes to a worker, the job comes back
-            pending.append((done[0], self.o.pool.submit(done[0].replay)) + done[2:])
+            pending.append(done._replace(future=self.o.pool.submit(done.job.replay)))
             return True
-        self.wins[done[4]] = lab
-        self.pieces.append(done[3])
+        self.wins[done.window] = lab
+        self.pieces.append(done.scratch)
         if self.on_window is not None:
-            self._hand_out(done[4], lab)
+            self._hand_out(done.window, lab)
         return True
 
     def setup_up_to(self, flow, n_frames, wait_for=None):
@@ -523,7 +612,6 @@ class _WindowFloods:
         Returns the jobs for sweep().
         wait_for: an event on the main stream behind the flow these windows need: until it has passed, floods whose replay
         has ended are finished (on the second stream) instead of blocking in the first synchronisation of a begin"""
-        import time
         bounds = self.o.bounds
         while wait_for is not None and self._ready(n_frames) and not wait_for.query():
             if not self._finish_any(block=False):
@@ -531,7 +619,7 @@ class _WindowFloods:
         begun = []
         while self._ready(n_frames):
             lo, hi = bounds[self.next]
-            while not self.pieces:                           # every flood slot is taken (by this stack's floods, or an earlier stack's)
+            while not self.pieces:                           # every flood slot is taken (by this member's floods, or another's)
                 self._finish_any()                           # (a flood begun in this call is completed there: its sweeps first)
             # the Flow create_flow(bt[lo:hi]) would return, bit for bit: the flow of a frame pair does not depend on the window
             # it is in, only the two end frames of a window are mirrored (flow.py:425-426); window_view patches those two frames
@@ -539,9 +627,9 @@ class _WindowFloods:
             # the set-up of the flood reads the flows (its neighbour table has the displacements applied): sweeps and root
             # phase run outside the block.
             with flow.window_view(lo, hi) as flow_w:
-                item = self._begin(flow_w, self.bt[lo:hi], self.pieces.pop()) + (self.next,)
-            self.pending.append(item)
-            begun.append(item[0])
+                flood = self._begin(flow_w, self.bt[lo:hi], self.pieces.pop())
+            self.pending.append(flood)
+            begun.append(flood.job)
             self.next += 1
         return begun
 
@@ -568,53 +656,218 @@ class _WindowFloods:
         """failure path: give up every flood still in flight -- wait for its host replay (a worker thread that still reads the
         job), free the job, return its slot and scratch (they used to stay held until garbage collection)"""
         while self.pending:
-            job, fut, _, scratch = self.pending.popleft()[:4]
-            if fut is not None:
+            flood = self.pending.popleft()
+            if flood.future is not None:
                 try:
-                    fut.result()
+                    flood.future.result()
                 except BaseException:                        # noqa: BLE001 -- the first failure is the one that is reported
                     pass
             try:
-                job.abandon()
+                flood.job.abandon()
             except BaseException:                            # noqa: BLE001
                 pass
-            self.pieces.append(scratch)
+            self.pieces.append(flood.scratch)
 
 
-class _StackRun:
-    pass
+class _FloodFamily:
+    """Several _WindowFloods that share the flood slots, all on the one thread and stream that drives the floods, oldest
+    first: the channels of ONE stack begun during its flow (BASELINE config F3: channels are independent detections that
+    share the Flow, detection.py:203-254), or the stacks of a detect_stack_sequence call that still have floods in flight.
+    A hand-over of frames sets up that window for every member, then sweeps them; whoever waits -- for a slot, for a
+    hand-over's event -- finishes whichever flood of whichever member is ready.  deliver(member): called, in order, for a
+    stack whose every window has its labels (None: nothing is delivered from inside -- the caller collects per channel)."""
 
+    def __init__(self, deliver=None):
+        self.active, self.deliver = [], deliver
 
-class _ChannelGroup:
-    """The window floods of several channels of ONE stack driven together (BASELINE config F3: channels are independent
-    detections that share the Flow, detection.py:203-254): a hand-over of frames sets up that window for every channel -- all
-    on the one thread and stream that drives the floods, sharing the flood slots -- then sweeps them; whoever waits for a slot
-    finishes whichever channel's flood is ready."""
+    def finish_any(self, block=True):
+        from concurrent.futures import FIRST_COMPLETED, wait
+        while True:
+            for wf in list(self.active):
+                if wf.pending and wf.finish_one(block=False):
+                    self.settle(wf)
+                    return True
+            if not block:
+                return False
+            futs = [p.future for wf in self.active for p in wf.pending if p.future is not None]
+            if not futs:
+                return False
+            wait(futs, return_when=FIRST_COMPLETED)
 
-    def __init__(self, floods):
-        self.floods = list(floods)
-        if len(self.floods) > 1:
-            fam = _SequenceFloods(lambda wf: None)           # (nothing is delivered from inside: the caller collects per channel)
-            fam.active = list(self.floods)
-            for wf in self.floods:
-                wf.family = fam
+    def settle(self, wf):
+        """a stack whose every window has its labels: stitch, hand over, forget"""
+        if self.deliver is not None and wf in self.active and wf.next == len(wf.o.bounds) and not wf.pending and wf.flow_enqueued:
+            self.active.remove(wf)
+            self.deliver(wf)
+
+    def poll(self):
+        """the flood thread has nothing to begin: finish a flood that is ready.  Is anything left to poll for?"""
+        self.finish_any(block=False)
+        return bool(self.active)
+
+    def deliver_all(self):
+        """the last stack's end: nothing left to run beside it"""
+        while self.active:
+            if not self.finish_any(block=True):
+                for wf in list(self.active):
+                    self.settle(wf)
+                if self.active:
+                    raise RuntimeError("detect_stack_sequence: a stack is left with windows that were never begun")
 
     def begin_up_to(self, flow, n_frames, wait_for=None):
-        begun = [(wf, wf.setup_up_to(flow, n_frames, wait_for)) for wf in self.floods]
+        begun = [(wf, wf.setup_up_to(flow, n_frames, wait_for)) for wf in self.active]
         for wf, jobs in begun:
             wf.sweep(jobs)
 
     def finish_all(self):
-        for wf in self.floods:
+        for wf in self.active:
             wf.finish_all()
 
     def abandon_all(self):
-        for wf in self.floods:
+        for wf in list(self.active):
             wf.abandon_all()
 
-    def set_own_stream(self, flag):
-        for wf in self.floods:
-            wf.own_stream = flag
+
+class _FloodThread:
+    """A FLOOD THREAD with the second stream as its current stream drives every window -- seeds, edge field, begin, finish --
+    while the calling thread does nothing but enqueue the flow's batches: the floods' latency-bound sweeps run BESIDE the
+    next batches' kernels instead of between them (the library is re-entrant per stream; scratch and memos of the Python
+    layer are keyed by (device, stream)).  The calling thread hands items over with put(); the thread calls handle(box) for
+    each, box being a one-element list: a handler that must not keep the item alive while it works pops it.  idle(): called
+    when no item has arrived for 0.5 ms, returns whether to go on polling (None: the thread just waits); after(): called
+    once behind the last item (close()); abandon(): called if any of them raises.  A failure is re-raised on the calling
+    thread by its next put() or check(), and by close().  stream=None (tests without a device): no stream is made current."""
+
+    def __init__(self, handle, abandon, after, idle=None, stream=None, device=None):
+        self.handle, self.abandon, self.after, self.idle, self.stream, self.device = handle, abandon, after, idle, stream, device
+        self.queue, self.failure, self.stop = queue.Queue(), [], threading.Event()
+        self.thread = threading.Thread(target=self._run, name="tf-window-floods", daemon=True)
+        self.thread.start()
+
+    def _run(self):
+        try:
+            with self._stream_current():
+                poll = False
+                while True:
+                    try:
+                        box = self.queue.get(timeout=0.0005) if poll else self.queue.get()
+                    except queue.Empty:
+                        poll = self.idle()
+                        continue
+                    if box is None:
+                        break
+                    self.handle(box)
+                    poll = self.idle is not None
+                self.after()
+                if self.stream is not None:
+                    self.stream.synchronize()
+        except BaseException as exc:                         # noqa: BLE001 -- re-raised on the calling thread
+            self.failure.append(exc)
+            try:
+                if self.stream is not None:
+                    self.stream.synchronize()
+            except BaseException:                            # noqa: BLE001
+                pass
+            self.abandon()                                   # (slots and scratch of the floods in flight go back now)
+            while True:                                      # drain: the calling thread must never block on the hand-over
+                try:
+                    if self.queue.get(timeout=0.05) is None:
+                        break
+                except queue.Empty:
+                    if self.stop.is_set():
+                        break
+
+    def _stream_current(self):
+        if self.stream is None:
+            return contextlib.nullcontext()
+        import torch
+        torch.cuda.set_device(self.device)
+        return torch.cuda.stream(self.stream)
+
+    def check(self):
+        if self.failure:
+            raise self.failure[0]
+
+    def put(self, item):
+        self.check()                                         # the flood thread has failed: stop the flow here, not after the
+        self.queue.put([item])                               # rest of the stack has been enqueued (ADVICE r5)
+
+    def close(self, reraise=True):
+        self.stop.set()
+        self.queue.put(None)
+        self.thread.join()
+        if reraise:
+            self.check()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close(reraise=exc_type is None)                 # (an exception of the calling thread is the one that is reported)
+
+
+def _deliver(o, wins, index, stitch, consume, caller_stream, what=""):
+    """every window of a channel / a stack has its labels: their ids made consistent over all windows (of all ranks) -- pair
+    counting on the GPU, one union-find, one LUT pass, in place -- and the windows handed to the caller: consume(index, windows)
+    or the windows themselves.  caller_stream: given where a flood thread allocated the labels under ITS stream; from here on
+    they are the caller's, used on the caller's stream: tell the caching allocator, or a later allocation of the flood stream
+    could take a block the caller has dropped while kernels of the caller's stream still read it (the same rule as
+    WatershedJob.step(stream=...))"""
+    o.mark(what + "all windows finished")
+    if stitch and (len(wins) > 1 or o.multi):
+        wins = stitch_rank_windows(wins, group=o.group, overlap=o.overlap, inplace=True)
+        o.mark(what + "stitched")
+    if caller_stream is not None:
+        for w in wins:
+            if w is not None and w.is_cuda:
+                w.record_stream(caller_stream)
+    return wins if consume is None else consume(index, wins)
+
+
+def _plan_windows(T, H, W, bounds, C, stream_windows, hand_out, max_in_flight):
+    """(channels whose windows are begun DURING the flow, flood slots): with on_window no labels stay resident -- all of them;
+    else one channel always, and more only if their labels fit beside the flow vectors, the floods in flight and a Farneback
+    scratch worth having (40 GB).  Same labels either way."""
+    n_windows = len(bounds)
+    n_fly = int(max(1, min(max_in_flight, n_windows * C, FLOOD_SLOTS)))
+
+    def room_for(cs, slots):
+        return _room_beside_the_flow(T, H, W, bounds, slots, cs, hand_out, C > 1)
+    if not (bool(stream_windows) and n_windows > 1):
+        Cs = 0
+    elif hand_out or C == 1:
+        Cs = C
+    else:
+        Cs = max([cs for cs in range(1, C + 1) if room_for(cs, n_fly) >= 40e9] or [0])
+    if C > 1 and Cs > 0:
+        # fewer flood slots before a starved flow: the floods run one after the other on the one flood stream anyway, the
+        # slots beyond the third only keep more host replays in flight
+        n_fly = next((nf for nf in range(n_fly, 2, -1) if room_for(Cs, nf) >= 50e9), min(n_fly, 3))
+    return Cs, n_fly
+
+
+def _slots_after_the_flow(o, H, W, max_in_flight, flow_released):
+    """the flood slots of a channel whose windows are begun after the stack's flow.  Every flood in flight owns ~17 B of
+    scratch per window voxel until it is finished.  The Farneback scratch of create_flow (up to 115 GB) is idle from here to
+    the next create_flow: the floods take their scratch from it, piece by piece, instead of allocating another 50 - 100 GB
+    beside it (which the device does not have)."""
+    import torch
+    from tobac_flow_amd import _lib
+    n_windows, per_job = len(o.bounds), _flood_scratch_bytes(o.bounds, H, W)
+    fb = None if flow_released else _lib.borrow_workspace("farneback")
+    if fb is not None and fb.numel() >= per_job:
+        n_fly = int(max(1, min(max_in_flight, n_windows, fb.numel() // per_job)))
+        piece = fb.numel() // n_fly // 256 * 256
+        return [fb[k * piece:(k + 1) * piece] for k in range(n_fly)]
+    # no scratch to borrow (released): every flood in flight allocates ~8 GB + its field and seeds; the labels of the
+    # channel (4 B per window voxel, rewritten in place by the stitch) still have to fit beside them
+    free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+    held = sum(int(v.numel()) for k, v in list(_lib._WS.items()) if v is not None and k[0].startswith("watershed_job"))
+    # (a flood in flight: scratch + field + seeds ~ 1.5 x the scratch; one window's transients: ~1.5 x more)
+    room = 0.75 * (free + held - 4 * sum(hi - lo for lo, hi in o.bounds) * H * W - 3 * per_job // 2)
+    n_fly = int(max(1, min(max_in_flight, n_windows, room // (3 * per_job // 2))))
+    o.mark("floods in flight: %d (free %.1f GB, flood slots held %.1f GB)" % (n_fly, free / 1e9, held / 1e9))
+    return [None] * n_fly
 
 
 def detect_stack_windows(bt, bounds, seeds_fn, channels=1, consume=None, overlap=DEFAULT_OVERLAP, stitch=True, group=None,
@@ -655,8 +908,6 @@ def detect_stack_windows(bt, bounds, seeds_fn, channels=1, consume=None, overlap
     beside them (default: what the device has left after the flow vectors, the labels and the floods in flight, memoised per
     stack shape so that every call of a sweep batches alike).  Each window's labels are those of
     Flow.watershed(get_combined_edge_field(create_flow(window), field), seeds) bit for bit."""
-    import os
-    import time
     import torch
     import tobac_flow_amd.flow as tf
     from tobac_flow_amd import _lib
@@ -665,178 +916,70 @@ def detect_stack_windows(bt, bounds, seeds_fn, channels=1, consume=None, overlap
         raise ValueError("detect_stack_windows: bt must be a (T, H, W) tensor on the GPU")
     T, H, W = bt.shape
     bounds = [(int(lo), int(hi)) for lo, hi in bounds]
-    if not bounds or any(not (0 <= lo < hi <= T) for lo, hi in bounds) or any(b[1] < a[1] or b[0] < a[0] for a, b in zip(bounds[:-1], bounds[1:])):
+    if not bounds or not _bounds_ok(bounds, T):
         raise ValueError("detect_stack_windows: bounds must be ascending (start, stop) windows inside the stack")
-    C = int(channels)
-    o = _StackRun()
-    o.bounds, o.seeds_fn, o.nbr, o.chain_depth, o.on_ambiguous = bounds, seeds_fn, neighbour_offsets(connectivity), chain_depth, on_ambiguous
-    o.info = info if info is not None else {}
-    o.info.setdefault("floods", [])
-    o.info.setdefault("reference_order", [])
-    t_start = time.perf_counter()
-    o.mark = (lambda what: mark(what, (time.perf_counter() - t_start) * 1e3)) if mark is not None else (lambda what: None)
-    o.pool = _replay_pool(max_in_flight)
-    o.side = None
-    n_windows = len(bounds)
-    longest = max(hi - lo for lo, hi in bounds)
-    per_job = 18 * longest * H * W                           # scratch of a flood in flight (~17 B per window voxel)
-    import torch.distributed as dist_
-    o.overlap, o.group = int(overlap), group
-    o.atol, o.rtol, o.sel = LINK_ATOL, LINK_RTOL, compare_frames(int(overlap))
-    o.multi = dist_.is_available() and dist_.is_initialized() and dist_.get_world_size(group) > 1
+    C, hand_out = int(channels), on_window is not None
+    info, mark = _info(info), _timed(mark)
     flow_kw = dict(model=model, vr_steps=vr_steps, smoothing_passes=smoothing_passes, interp_method=interp_method)
     total = torch.cuda.mem_get_info()[1]
-    first = None
-    sum_win = sum(hi - lo for lo, hi in bounds)
-    label_bytes = 4 * sum_win * H * W                        # the windows of ONE channel
-    # How many channels have their windows begun DURING the flow: with on_window no labels stay resident -- all of them; else
-    # one channel always (round 4/5), and more only if their labels fit beside the flow vectors, the floods in flight and a
-    # Farneback scratch worth having (40 GB).  Same labels either way.
-    n_fly = int(max(1, min(max_in_flight, n_windows * C, 5)))
-
-    def room_for(cs, slots=None):
-        free = torch.cuda.mem_get_info()[0] + (torch.cuda.memory_reserved() - torch.cuda.memory_allocated())
-        held = sum(int(v.numel()) for k, v in list(_lib._WS.items()) if v is not None and k[1] == torch.cuda.current_device())
-        resident = 0 if on_window is not None else cs * label_bytes
-        # several channels: what the single-channel estimate leaves out is no longer small beside what is left -- the raw flow
-        # vectors and 8-bit frames of a batch, the refinement's and the labelling's scratch, the flood stream's cached transients
-        # (measured on config F3: 25 GB; the device ran out, the allocator flushed its cache -- a 4.4 s hole in the step)
-        other = int(0.08 * total) if C > 1 else 0
-        return free + held - (2 * T * H * W * 8 + resident + ((n_fly if slots is None else slots) + 1) * (3 * per_job // 2) + other)
-    if not (bool(stream_windows) and n_windows > 1):
-        Cs = 0
-    elif on_window is not None or C == 1:
-        Cs = C
-    else:
-        Cs = max([cs for cs in range(1, C + 1) if room_for(cs) >= 40e9] or [0])
-    if C > 1 and Cs > 0:
-        # fewer flood slots before a starved flow: the floods run one after the other on the one flood stream anyway, the
-        # slots beyond the third only keep more host replays in flight
-        n_fly = next((nf for nf in range(n_fly, 2, -1) if room_for(Cs, nf) >= 50e9), min(n_fly, 3))
-    stream = Cs > 0
-    o.info["channels_begun_during_the_flow"] = Cs
-    if not stream and T * H * W * (1 + 4 + C) * 4 > 0.6 * total:
+    # the plan: the channels begun during the flow, their flood slots, who drives them, the Farneback batches' budget
+    Cs, n_fly = _plan_windows(T, H, W, bounds, C, stream_windows, hand_out, max_in_flight)
+    info["channels_begun_during_the_flow"] = Cs
+    # (measured, config F.  Middle of round 5, six steps each: flood thread 4.48 - 5.11 s per step, mean 4.72; calling thread
+    # 4.66 - 4.75, mean 4.71; flood thread on a low-priority stream 4.72 - 4.87.  End of round 5, with the build that no longer
+    # pairs float operations (csrc/Makefile), two runs of eight steps each, alternating: flood thread 4.53 / 4.59 s per step
+    # (4.44 - 4.70), calling thread 4.62 / 4.65 (4.49 - 4.86) -- the flow's seven parts are enqueued back to back (4.04 s
+    # instead of 4.36 s until the last part has passed), the begins run beside them at 70 - 290 ms each instead of 50 ms
+    # between them: the flood thread is the default, flood_thread=False the calling thread)
+    threaded = Cs > 0 and (flood_thread is None or bool(flood_thread))
+    second = _side_stream() if Cs > 0 else None
+    # (on the flood thread the CURRENT stream is the second stream: floods are finished on it.  On the calling thread the windows
+    # are begun on the calling stream, BETWEEN the flow's batches -- a window's set-up, phase A and chain phases: small,
+    # latency-bound launches with a host synchronisation every 32 sweeps -- and finished floods' root phases run on the second)
+    o = _StackRun(bounds, seeds_fn, neighbour_offsets(connectivity), chain_depth, on_ambiguous, info, mark, _replay_pool(),
+                  None if threaded else second, overlap, group)
+    if Cs == 0 and T * H * W * (1 + 4 + C) * 4 > 0.6 * total:
         # a stack that takes most of the device: the flood slots of the previous call go back to the allocator's cache before
         # the flow is sized (held, they cost the Farneback batches a third of their pairs); the floods take them again afterwards
         for k in range(64):
             _lib.release_workspaces("watershed_job%d" % k)
     retries_before = torch.cuda.memory_stats().get("num_alloc_retries", 0)
-    budget_key = None
-    if stream:
+    budget_key, first = None, None
+    if Cs > 0:
         if flow_workspace_gb is None:
-            # floods in flight beside the flow need scratch of their own (the Farneback workspace is busy): the Farneback batches
-            # get what is left after the flow vectors, the labels of all windows, the floods (scratch + field + seeds ~ 1.5 x
-            # the scratch each, and one window's transients) -- with 30 % of it kept back: free memory that sits in the caching
-            # allocator as fragments cannot serve the one block the Farneback scratch is, and a budget the device can only just
-            # hold costs allocator retries (measured: 98.8 GB -> batches of 64 pairs, 268 GB at the peak, steps of 4.7 / 8.4 /
-            # 6.4 s instead of 4.6).  Memoised per stack shape: the batches of every call of a sweep are then the same, whatever
-            # an earlier call left cached.  Config F (144 x 5424^2, 12 windows) on 288 GB: 86 GB -- any budget from 65 to 98 GB
-            # gives the library's batch hint 21 full-resolution pairs, i.e. 42-pair batches finished in two parts of 21.
-            key = (torch.cuda.current_device(), T, H, W, tuple(bounds), n_fly, Cs, on_window is not None)
-            if key not in _BUDGET_MEMO:
-                _BUDGET_MEMO[key] = max(4.0, 0.7 * room_for(Cs) / 1e9)
-            flow_workspace_gb = _BUDGET_MEMO[key]
-            budget_key = key
+            budget_key, flow_workspace_gb = _flow_budget_gb("windows", T, H, W, bounds, n_fly, Cs, hand_out, C > 1)
+        info["floods_in_flight"], info["flood_thread"] = n_fly, threaded
         slots = [None] * n_fly                               # the flood slots, shared by the channels begun during the flow
-        streamed = [_WindowFloods(o, bt, c, slots, n_fly) for c in range(Cs)]
-        for wf_ in streamed:
-            wf_.on_window = on_window
-        first = _ChannelGroup(streamed)
-        o.info["floods_in_flight"] = n_fly
-        o.side = _side_stream()
+        first = _FloodFamily()
+        first.active = [_WindowFloods(o, bt, c, slots, on_window, own_stream=threaded, family=first if Cs > 1 else None)
+                        for c in range(Cs)]
+        # The flood thread gets (flow, n, event behind the batch) from the callback; it polls the event on the host, finishing
+        # ready floods meanwhile, then begins the windows that end within the first n frames.  What it reads of the stack's flow
+        # arrays is final by then (the flow of a frame pair is written once, before its event); window_view's two patched end
+        # frames lie inside windows of this same thread only, which it handles one after the other.
+        flood = _FloodThread(handle=lambda box: first.begin_up_to(*box.pop()), abandon=first.abandon_all, after=first.finish_all,
+                             stream=second, device=torch.cuda.current_device()) if threaded else None
 
-        # (measured, config F.  Middle of round 5, six steps each: flood thread 4.48 - 5.11 s per step, mean 4.72; calling thread
-        # 4.66 - 4.75, mean 4.71; flood thread on a low-priority stream 4.72 - 4.87.  End of round 5, with the build that no longer
-        # pairs float operations (csrc/Makefile), two runs of eight steps each, alternating: flood thread 4.53 / 4.59 s per step
-        # (4.44 - 4.70), calling thread 4.62 / 4.65 (4.49 - 4.86) -- the flow's seven parts are enqueued back to back (4.04 s
-        # instead of 4.36 s until the last part has passed), the begins run beside them at 70 - 290 ms each instead of 50 ms
-        # between them: the flood thread is the default, TF_WINDOWS_THREAD=0 / flood_thread=False the calling thread)
-        threaded = flood_thread if flood_thread is not None else os.environ.get("TF_WINDOWS_THREAD", "1") == "1"
-        o.info["flood_thread"] = bool(threaded)
-        if not threaded:
-            # the calling thread begins the windows itself, inside create_flow's callback -- on the calling stream, i.e. BETWEEN the
-            # flow's batches (a window's set-up, phase A and chain phases: small, latency-bound launches with a host
-            # synchronisation every 32 sweeps); finished floods' root phases run on the second stream
-            def frames_ready(fl, n):
-                o.mark("flow enqueued for %d frames" % n)
-                ev = torch.cuda.Event()
-                ev.record()
+        def frames_ready(fl, n):
+            o.mark("flow enqueued for %d frames" % n)
+            ev = torch.cuda.Event()
+            ev.record()
+            if flood is None:
                 first.begin_up_to(fl, n, wait_for=ev)
-            worker = None
-        else:
-            # A FLOOD THREAD with the second stream as its current stream drives every window -- seeds, edge field, begin,
-            # finish -- while the calling thread does nothing but enqueue the flow's batches: the floods' latency-bound sweeps
-            # run BESIDE the next batches' kernels instead of between them (the library is re-entrant per stream; scratch and
-            # memos of the Python layer are keyed by (device, stream)).  The callback hands over (flow, n, event behind the
-            # batch); the thread polls the event on the host, finishing ready floods meanwhile, then begins the windows that
-            # end within the first n frames.  What it reads of the stack's flow arrays is final by then (the flow of a frame
-            # pair is written once, before its event); window_view's two patched end frames lie inside windows of this same
-            # thread only, which it handles one after the other.
-            import queue
-            import threading
-            handover = queue.Queue()
-            failure = []
-            flood_stream, dev_index = o.side, torch.cuda.current_device()
-            first.set_own_stream(True)
-            o.side = None                                      # (the thread's CURRENT stream is the second stream: floods are finished on it)
-
-            def flood_loop():
-                try:
-                    torch.cuda.set_device(dev_index)
-                    with torch.cuda.stream(flood_stream):
-                        while True:
-                            item = handover.get()
-                            if item is None:
-                                break
-                            first.begin_up_to(item[0], item[1], wait_for=item[2])
-                        first.finish_all()
-                        flood_stream.synchronize()
-                except BaseException as exc:                    # noqa: BLE001 -- re-raised on the calling thread
-                    failure.append(exc)
-                    try:
-                        flood_stream.synchronize()
-                    except BaseException:                       # noqa: BLE001
-                        pass
-                    first.abandon_all()                        # (slots and scratch of the floods in flight go back now)
-                    while True:                                # drain: the calling thread must never block on a full hand-over
-                        try:
-                            if handover.get_nowait() is None:
-                                break
-                        except queue.Empty:
-                            break
-
-            worker = threading.Thread(target=flood_loop, name="tf-window-floods", daemon=True)
-            worker.start()
-
-            def frames_ready(fl, n):
-                if failure:                                    # the flood thread has failed: stop the flow here, not after the
-                    raise failure[0]                           # rest of the stack has been enqueued
-                o.mark("flow enqueued for %d frames" % n)
-                if os.environ.get("TF_WINDOWS_MEMDEBUG"):      # development aid: who holds the device's memory at this point
-                    ws = sorted(((int(v.numel()), k[0], k[2]) for k, v in list(_lib._WS.items()) if v is not None), reverse=True)
-                    print("  mem: allocated %.1f GB, reserved %.1f GB; workspaces %s" % (
-                        torch.cuda.memory_allocated() / 1e9, torch.cuda.memory_reserved() / 1e9,
-                        ", ".join("%s@%x %.1f" % (t_, s_ & 0xffff, b_ / 1e9) for b_, t_, s_ in ws[:14])), flush=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                handover.put((fl, n, ev))
+            else:
+                flood.put((fl, n, ev))
         # a batch has twice the pairs at the pyramid levels >= 2 (with half, their launches are one half-empty round of
         # workgroups) and is finished -- finest levels, refinement, smoothing, hand-over of its frames -- in two parts
         try:
-            flow_all = tf.create_flow(bt, on_frames_ready=frames_ready, workspace_gb=flow_workspace_gb, split_parts=2, **flow_kw)
+            with flood if flood is not None else contextlib.nullcontext():
+                flow_all = tf.create_flow(bt, on_frames_ready=frames_ready, workspace_gb=flow_workspace_gb, split_parts=2, **flow_kw)
         except BaseException:
-            if worker is None:                                 # (the calling thread drives the floods: theirs to give up)
+            if flood is None:                                  # (the calling thread drives the floods: theirs to give up)
                 first.abandon_all()
             raise
-        finally:
-            if worker is not None:
-                handover.put(None)
-                worker.join()
-        if worker is not None and failure:
-            raise failure[0]
     else:
         flow_all = tf.create_flow(bt, deferred_check=True, **flow_kw)     # (flow_all.check() below, behind the last flood)
-    o.info["flow_workspace_gb"] = None if flow_workspace_gb is None else round(float(flow_workspace_gb), 1)
+    info["flow_workspace_gb"] = None if flow_workspace_gb is None else round(float(flow_workspace_gb), 1)
     o.mark("create_flow returned (device still working)")
     flow_released = False
     if T * H * W * (1 + 4 + C) * 4 > 0.6 * total:
@@ -849,54 +992,20 @@ def detect_stack_windows(bt, bounds, seeds_fn, channels=1, consume=None, overlap
         first.begin_up_to(flow_all, T)                       # (every window has been begun by the last hand-over: a no-op then)
         first.finish_all()
     for c in range(C):                                       # channels one after the other: their labels leave in that order
-        wq = None
-        if first is not None and c < Cs:
-            wq = first.floods[c]
+        if c < Cs:
+            wq = first.active[c]
         else:
-            # Every flood in flight owns ~17 B of scratch per window voxel until it is finished.  The Farneback scratch of
-            # create_flow (up to 115 GB) is idle from here to the next create_flow: the floods take their scratch from it,
-            # piece by piece, instead of allocating another 50 - 100 GB beside it (which the device does not have).
-            fb = None if flow_released else _lib.borrow_workspace("farneback")
-            if fb is not None and fb.numel() >= per_job:
-                n_fly = int(max(1, min(max_in_flight, n_windows, fb.numel() // per_job)))
-                piece = fb.numel() // n_fly // 256 * 256
-                pieces = [fb[k * piece:(k + 1) * piece] for k in range(n_fly)]
-            else:
-                # no scratch to borrow (released above): every flood in flight allocates ~8 GB + its field and seeds; the
-                # labels of the channel (4 B per window voxel, rewritten in place by the stitch) still have to fit beside them
-                free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-                held = sum(int(v.numel()) for k, v in list(_lib._WS.items()) if v is not None and k[0].startswith("watershed_job"))
-                # (a flood in flight: scratch + field + seeds ~ 1.5 x the scratch; one window's transients: ~1.5 x more)
-                room = 0.75 * (free + held - 4 * sum(hi - lo for lo, hi in bounds) * H * W - 3 * per_job // 2)
-                n_fly = int(max(1, min(max_in_flight, n_windows, room // (3 * per_job // 2))))
-                o.mark("floods in flight: %d (free %.1f GB, flood slots held %.1f GB)" % (n_fly, free / 1e9, held / 1e9))
-                pieces = [None] * n_fly
-            o.info["floods_in_flight"] = n_fly
-            wq = _WindowFloods(o, bt, c, pieces, n_fly)
-            wq.on_window = on_window
+            pieces = _slots_after_the_flow(o, H, W, max_in_flight, flow_released)
+            info["floods_in_flight"] = len(pieces)
+            wq = _WindowFloods(o, bt, c, pieces, on_window)
         wq.begin_up_to(flow_all, T)
         wins = wq.finish_all()
-        if on_window is not None:
+        if hand_out:
             # hand-out mode: the windows have left one by one; what is returned are the callee's values and the tables
             results.append({"windows": wq.handed, "luts": wq.tables() if stitch else None})
             o.mark("channel %d: tables" % c)
-            del wins, wq
-            continue
-        if o.info.get("flood_thread"):
-            # the flood thread allocated the labels under ITS stream; from here on they are the caller's, used on the caller's
-            # stream: tell the caching allocator, or a later allocation of the flood stream could take a block the caller has
-            # dropped while kernels of the caller's stream still read it (the same rule as WatershedJob.step(stream=...))
-            for w_ in wins:
-                if w_ is not None and w_.is_cuda:
-                    w_.record_stream(torch.cuda.current_stream())
-        o.mark("all windows finished")
-        # label ids of all windows (of all ranks) made consistent: pair counting on the GPU, one union-find, one LUT pass
-        import torch.distributed as dist
-        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-        if stitch and (len(wins) > 1 or multi):
-            wins = stitch_rank_windows(wins, group=group, overlap=overlap, inplace=True)
-            o.mark("stitched")
-        results.append(wins if consume is None else consume(c, wins))
+        else:
+            results.append(_deliver(o, wins, c, stitch, consume, torch.cuda.current_stream() if threaded else None))
         del wins, wq
     # the stack's flow was computed asynchronously: by now every window has been finished (host synchronisations behind the
     # flow's last launch) -- a starved chain of the iteration kernel (NaN rows, TF_ESTARVED) is reported here at the latest
@@ -906,38 +1015,31 @@ def detect_stack_windows(bt, bounds, seeds_fn, channels=1, consume=None, overlap
     # back to the driver and retry, which synchronises everything: seconds, measured on config F3 (three channels beside 136 GB
     # of flow vectors: a 4.4 s hole in a 14.6 s step) -- the next call of this shape gives the Farneback batches a quarter less.
     retries = torch.cuda.memory_stats().get("num_alloc_retries", 0) - retries_before
-    o.info["allocator_retries"] = int(retries)
+    info["allocator_retries"] = int(retries)
     if retries > 0 and budget_key is not None:
         _BUDGET_MEMO[budget_key] = max(4.0, 0.75 * _BUDGET_MEMO[budget_key])
-    return results, o.info
+    return results, info
 
 
-class _SequenceFloods:
-    """The stacks of a detect_stack_sequence call that still have floods in flight, oldest first: they share the flood slots,
-    and whoever waits -- for a slot, for a hand-over's event -- finishes whichever flood of whichever stack is ready."""
-
-    def __init__(self, deliver):
-        self.active, self.deliver = [], deliver
-
-    def finish_any(self, block=True):
-        from concurrent.futures import FIRST_COMPLETED, wait
-        while True:
-            for wf in list(self.active):
-                if wf.pending and wf.finish_one(block=False):
-                    self.settle(wf)
-                    return True
-            if not block:
-                return False
-            futs = [p[1] for wf in self.active for p in wf.pending if p[1] is not None]
-            if not futs:
-                return False
-            wait(futs, return_when=FIRST_COMPLETED)
-
-    def settle(self, wf):
-        """a stack whose every window has its labels: stitch, hand over, forget"""
-        if wf in self.active and wf.next == len(wf.o.bounds) and not wf.pending and getattr(wf, "flow_enqueued", False):
-            self.active.remove(wf)
-            self.deliver(wf)
+def _handle_sequence_item(fam, flood_stream, box):
+    """detect_stack_sequence's flood thread: ("new", stack) -- a stack joins those in flight; ("frames", stack, flow, n, event) --
+    the hand-over of create_flow's callback; ("end", stack) -- its flow is enqueued to the last frame"""
+    item = box.pop()
+    what, wf = item[0], item[1]
+    if what == "new":
+        fam.active.append(wf)
+    elif what == "frames":
+        begun = wf.setup_up_to(item[2], item[3], wait_for=item[4])
+        item = None                                          # (the hand-over holds the stack's Flow: 68 GB at config F that must be free for the next stack)
+        if wf.next == len(wf.o.bounds) and not wf.setups_done.is_set():
+            # the stack's last window is set up: nothing reads its flow vectors any more (the sweeps that follow work on the
+            # compact graph) -- the calling thread releases them and enqueues the next stack's flow
+            flood_stream.synchronize()                       # (window_view's restored frames have landed)
+            wf.setups_done.set()
+        wf.sweep(begun)
+    elif what == "end":
+        wf.flow_enqueued = True
+        fam.settle(wf)
 
 
 def detect_stack_sequence(stacks, bounds, seeds_fn, consume=None, overlap=DEFAULT_OVERLAP, stitch=True, group=None,
@@ -955,156 +1057,57 @@ def detect_stack_sequence(stacks, bounds, seeds_fn, consume=None, overlap=DEFAUL
     stitch=False -- and its return value collected (default: the windows themselves; a sweep that keeps every stack's label
     windows resident runs out of memory: reduce or store them there).  Returns (results, info) like detect_stack_windows.
     With a process group every rank must pass the same number of stacks (the stitch of stack k is a collective)."""
-    import os
-    import queue
-    import threading
-    import time
     import torch
     import tobac_flow_amd.flow as tf
     from tobac_flow_amd.watershed import neighbour_offsets
     bounds = [(int(lo), int(hi)) for lo, hi in bounds]
-    if len(bounds) < 2 or any(b[1] < a[1] or b[0] < a[0] for a, b in zip(bounds[:-1], bounds[1:])):
+    if len(bounds) < 2 or not _bounds_ok(bounds):
         raise ValueError("detect_stack_sequence: bounds must be two or more ascending (start, stop) windows")
-    info = info if info is not None else {}
-    info.setdefault("floods", [])
-    info.setdefault("reference_order", [])
-    t_start = time.perf_counter()
-    marker = (lambda what: mark(what, (time.perf_counter() - t_start) * 1e3)) if mark is not None else (lambda what: None)
-    n_windows = len(bounds)
-    n_fly = int(max(1, min(max_in_flight, n_windows, int(os.environ.get("TF_WINDOWS_SLOTS", "5")))))      # (development switch: flood slots)
+    info, marker = _info(info), _timed(mark)
+    n_fly = int(max(1, min(max_in_flight, len(bounds), FLOOD_SLOTS)))
     pieces = [None] * n_fly                                  # the flood slots, shared by the stacks in flight
-    pool = _replay_pool(max_in_flight)
-    nbr = neighbour_offsets(connectivity)
+    pool, nbr = _replay_pool(), neighbour_offsets(connectivity)
     flow_kw = dict(model=model, vr_steps=vr_steps, smoothing_passes=smoothing_passes, interp_method=interp_method)
-    results, failure = {}, []
-    handover = queue.Queue()
-    dev_index = torch.cuda.current_device()
-    main_stream = torch.cuda.current_stream()
-    flood_stream = _side_stream()
+    results = {}
+    main_stream, flood_stream = torch.cuda.current_stream(), _side_stream()
     info["floods_in_flight"], info["flood_thread"], info["stacks_pipelined"] = n_fly, True, True
     info["channels_begun_during_the_flow"] = 1
 
     def deliver(wf):
-        wins = wf.wins
-        wf.o.mark("stack %d: all windows finished" % wf.index)
-        import torch.distributed as dist
-        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-        if stitch and (len(wins) > 1 or multi):
-            wins = stitch_rank_windows(wins, group=group, overlap=overlap, inplace=True)
-            wf.o.mark("stack %d: stitched" % wf.index)
-        for w_ in wins:                                      # (allocated under the flood stream; the caller's stream may use them afterwards)
-            if w_ is not None and w_.is_cuda:
-                w_.record_stream(main_stream)
-        results[wf.index] = wins if consume is None else consume(wf.index, wins)
+        results[wf.index] = _deliver(wf.o, wf.wins, wf.index, stitch, consume, main_stream, "stack %d: " % wf.index)
         wf.wins = None
-        wf.delivered.set()
 
-    fam = _SequenceFloods(deliver)
-
-    def flood_loop():
-        try:
-            torch.cuda.set_device(dev_index)
-            with torch.cuda.stream(flood_stream):
-                while True:
-                    try:
-                        item = handover.get(timeout=0.0005) if fam.active else handover.get()
-                    except queue.Empty:
-                        fam.finish_any(block=False)
-                        continue
-                    if item is None:
-                        break
-                    what, wf = item[0], item[1]
-                    if what == "new":
-                        fam.active.append(wf)
-                    elif what == "frames":
-                        begun = wf.setup_up_to(item[2], item[3], wait_for=item[4])
-                        item = None                              # (the hand-over holds the stack's Flow: 68 GB at config F)
-                        if wf.next == n_windows and not wf.setups_done.is_set():
-                            # the stack's last window is set up: nothing reads its flow vectors any more (the sweeps that follow
-                            # work on the compact graph) -- the calling thread releases them and enqueues the next stack's flow
-                            flood_stream.synchronize()           # (window_view's restored frames have landed)
-                            wf.setups_done.set()
-                        wf.sweep(begun)
-                        begun = None
-                    elif what == "end":
-                        wf.flow_enqueued = True
-                        fam.settle(wf)
-                    item = wf = None                             # (a hand-over holds the stack's Flow: 68 GB at config F that must be free for the next stack)
-                while fam.active:                                # the last stack's end: nothing left to run beside it
-                    if not fam.finish_any(block=True):
-                        for wf in list(fam.active):
-                            fam.settle(wf)
-                        if fam.active:
-                            raise RuntimeError("detect_stack_sequence: a stack is left with windows that were never begun")
-                flood_stream.synchronize()
-        except BaseException as exc:                             # noqa: BLE001 -- re-raised on the calling thread
-            failure.append(exc)
-            try:
-                flood_stream.synchronize()
-            except BaseException:                                # noqa: BLE001
-                pass
-            for wf_ in list(fam.active):                         # (slots and scratch of the floods in flight go back now)
-                wf_.abandon_all()
-            while True:                                          # drain: the calling thread must never block on the hand-over
-                try:
-                    if handover.get(timeout=0.05) is None:
-                        break
-                except queue.Empty:
-                    if stop.is_set():
-                        break
-
-    stop = threading.Event()
-    worker = threading.Thread(target=flood_loop, name="tf-window-floods", daemon=True)
-    worker.start()
+    fam = _FloodFamily(deliver)
+    flood = _FloodThread(handle=lambda box: _handle_sequence_item(fam, flood_stream, box), abandon=fam.abandon_all,
+                         after=fam.deliver_all, idle=fam.poll, stream=flood_stream, device=torch.cuda.current_device())
     n_stacks = 0
-    try:
+    with flood:
         for k, bt in enumerate(stacks):
             if not (isinstance(bt, torch.Tensor) and bt.is_cuda and bt.dim() == 3):
                 raise ValueError("detect_stack_sequence: every stack must be a (T, H, W) tensor on the GPU")
             T, H, W = bt.shape
-            if any(not (0 <= lo < hi <= T) for lo, hi in bounds) or bounds[-1][1] != T:
+            if not _bounds_ok(bounds, T) or bounds[-1][1] != T:
                 raise ValueError("detect_stack_sequence: bounds must lie inside every stack and end with it")
-            o = _StackRun()
-            o.bounds, o.seeds_fn, o.nbr, o.chain_depth, o.on_ambiguous = bounds, seeds_fn, nbr, chain_depth, on_ambiguous
-            o.info, o.pool, o.side, o.mark = info, pool, None, (lambda what, k_=k: marker("[stack %d] %s" % (k_, what)))
+            o = _StackRun(bounds, seeds_fn, nbr, chain_depth, on_ambiguous, info, lambda what, k_=k: marker("[stack %d] %s" % (k_, what)),
+                          pool, None, overlap, group)
             if flow_workspace_gb is None:
-                longest = max(hi - lo for lo, hi in bounds)
-                per_job = 18 * longest * H * W
-                key = (torch.cuda.current_device(), T, H, W, tuple(bounds), n_fly)
-                if key not in _BUDGET_MEMO:
-                    free = torch.cuda.mem_get_info()[0] + (torch.cuda.memory_reserved() - torch.cuda.memory_allocated())
-                    from tobac_flow_amd import _lib
-                    held = sum(int(v.numel()) for kk, v in list(_lib._WS.items()) if v is not None and kk[1] == torch.cuda.current_device())
-                    need = 2 * T * H * W * 8 + 4 * sum(hi - lo for lo, hi in bounds) * H * W + (n_fly + 1) * (3 * per_job // 2)
-                    _BUDGET_MEMO[key] = max(4.0, 0.7 * (free + held - need) / 1e9)
-                flow_workspace_gb = _BUDGET_MEMO[key]
+                _, flow_workspace_gb = _flow_budget_gb("sequence", T, H, W, bounds, n_fly, 1, False, False)
                 info["flow_workspace_gb"] = round(float(flow_workspace_gb), 1)
-            wf = _WindowFloods(o, bt, 0, pieces, n_fly)
-            wf.family, wf.index, wf.flow_enqueued, wf.own_stream = fam, k, False, True
-            wf.setups_done, wf.delivered = threading.Event(), threading.Event()
-            handover.put(("new", wf))
+            wf = _WindowFloods(o, bt, 0, pieces, own_stream=True, family=fam, index=k)
+            flood.put(("new", wf))
 
-            def frames_ready(fl, n, wf_=wf, o_=o):
-                if failure:                                      # (stop this stack's flow where the flood thread failed)
-                    raise failure[0]
-                o_.mark("flow enqueued for %d frames" % n)
+            def frames_ready(fl, n, wf_=wf):
+                wf_.o.mark("flow enqueued for %d frames" % n)
                 ev = torch.cuda.Event()
                 ev.record()
-                handover.put(("frames", wf_, fl, n, ev))
+                flood.put(("frames", wf_, fl, n, ev))
             flow = tf.create_flow(bt, on_frames_ready=frames_ready, workspace_gb=flow_workspace_gb, split_parts=2, **flow_kw)
-            handover.put(("end", wf))
+            flood.put(("end", wf))
             n_stacks += 1
             # this stack's flow vectors are read until its last window has been set up: then they go, and the next stack's flow
             # is enqueued while the flood thread is still sweeping, replaying and stitching this one
             while not wf.setups_done.wait(0.002):
-                if failure:
-                    raise failure[0]
+                flood.check()
             flow.check()                                         # (a starved chain of the iteration kernel is reported per stack)
             del flow
-    finally:
-        stop.set()
-        handover.put(None)
-        worker.join()
-    if failure:
-        raise failure[0]
     return [results[k] for k in range(n_stacks)], info
