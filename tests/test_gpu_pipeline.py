@@ -157,29 +157,24 @@ def test_create_flow_clip_is_the_elementwise_clip_of_the_unclipped_flow(smoothin
     assert bool(torch.isnan(one.forward_flow).all()) and bool(torch.isnan(one.backward_flow).all())
 
 
-def test_flow_batches_and_stream_overlap_do_not_change_the_flow(monkeypatch):
-    """The flow of a stack does not depend on how its pairs are batched, nor on whether the refinement / smoothing of a
-    batch runs on the second stream while the next batch's Farneback is under way (flow.py: _calculate_flow_impl)."""
+def test_flow_batches_do_not_change_the_flow():
+    """The flow of a stack does not depend on how its pairs are batched (flow.py: create_flow(batch_pairs=...))."""
     import torch
     import tobac_flow_amd.flow as tf
     from tools.synth import blob_stack
     bt = blob_stack(8, 180, 236, seed=9)
     kw = dict(model="Farneback", vr_steps=1, smoothing_passes=1, interp_method="cubic")
-    monkeypatch.setenv("TF_FLOW_OVERLAP", "0")
-    monkeypatch.setenv("TF_FLOW_BATCH", "64")
-    want = tf.create_flow(bt, **kw)                                    # one batch, one stream
-    for batch, overlap in (("2", "1"), ("3", "1"), ("2", "0"), ("1", "1")):
-        monkeypatch.setenv("TF_FLOW_BATCH", batch)
-        monkeypatch.setenv("TF_FLOW_OVERLAP", overlap)
-        for _ in range(2):                                             # twice: the second run reuses the side stream and its buffers
-            got = tf.create_flow(bt, **kw)
+    want = tf.create_flow(bt, batch_pairs=64, **kw)                    # one batch
+    for batch in (2, 3, 1):
+        for _ in range(2):                                             # twice: the second run reuses the pooled buffers
+            got = tf.create_flow(bt, batch_pairs=batch, **kw)
             torch.cuda.synchronize()
             for g, w in ((got.forward_flow, want.forward_flow), (got.backward_flow, want.backward_flow)):
-                assert torch.equal(torch.nan_to_num(g, nan=-777.0), torch.nan_to_num(w, nan=-777.0)), (batch, overlap)
+                assert torch.equal(torch.nan_to_num(g, nan=-777.0), torch.nan_to_num(w, nan=-777.0)), batch
 
 
 def test_a_batch_that_does_not_fit_is_halved_and_the_flow_is_the_same(monkeypatch):
-    """_calculate_flow_impl sizes its Farneback batches from an ESTIMATE of the free memory; a batch whose scratch cannot
+    """create_flow sizes its Farneback batches from an ESTIMATE of the free memory; a batch whose scratch cannot
     be allocated after all (fragmented allocator) is halved and tried again, together with the batches after it -- the
     flow does not change.  Simulated here with a model that refuses every batch of more than two pairs."""
     import torch
@@ -257,7 +252,6 @@ def test_create_flow_on_frames_ready_hands_out_final_windows():
     that ends within the first n frames is then already the window of the finished Flow, bit for bit -- which is what lets
     bench.py begin a window's Sobel / seeds / flood (and its host replay) while the device computes the flow of the later
     frames.  Checked: the windows copied out inside the callbacks equal create_flow(window) of a fresh call."""
-    import os
     import torch
     import tobac_flow_amd.flow as tf
     from tools.synth import blob_stack
@@ -271,15 +265,8 @@ def test_create_flow_on_frames_ready_hands_out_final_windows():
             if b <= n and (a, b) not in got:
                 with flow.window_view(a, b) as w:
                     got[(a, b)] = (w.forward_flow.clone(), w.backward_flow.clone())
-    old = os.environ.get("TF_FLOW_BATCH")
-    os.environ["TF_FLOW_BATCH"] = "3"                                  # four batches of 3 / 3 / 2 / 2 pairs
-    try:
-        full = tf.create_flow(bt, vr_steps=1, smoothing_passes=1, interp_method="cubic", on_frames_ready=ready)
-    finally:
-        if old is None:
-            del os.environ["TF_FLOW_BATCH"]
-        else:
-            os.environ["TF_FLOW_BATCH"] = old
+    full = tf.create_flow(bt, vr_steps=1, smoothing_passes=1, interp_method="cubic", on_frames_ready=ready,
+                          batch_pairs=3)                               # four batches of 2 / 3 / 3 / 2 pairs
     assert seen == sorted(seen) and seen[-1] == 11 and len(seen) >= 3
     assert set(got) == set(bounds)
     plain = tf.create_flow(bt, vr_steps=1, smoothing_passes=1, interp_method="cubic")
@@ -354,29 +341,29 @@ def test_watershed_job_in_parts_on_a_second_stream_equals_the_one_call(golden_ws
 
 
 def test_create_flow_with_split_batches_is_bit_identical_and_hands_out_parts(monkeypatch):
-    """TF_FLOW_SPLIT=2: a batch runs its coarse pyramid levels for all pairs at once and its two finest levels, refinement and
+    """split_parts=2: a batch runs its coarse pyramid levels for all pairs at once and its two finest levels, refinement and
     smoothing part by part (tf_farneback_batch_phase); the flows are those of the unsplit schedule bit for bit, and
     on_frames_ready fires after every PART."""
     import torch
     import tobac_flow_amd.flow as tf
     from tools.synth import blob_stack
     bt = blob_stack(11, 203, 331, seed=9, t0=1)
-    want = tf.create_flow(bt, vr_steps=1, smoothing_passes=1, interp_method="cubic")
-    monkeypatch.setenv("TF_FLOW_SPLIT", "2")
+    kw = dict(vr_steps=1, smoothing_passes=1, interp_method="cubic")
+    want = tf.create_flow(bt, **kw)
     seen = []
-    got = tf.create_flow(bt, vr_steps=1, smoothing_passes=1, interp_method="cubic", on_frames_ready=lambda fl, n: seen.append(n))
+    got = tf.create_flow(bt, split_parts=2, on_frames_ready=lambda fl, n: seen.append(n), **kw)
     assert seen == [11]                                               # parts of five pairs of 203 x 331 would not fill the GPU: not split
-    monkeypatch.setenv("TF_FLOW_SPLIT_FORCE", "1")                    # (split whatever the size)
+    monkeypatch.setattr(tf, "_part_fills_a_round", lambda *a: True)   # (split whatever the size)
     seen = []
-    got = tf.create_flow(bt, vr_steps=1, smoothing_passes=1, interp_method="cubic", on_frames_ready=lambda fl, n: seen.append(n))
+    got = tf.create_flow(bt, split_parts=2, on_frames_ready=lambda fl, n: seen.append(n), **kw)
     assert seen == [6, 11]                                            # ten pairs: two parts of five
     assert torch.equal(torch.nan_to_num(got.forward_flow, nan=-7.0), torch.nan_to_num(want.forward_flow, nan=-7.0))
     assert torch.equal(torch.nan_to_num(got.backward_flow, nan=-7.0), torch.nan_to_num(want.backward_flow, nan=-7.0))
-    raw = tf.calculate_flow(bt, "Farneback")                          # no refinement, no smoothing: written straight into the arrays
-    monkeypatch.delenv("TF_FLOW_SPLIT")
-    monkeypatch.delenv("TF_FLOW_SPLIT_FORCE")
+    # no refinement, no smoothing: written straight into the arrays
+    raw = tf.create_flow(bt, split_parts=2, max_value=float("inf"))
+    monkeypatch.undo()
     raw0 = tf.calculate_flow(bt, "Farneback")
-    assert torch.equal(torch.nan_to_num(raw[0], nan=-7.0), torch.nan_to_num(raw0[0], nan=-7.0))
+    assert torch.equal(torch.nan_to_num(raw.forward_flow, nan=-7.0), torch.nan_to_num(raw0[0], nan=-7.0))
 
 
 def test_out_of_memory_in_the_callback_is_the_callers_and_handed_out_frames_are_never_recomputed(monkeypatch):
@@ -399,14 +386,12 @@ def test_out_of_memory_in_the_callback_is_the_callers_and_handed_out_frames_are_
     def greedy(flow, n):
         calls.append(n)
         raise torch.OutOfMemoryError("simulated: the caller's own allocation failed")
-    monkeypatch.setenv("TF_FLOW_BATCH", "4")
     with pytest.raises(torch.OutOfMemoryError, match="caller's own"):
-        tf.create_flow(bt, on_frames_ready=greedy, **kw)
+        tf.create_flow(bt, on_frames_ready=greedy, batch_pairs=4, **kw)
     assert calls == [4]                                               # (batches of 3 / 4 / 3 pairs) entered once, not again with a smaller batch
-    monkeypatch.delenv("TF_FLOW_BATCH")
     # (ii)
-    monkeypatch.setenv("TF_FLOW_SPLIT", "2")
-    monkeypatch.setenv("TF_FLOW_SPLIT_FORCE", "1")
+    kw["split_parts"] = 2
+    monkeypatch.setattr(tf, "_part_fills_a_round", lambda *a: True)   # (split whatever the size)
     real = FarnebackFlow.calc_phase_dev
     state = {"phase2_calls": 0, "refused": 0}
 

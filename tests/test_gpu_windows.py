@@ -251,9 +251,10 @@ def test_a_window_that_ends_at_a_hand_over_waits_for_the_next_one_on_the_flood_t
     flood thread == calling thread == the serial plain calls, voxel for voxel."""
     import time
     import torch
+    import tobac_flow_amd.flow as tf
     from tobac_flow_amd.parallel import detect_stack_windows
     from tools.synth import blob_stack
-    monkeypatch.setenv("TF_FLOW_SPLIT_FORCE", "1")
+    monkeypatch.setattr(tf, "_part_fills_a_round", lambda *a: True)     # (split whatever the size)
     t_, h_, w_ = 30, 500, 700
     bt = blob_stack(t_, h_, w_, seed=20240601, t0=2)
     bounds = [(0, 16), (12, 30)]

@@ -10,7 +10,7 @@ any vr_steps > 0 runs exactly ONE refinement per direction.
 """
 import contextlib
 import ctypes
-import os
+import dataclasses
 import warnings
 from datetime import datetime
 from typing import Callable
@@ -19,6 +19,7 @@ import numpy as np
 from scipy import ndimage as ndi
 
 from tobac_flow_amd import _lib
+from tobac_flow_amd._flow_plan import budget_batches, even_batches, flow_budget, requeue_halved, varref_group, varref_tiles
 from tobac_flow_amd.convolve import convolve, tag_func
 from tobac_flow_amd.core import AbstractFlow
 from tobac_flow_amd.label import flow_label, flow_link_overlap
@@ -41,7 +42,7 @@ def _unwrap_device_field(x):
 
 def create_flow(data, model: str = "Farneback", vr_steps: int = 0, smoothing_passes: int = 0,
                 interp_method: str = "linear", max_value=20, on_frames_ready=None, workspace_gb=None,
-                split_parts=None, deferred_check=None) -> "Flow":
+                split_parts=None, deferred_check=None, batch_pairs=None) -> "Flow":
     """Forward and backward optical flow along the leading dimension of `data`, clipped to
     +-`max_value` pixels, wrapped in a Flow object (reference: flow.py:23-65).
 
@@ -52,11 +53,11 @@ def create_flow(data, model: str = "Farneback", vr_steps: int = 0, smoothing_pas
     start on its first windows -- Sobel, seeds, flood, host work -- while the device computes the flow of the later frames
     (parallel.detect_stack_windows).  The calls are made on the calling thread, in order; n == len(data) in the last one.
 
-    workspace_gb / split_parts (not in the reference; scheduling only, the flow is the same bits): the scratch budget of the
-    Farneback batches in GB (default 115, and never more than 60 % of the free device memory) and the number of parts a batch's
-    two finest pyramid levels, refinement and smoothing are run in (default 1; a caller that runs other work beside the
-    flow -- detect_stack_windows -- asks for less scratch and for 2 parts).  The environment variables TF_FLOW_WORKSPACE_GB /
-    TF_FLOW_SPLIT (development switches) override them.
+    workspace_gb / split_parts / batch_pairs (not in the reference; scheduling only, the flow is the same bits): the scratch
+    budget of the Farneback batches in GB (default 115, and never more than 60 % of the free device memory), the number of
+    parts a batch's two finest pyramid levels, refinement and smoothing are run in (default 1; a caller that runs other work
+    beside the flow -- detect_stack_windows -- asks for less scratch and for 2 parts), and a fixed number of frame pairs per
+    batch instead of the budgeted sizes (spread evenly, _flow_plan.even_batches; every batch then runs unsplit).
 
     deferred_check (not in the reference; device-resident input only): create_flow on a device tensor returns while the device
     is still computing, so the library's report on those launches (a starved chain of the iteration kernel -> NaN rows,
@@ -67,43 +68,33 @@ def create_flow(data, model: str = "Farneback", vr_steps: int = 0, smoothing_pas
     before it hands results on."""
     # the clip of flow.py:60-61 is applied by the same kernel that mirrors the end frames (tf_flow_finalize);
     # clipping commutes with the sign-flipped mirror
-    extra = {}
+    # host (numpy / DataArray) input: the flow stays in HBM (device_out), where every Flow method works, and the object's numpy
+    # arrays `forward_flow` / `backward_flow` are downloaded when somebody reads them -- the drop-in scripts never do
+    # (scripts/dcc_detect_goes.py:164-303 only pass the object on), and 2 x 7.5 GB per 16 x 5424^2 window would cross PCIe
+    # twice otherwise (down here, up again at the first Flow method)
+    sched = _Schedule(max_value=float(max_value), device_out=True, workspace_gb=workspace_gb, split_parts=split_parts,
+                      batch_pairs=batch_pairs)
+    holder = {}
     if on_frames_ready is not None:
-        holder = {}
-
         def on_batch(forward, backward, pairs_done, n_pairs):
             if "flow" not in holder:
                 holder["flow"] = Flow(forward, backward)
             on_frames_ready(holder["flow"], pairs_done + 1 if pairs_done < n_pairs else n_pairs + 1)
-        extra["_on_batch"] = on_batch
-    # host (numpy / DataArray) input: the flow stays in HBM, where every Flow method works, and the object's numpy arrays
-    # `forward_flow` / `backward_flow` are downloaded when somebody reads them -- the drop-in scripts never do
-    # (scripts/dcc_detect_goes.py:164-303 only pass the object on), and 2 x 7.5 GB per 16 x 5424^2 window would cross PCIe
-    # twice otherwise (down here, up again at the first Flow method)
-    extra["_device_out"] = True
-    checks = []
-    extra["_check_out"] = checks                # device output: the starved-chain check arrives as a poll bound to an event
-    if workspace_gb is not None:
-        extra["_workspace_gb"] = float(workspace_gb)
-    if split_parts is not None:
-        extra["_split_parts"] = int(split_parts)
+        sched.on_batch = on_batch
     data = _unwrap_device_field(data)
-    forward_flow, backward_flow = calculate_flow(data, model=model, vr_steps=vr_steps,
-                                                 smoothing_passes=smoothing_passes, interp_method=interp_method,
-                                                 _max_value=float(max_value), **extra)
-    t = _lib.torch()
-    if on_frames_ready is not None and "flow" in holder:
+    forward_flow, backward_flow, check = _calculate_flow(data, model, vr_steps, smoothing_passes, interp_method, "linear", {}, sched)
+    on_device = isinstance(data, _lib.torch().Tensor)
+    if "flow" in holder:
         flow = holder["flow"]
-    elif isinstance(data, t.Tensor):
+    elif on_device:
         flow = Flow(forward_flow, backward_flow)
     else:
         flow = Flow._lazy_host(forward_flow, backward_flow)
-    if checks:
-        if isinstance(data, t.Tensor):
-            flow._pending_check = checks[0]       # looked at by every use of the object (Flow._dev_flows); Flow.check() waits for it
-            flow._check_blocking = not (deferred_check if deferred_check is not None else on_frames_ready is not None)
-        else:
-            checks[0](block=True)                # host input: the reference's call is synchronous, so is this one
+    if on_device:
+        flow._pending_check = check               # looked at by every use of the object (Flow._dev_flows); Flow.check() waits for it
+        flow._check_blocking = not (deferred_check if deferred_check is not None else on_frames_ready is not None)
+    else:
+        check(block=True)                         # host input: the reference's call is synchronous, so is this one
     return flow
 
 
@@ -304,10 +295,10 @@ class VariationalRefinement:
         self.fixedPointIterations, self.sorIterations = p.fixed_point_iterations, p.sor_iterations
         self.alpha, self.delta, self.gamma, self.omega = p.alpha, p.delta, p.gamma, p.omega
         # not in OpenCV: True = hardware reciprocals instead of correctly rounded divisions / square roots
-        # (TF_VR_FAST_DIVIDE, include/tobac_flow_hip.h: within 1e-4 px of the default, ~25 % faster); default False
-        self.fastDivide = os.environ.get("TF_VR_FAST_DIVIDE", "0") == "1"
+        # (TF_VR_FAST_DIVIDE, include/tobac_flow_hip.h: within 1e-4 px of the default, ~25 % faster)
+        self.fastDivide = False
         # ... in the SOR sweeps only (TF_VR_FAST_SOR: the system assembly keeps its correctly rounded divisions)
-        self.fastSor = os.environ.get("TF_VR_FAST_SOR", "0") == "1"
+        self.fastSor = False
 
     @classmethod
     def create(cls):
@@ -333,8 +324,7 @@ class VariationalRefinement:
         """The refinement of B images at once (tf_varref_batch: the grid gains an image dimension, the bits are calc_dev's):
         i0, i1 (B, H, W) uint8 device tensors, flow (B, H, W, 2) float32 refined in place -- frames with contiguous rows, any
         stride between them (views into the stack's flow arrays).  Images go out in groups that fill ~`rounds` rounds of the
-        fused SOR kernel's tiles on the device's CUs: at 1500 x 2500 (282 tiles) all 23 pairs of BASELINE config C in one set
-        of 11 launches; at 5424^2 (2279 tiles, 8.9 rounds by itself) one image per launch, as before round 6."""
+        fused SOR kernel's tiles on the device's CUs (_flow_plan.varref_group)."""
         L = _lib.lib()
         t = _lib.torch()
         B, H, W = i0.shape
@@ -343,22 +333,8 @@ class VariationalRefinement:
         if B == 1:
             self.calc_dev(i0[0], i1[0], flow[0])
             return flow
-        tiles = -(-W // 108) * -(-H // 84)
         cus = t.cuda.get_device_properties(i0.device).multi_processor_count
-        group = int(max(1, min(B, -(-rounds * cus // tiles))))
-        # ... but only where ONE image does not fill the chip for several rounds by itself (fewer tiles than 4 x the CUs) and within
-        # 6.5 GB of scratch (48 B per pixel and image).  At 5424^2 an image is 8.9 rounds; three per launch were measured 3 %
-        # slower in bench.py's timed region (vr_sor 925 -> 952 ms per step: longer launches interleave worse with the floods' kernels)
-        if tiles >= 4 * cus and rounds > 0:
-            # ... unless its last round is poorly filled: the smallest group of up to four images that wastes < 3 % of its rounds
-            # (3712^2: 1575 tiles = 6.15 rounds, 14 % of 7 rounds idle by itself, 5 % of 13 in pairs, 3 % of 19 in threes)
-            def waste(g):
-                r = g * tiles / cus
-                return -(-g * tiles // cus) / r - 1.0
-            group = next((g for g in range(1, min(B, 4) + 1) if waste(g) < 0.03), min(range(1, min(B, 4) + 1), key=waste))
-        group = int(max(1, min(group, 6.5e9 // max(1, L.tf_varref_workspace_bytes(H, W)))))
-        if os.environ.get("TF_VR_GROUP"):                    # development switch: images per launch
-            group = max(1, min(B, int(os.environ["TF_VR_GROUP"])))
+        group = varref_group(B, varref_tiles(H, W), cus, rounds, L.tf_varref_workspace_bytes(H, W))
         ws = _lib.workspace(L.tf_varref_workspace_bytes_batch(group, H, W), "varref")
         p = self._params()
         flags = (1 if self.fastDivide else 0) | (2 if self.fastSor else 0)
@@ -428,275 +404,224 @@ def _pair_flows_dev(prev8, next8, of_model, vr_steps, smoothing_steps, interp_me
     return fwd, bwd
 
 
-_SIDE_STREAMS = {}
+@dataclasses.dataclass
+class _Schedule:
+    """How a stack's frame pairs reach the device: what create_flow adds to calculate_flow (same bits, but for the clip)."""
+    max_value: float = float("inf")             # clip of create_flow (inf: none)
+    on_batch: Callable | None = None            # f(forward, backward, pairs_done, n_pairs) after every part of a batch
+    device_out: bool = False                    # host input is treated like device input: device normalisation, flow left in HBM
+    workspace_gb: float | None = None           # scratch budget of the Farneback batches (default 115)
+    split_parts: int | None = None              # parts a batch's two finest levels, refinement and smoothing run in (default 1)
+    batch_pairs: int | None = None              # a fixed number of pairs per batch, run unsplit, instead of the budgeted sizes
 
 
-def _side_stream(main):
-    """one extra stream per (device, calling stream), created on first use"""
+def _pair_normaliser(frame_pairs, stacks, on_device, norm_name, norm_method, normalisation_kwargs):
+    """The callable `(i, out)` that writes the 8-bit frames of pair i into out = (prev8, next8): the linear kernel, the other
+    methods' device form for device data, or the host glue where only that computes what the call asks for (ValueError)."""
     t = _lib.torch()
-    key = (main.device.index, main.cuda_stream)
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = t.cuda.Stream(device=main.device)
-    return _SIDE_STREAMS[key]
+    if norm_name == "linear" and not normalisation_kwargs:
+        return lambda i, out: to_8bit_pair_dev(*frame_pairs(i), out=out)
+    if on_device:
+        try:
+            norm_params_dev(norm_name, tuple(stacks[0].shape[1:]), **normalisation_kwargs)
+            # uniform: finite stacks only (one reduction and one synchronisation per call)
+            if norm_name != "uniform" or all(bool(t.isfinite(s).all()) for s in stacks):
+                return lambda i, out: normalise_pair_dev(norm_name, *frame_pairs(i), out=out, check_finite=False, **normalisation_kwargs)
+        except ValueError:
+            pass
+
+    def host_glue(i, out):                       # (not on the production path; `to_8bit` is this module's, looked up per call)
+        fa, fb = frame_pairs(i)
+        p8 = to_8bit(norm_method(np.stack([fa.cpu().numpy(), fb.cpu().numpy()], 0), **normalisation_kwargs), 0, 1)
+        out[0].copy_(_lib.to_dev(p8[0]))
+        out[1].copy_(_lib.to_dev(p8[1]))
+    return host_glue
 
 
-def _calculate_flow_impl(frame_pairs, T, shape, of_model, vr_steps, smoothing_passes, interp_method,
-                         norm_name, norm_method, normalisation_kwargs, on_device, max_value=float("inf"), on_batch=None,
-                         workspace_gb=None, split_parts=None, check_out=None, stacks=()):
+def _part_fills_a_round(of_model, H, W, pairs):
+    """Does a part of `pairs` pairs still fill a round of the iteration kernel's resident workgroups at the full resolution?
+    (Tests that need a split at toy sizes patch this.)"""
+    # a launch costs whole rounds: parts that do not each cost what the whole batch costs (config C, 23 pairs of 1500 x 2500 =
+    # one round: two parts took 2 x 2.3 ms per iteration instead of 2.6)
+    resident = ctypes.c_int64(0)
+    wgs = int(_lib.lib().tf_farneback_iteration_workgroups(H, W, ctypes.byref(of_model.params), pairs, ctypes.byref(resident)))
+    return wgs >= 0.9 * max(1, resident.value)
+
+
+def _plan_batches(n_pairs, H, W, of_model, sched):
+    """(batch sizes, parts a batch is run in): frame pairs are independent units, processed in batches per set of kernel
+    launches (tf_farneback_batch), which keeps the coarse pyramid levels busy on all CUs."""
+    if sched.batch_pairs is not None:
+        return even_batches(n_pairs, max(1, int(sched.batch_pairs))), 1
     t = _lib.torch()
     L = _lib.lib()
-    H, W = shape
+    # split_parts: a batch of B pairs runs its pyramid levels >= 2 for all pairs at once and the two finest levels in `parts`
+    # parts (tf_farneback_batch_split): full-size library scratch for B / parts pairs only, so a budget that holds the
+    # full-size scratch of 21 pairs still fills the coarse levels' launches with 42
+    parts = max(1, int(sched.split_parts if sched.split_parts is not None else 1))
+    free = t.cuda.mem_get_info()[0] + (t.cuda.memory_reserved() - t.cuda.memory_allocated())
+    budget = flow_budget(float(sched.workspace_gb if sched.workspace_gb is not None else 115) * 1e9, _lib.workspace_bytes("farneback"), free)
+    lib_per_pair = max(1, int(L.tf_farneback_workspace_bytes_batch(1, H, W, ctypes.byref(of_model.params))))
+    return budget_batches(n_pairs, H * W, lib_per_pair, budget, parts,
+                          lambda pairs, nbytes: L.tf_farneback_batch_hint(H, W, ctypes.byref(of_model.params), pairs, nbytes)), parts
+
+
+class _BatchRunner:
+    """One call's batches: the output arrays, the stages after the Farneback batch, the pooled buffers, the work of a batch."""
+
+    def __init__(self, forward, backward, normalise, of_model, vr_steps, smoothing_passes, interp, max_value, parts, B_max):
+        self.forward, self.backward, self.normalise, self.of_model = forward, backward, normalise, of_model
+        self.vr_steps, self.smoothing_passes, self.interp, self.max_value = vr_steps, smoothing_passes, interp, max_value
+        self.T, self.H, self.W = forward.shape[:3]
+        self.parts, self.B_max = parts, B_max    # (B_max shrinks when a batch has to be halved)
+
+    def buffers(self, B):
+        # The 8-bit frames and the raw (unsmoothed) flow vectors of a batch -- 2 x 1.6 GB and 2 x 9.9 GB for 42 pairs at
+        # 5424^2 -- live in buffers that stay allocated for the next batch and the next call, like the library's scratch: as
+        # fresh tensors per batch they were carved out of the caching allocator's blocks in a different way in every call, and
+        # the second call of a process paid two more device allocations (25 GB, 0.65 s: bench.py's first timed step)
+        t = _lib.torch()
+        H, W = self.H, self.W
+        n8, nraw, B_max = H * W, H * W * 2 * 4, max(self.B_max, B)
+        u8 = _lib.workspace(2 * B_max * n8, "farneback_u8")
+        prev8, next8 = u8[:B * n8].view(B, H, W), u8[B_max * n8:(B_max + B) * n8].view(B, H, W)
+        if self.smoothing_passes == 0:           # no smoothing: the batch writes straight into the stack's arrays
+            return prev8, next8, None, None
+        raw = _lib.workspace(2 * B_max * nraw, "farneback_raw")
+        f = raw[:B * nraw].view(t.float32).view(B, H, W, 2)
+        bk = raw[B_max * nraw:(B_max + B) * nraw].view(t.float32).view(B, H, W, 2)
+        return prev8, next8, f, bk
+
+    def parts_used(self, B):
+        split = self.parts > 1 and B >= 2 * self.parts and _part_fills_a_round(self.of_model, self.H, self.W, -(-B // self.parts))
+        return self.parts if split else 1
+
+    def work(self, i0, B):
+        """GENERATOR over the library work of the batch of B pairs from pair i0: yields the number of leading frame pairs that
+        are final after each part of a split batch / after the batch.  Everything that allocates or launches for the batch
+        happens inside `next()`; what the caller does with the frames (on_frames_ready) happens between two `next()` calls,
+        OUTSIDE the out-of-memory handler of _drive_batches."""
+        if B <= 0:
+            return
+        of_model = self.of_model
+        prev8, next8, f, bk = self.buffers(B)
+        for b in range(B):
+            self.normalise(i0 + b, (prev8[b], next8[b]))
+        if self.smoothing_passes == 0:
+            f, bk = self.forward[i0:i0 + B], self.backward[i0 + 1:i0 + 1 + B]
+        parts = self.parts_used(B)
+        if parts == 1 or not of_model.can_split(self.H, self.W):
+            of_model.calc_batch_dev(prev8, next8, f, bk, parts=parts)
+            self.refine_and_smooth(i0, prev8, next8, f, bk)
+            yield i0 + B
+            return
+        # SPLIT BATCH, part by part: the coarse pyramid levels for all B pairs at once (their launches are half empty with
+        # B / parts pairs), then per part the two finest levels, the refinement, the smoothing -- and the caller's callback:
+        # the frames are handed out with the granularity of a part
+        per = -(-B // parts)
+        of_model.calc_phase_dev(prev8, next8, f, bk, 1, (B, per))
+        for b0 in range(0, B, per):
+            b1 = min(B, b0 + per)
+            of_model.calc_phase_dev(prev8[b0:b1], next8[b0:b1], f[b0:b1], bk[b0:b1], 2, (B, per))
+            self.refine_and_smooth(i0 + b0, prev8[b0:b1], next8[b0:b1], f[b0:b1], bk[b0:b1])
+            yield i0 + b1
+
+    def refine_and_smooth(self, i0, prev8, next8, f, bk):
+        L = _lib.lib()
+        t = _lib.torch()
+        if self.vr_steps > 0:                    # flow.py:513-519, before the smoothing (flow.py:521-525)
+            # (all pairs of the batch per set of launches, one direction after the other -- tf_varref_batch)
+            vr_model.calc_batch_dev(prev8, next8, f)
+            vr_model.calc_batch_dev(next8, prev8, bk)
+        for b in range(prev8.shape[0] if self.smoothing_passes > 0 else 0):
+            fi, bi = f[b], bk[b]
+            for k in range(self.smoothing_passes):
+                last = k == self.smoothing_passes - 1
+                fo = self.forward[i0 + b] if last else t.empty_like(fi)
+                bo = self.backward[i0 + 1 + b] if last else t.empty_like(bi)
+                # the clip of create_flow rides on the store of the LAST pass (elementwise: same values as a pass of its
+                # own over both arrays afterwards, which cost 23 ms per 144 x 5424^2 stack)
+                _lib.check(L.tf_smooth_flow_step_clip(_lib.ptr(fi), _lib.ptr(bi), self.H, self.W, self.interp, _lib.ptr(fo), _lib.ptr(bo),
+                                                      self.max_value if last else float("inf"), _lib.stream_ptr()), "tf_smooth_flow_step")
+                fi, bi = fo, bo
+
+    def finalize_ends(self):
+        # flow.py:425-426 (mirror the end frames); max_value = inf -> no clipping.  With smoothing the interior is already
+        # clipped (refine_and_smooth): only the two end frames are left to write
+        L = _lib.lib()
+        ends_only = self.smoothing_passes > 0 or self.max_value == float("inf")
+        fn, name = (L.tf_flow_finalize_ends, "tf_flow_finalize_ends") if ends_only else (L.tf_flow_finalize, "tf_flow_finalize")
+        _lib.check(fn(_lib.ptr(self.forward), _lib.ptr(self.backward), self.T, self.H, self.W, self.max_value, _lib.stream_ptr()), name)
+
+    def release(self, half):
+        # a batch did not fit: the scratch goes back to the device and the pooled buffers are sized for `half` pairs
+        _lib.release_workspaces("farneback")
+        _lib.torch().cuda.empty_cache()
+        self.B_max = half
+
+
+def _drive_batches(batches, make_work, on_done, release):
+    """Run the batches [(first pair, pairs)] in order: `make_work(i0, B)` is a generator that yields the number of leading
+    pairs that are final, `on_done(n)` is told after every yield.  A batch that does not fit (the budget is an estimate; a
+    caching allocator's free memory can be fragmented) is halved and tried again from the first pair that is not final, and
+    so are the batches after it, after `release(half)`."""
+    oom = _lib.torch().OutOfMemoryError
+    pending = list(batches)
+    while pending:
+        i0, B = pending.pop(0)
+        work = make_work(i0, B)
+        done = i0                                # leading pairs that are final (and handed out)
+        while True:
+            # ONLY the batch's own allocations and launches sit inside the handler: an out-of-memory error raised by `on_done`
+            # (bench.py's callback allocates edge fields and flood scratch on a nearly full device) is the caller's, not "this
+            # batch's scratch did not fit" -- which used to release the workspace, recompute the batch at half size over frames
+            # already handed out and re-enter the callback with a smaller n (ADVICE r4)
+            try:
+                done_now = next(work, None)
+            except oom:
+                if B <= 1:
+                    raise
+                work.close()
+                release(B // 2)
+                pending = requeue_halved(done, i0 + B, pending, B // 2)
+                break
+            if done_now is None:
+                break
+            done = done_now
+            on_done(done)
+
+
+def _flow_of_pairs(normalise, shape, of_model, vr_steps, smoothing_passes, interp_method, on_device, sched):
+    """Forward / backward flow of shape[0] - 1 frame pairs whose 8-bit frames `normalise(i, out)` writes, under the schedule
+    `sched`: device tensors (forward, backward) and the deferred check of the launches that produce them."""
+    t = _lib.torch()
+    (T, H, W), n_pairs = shape, shape[0] - 1
+    on_batch, ends_only = sched.on_batch, smoothing_passes > 0 or sched.max_value == float("inf")
+    if on_batch is not None and not (on_device and ends_only):
+        raise ValueError("on_frames_ready needs device-resident input, the default schedule and either smoothing or no clipping")
     # the iteration kernel's chains in two parts when nothing is going to run beside the flow (no windows handed out while
     # the later frames are computed): same bits, 8 % faster alone, but it fills the CUs' LDS (csrc/farneback.hip).  A field of
     # THIS call's parameter block (select_of_model returns a fresh object per call), not a process-wide switch
-    if hasattr(of_model, "params") and hasattr(of_model.params, "chain_form"):
-        of_model.params.chain_form = _lib.FB_CHAIN_ONE_LANE if on_batch is not None else _lib.FB_CHAIN_TWO_PART
+    of_model.params.chain_form = _lib.FB_CHAIN_ONE_LANE if on_batch is not None else _lib.FB_CHAIN_TWO_PART
     forward = _lib.empty((T, H, W, 2), t.float32)
     backward = _lib.empty((T, H, W, 2), t.float32)
     # every frame is written below except the two mirrored ends, which tf_flow_finalize derives from their neighbours
     # (NaN there if the stack has a single frame and there is nothing to mirror)
     forward[T - 1].fill_(float("nan"))
     backward[0].fill_(float("nan"))
-    # Frame pairs are independent units: they are processed in batches of TF_FLOW_BATCH pairs per set of
-    # kernel launches (tf_farneback_batch), which keeps the coarse pyramid levels busy on all CUs.
-    linear = norm_name == "linear" and not normalisation_kwargs
-    # the other methods stay on the device when the caller's data was there (host containers keep the host glue byte for
-    # byte); ValueError: only the host form computes what this call asks for
-    norm_dev = False
-    if on_device and not linear:
-        try:
-            norm_params_dev(norm_name, (H, W), **normalisation_kwargs)
-            # uniform: finite stacks only (one reduction and one synchronisation per call)
-            norm_dev = norm_name != "uniform" or all(bool(t.isfinite(s).all()) for s in stacks)
-        except ValueError:
-            pass
+    sizes, parts = _plan_batches(n_pairs, H, W, of_model, sched)
+    starts = [sum(sizes[:k]) for k in range(len(sizes))]
     interp = select_interp_mode(interp_method) if smoothing_passes > 0 else 1
-    # The fused iteration kernel walks whole columns (OpenCV's running column sums cannot be split over rows,
-    # csrc/farneback.hip), so its parallelism is strips x directions x PAIRS and a launch costs a whole number of rounds
-    # of resident workgroups -- at every pyramid level.  Within the scratch budget the library picks the batch whose
-    # rounds are fullest summed over the levels (tf_farneback_batch_hint: 42 pairs at 5424^2 -- full rounds at levels 0, 1
-    # and 2 -- rather than the 54 that fit); what is left at the end goes into one batch, which never costs more rounds
-    # than splitting it.  TF_FLOW_BATCH fixes the batch size (development switch).
-    n_pairs = T - 1
-    sizes = []
-    if "TF_FLOW_BATCH" in os.environ or n_pairs <= 0 or not hasattr(of_model, "params"):
-        chunk = max(1, int(os.environ.get("TF_FLOW_BATCH", "16")))
-        n_b = max(1, -(-n_pairs // chunk))
-        edges = [round(k * n_pairs / n_b) for k in range(n_b + 1)]
-        sizes = [b - a for a, b in zip(edges[:-1], edges[1:]) if b > a]
-    else:
-        # budget: TF_FLOW_WORKSPACE_GB (default 115), and never more than 60 % of what the device has free now (the stages
-        # after the flow need room too)
-        budget = float(os.environ.get("TF_FLOW_WORKSPACE_GB", workspace_gb if workspace_gb is not None else "115")) * 1e9
-        held = _lib.workspace_bytes("farneback")           # scratch kept from the previous call: reusable as it is
-        free = t.cuda.mem_get_info()[0] + (t.cuda.memory_reserved() - t.cuda.memory_allocated())
-        budget = int(max(min(budget, held + 0.6 * free), 1))   # (_lib.workspace empties the allocator's cache if fragments are in the way)
-        # scratch of the library + the batch's 8-bit frames and raw flow vectors (this function's own buffers)
-        lib_per_pair = max(1, int(L.tf_farneback_workspace_bytes_batch(1, H, W, ctypes.byref(of_model.params))))
-        # TF_FLOW_SPLIT=<parts> (default 1): a batch of B pairs runs its pyramid levels >= 2 for all pairs at once and the two
-        # finest levels in `parts` parts (tf_farneback_batch_split): full-size library scratch for B / parts pairs only, so a
-        # budget that holds the full-size scratch of 21 pairs still fills the coarse levels' launches with 42
-        split_parts = max(1, int(os.environ.get("TF_FLOW_SPLIT", split_parts if split_parts is not None else "1")))
-        per_pair = lib_per_pair // split_parts + H * W * (2 + 16)
-        cap = max(1, budget // per_pair)
-        # the library's hint counts ITS scratch only: hand it the share of the budget that is the library's, so that both
-        # sides price a pair the same way (ADVICE r3: the hint could return a batch ~25 % over the budget, which then went
-        # through the halving path -- release, empty_cache, half batches for the rest of the call)
-        lib_budget = max(1, int(budget * ((lib_per_pair // split_parts) / per_pair)))
-        left = n_pairs
-        while left > 0:
-            if left <= cap:
-                B = left
-            else:       # the hint sizes the FULL-resolution launches: B / parts pairs of them
-                b_fine = max(1, int(L.tf_farneback_batch_hint(H, W, ctypes.byref(of_model.params), -(-left // split_parts), lib_budget)))
-                B = min(cap, left, b_fine * split_parts)
-            sizes.append(B)
-            left -= B
-    if os.environ.get("TF_FLOW_DEBUG"):
-        print("flow: %d pairs in batches %s" % (n_pairs, sizes), flush=True)
-    n_batches = len(sizes)
-    starts = [0]
-    for B in sizes:
-        starts.append(starts[-1] + B)
-    # TF_FLOW_OVERLAP=1: a second stream for the per-pair stages after the Farneback batch.  Off by default: measured on
-    # config F (144 x 5424^2) it gains 1.5 % (5033 vs 5110 ms per step) -- every kernel involved fills the GPU by itself
-    # -- and the HIP-event kernel timing of bench.py cannot attribute time to kernels that run side by side.
-    main = t.cuda.current_stream()
-    side = None
-    if n_batches > 1 and (vr_steps > 0 or smoothing_passes > 0) and os.environ.get("TF_FLOW_OVERLAP", "0") == "1":
-        side = _side_stream(main)
-        forward.record_stream(side)
-        backward.record_stream(side)
+    runner = _BatchRunner(forward, backward, normalise, of_model, vr_steps, smoothing_passes, interp, sched.max_value, parts, max(sizes, default=0))
 
-    # The 8-bit frames and the raw (unsmoothed) flow vectors of a batch -- 2 x 1.6 GB and 2 x 9.9 GB for 42 pairs at 5424^2
-    # -- live in buffers that stay allocated for the next batch and the next call, like the library's scratch: as fresh
-    # tensors per batch they were carved out of the caching allocator's blocks in a different way in every call, and the
-    # second call of a process paid two more device allocations (25 GB, 0.65 s: bench.py's first timed step).  With the
-    # second stream (TF_FLOW_OVERLAP) two batches are in flight and each needs its own: fresh tensors then.
-    pool = {"B_max": max(sizes) if sizes else 0}             # (shrinks when a batch has to be halved)
-    pooled = side is None and pool["B_max"] > 0
-
-    def batch_buffers(B):
-        n8, nraw, B_max = H * W, H * W * 2 * 4, max(pool["B_max"], B)
-        if pooled:
-            u8 = _lib.workspace(2 * B_max * n8, "farneback_u8")
-            prev8, next8 = u8[:B * n8].view(B, H, W), u8[B_max * n8:(B_max + B) * n8].view(B, H, W)
-        else:
-            prev8, next8 = _lib.empty((B, H, W), t.uint8), _lib.empty((B, H, W), t.uint8)
-        if smoothing_passes == 0:
-            return prev8, next8, None, None
-        if pooled:
-            raw = _lib.workspace(2 * B_max * nraw, "farneback_raw")
-            f = raw[:B * nraw].view(t.float32).view(B, H, W, 2)
-            bk = raw[B_max * nraw:(B_max + B) * nraw].view(t.float32).view(B, H, W, 2)
-        else:
-            f, bk = _lib.empty((B, H, W, 2), t.float32), _lib.empty((B, H, W, 2), t.float32)
-        return prev8, next8, f, bk
-
-    def split_parts_used(B):
-        parts = max(1, int(os.environ.get("TF_FLOW_SPLIT", split_parts if split_parts is not None else "1")))
-        if parts == 1 or not hasattr(of_model, "params") or "TF_FLOW_BATCH" in os.environ or B < 2 * parts:
-            return 1
-        # a launch of the iteration kernel costs whole rounds of resident workgroups: parts that no longer fill a round at
-        # the full resolution each cost what the whole batch costs (config C, 23 pairs of 1500 x 2500 = one round:
-        # two parts took 2 x 2.3 ms per iteration instead of 2.6)
-        if os.environ.get("TF_FLOW_SPLIT_FORCE"):            # (tests: split whatever the size)
-            return parts
-        resident = ctypes.c_int64(0)
-        wgs = int(L.tf_farneback_iteration_workgroups(H, W, ctypes.byref(of_model.params), -(-B // parts), ctypes.byref(resident)))
-        return parts if wgs >= 0.9 * max(1, resident.value) else 1
-
-    def run_batch(i0, B):
-        """GENERATOR over the library work of one batch: yields the number of leading frame pairs that are final after each
-        part of a split batch / after the batch.  Everything that allocates or launches for the batch happens inside
-        `next()`; what the caller does with the frames (on_frames_ready) happens between two `next()` calls, OUTSIDE the
-        out-of-memory handler of the loop below."""
-        if B <= 0:
-            return
-        prev8, next8, f, bk = batch_buffers(B)
-        for b in range(B):
-            fa, fb = frame_pairs(i0 + b)
-            if linear:
-                to_8bit_pair_dev(fa, fb, out=(prev8[b], next8[b]))
-            elif norm_dev:
-                normalise_pair_dev(norm_name, fa, fb, out=(prev8[b], next8[b]), check_finite=False, **normalisation_kwargs)
-            else:   # other normalisations are host glue (not on the production path)
-                pair = np.stack([fa.cpu().numpy(), fb.cpu().numpy()], 0)
-                p8 = to_8bit(norm_method(pair, **normalisation_kwargs), 0, 1)
-                prev8[b].copy_(_lib.to_dev(p8[0]))
-                next8[b].copy_(_lib.to_dev(p8[1]))
-        if smoothing_passes == 0:
-            f, bk = forward[i0:i0 + B], backward[i0 + 1:i0 + 1 + B]
-        parts = split_parts_used(B)
-        by_part = parts > 1 and side is None and of_model.can_split(H, W)
-        if by_part:
-            # SPLIT BATCH, part by part: the coarse pyramid levels for all B pairs at once (their launches are half empty with
-            # B / parts pairs), then per part the two finest levels, the refinement, the smoothing -- and the caller's callback:
-            # the frames are handed out with the granularity of a part
-            per = -(-B // parts)
-            of_model.calc_phase_dev(prev8, next8, f, bk, 1, (B, per))
-        else:
-            of_model.calc_batch_dev(prev8, next8, f, bk, parts=parts)
-        if vr_steps == 0 and smoothing_passes == 0 and not by_part:
-            yield i0 + B
-            return
-
-        def refine_and_smooth(i0=i0, B=B, prev8=prev8, next8=next8, f=f, bk=bk):
-            if vr_steps > 0:                     # flow.py:513-519, before the smoothing (flow.py:521-525)
-                # (round 6: all pairs of the batch per set of launches, one direction after the other -- tf_varref_batch)
-                vr_model.calc_batch_dev(prev8, next8, f)
-                vr_model.calc_batch_dev(next8, prev8, bk)
-            for b in range(B if smoothing_passes > 0 else 0):
-                fi, bi = f[b], bk[b]
-                for k in range(smoothing_passes):
-                    last = k == smoothing_passes - 1
-                    fo = forward[i0 + b] if last else t.empty_like(fi)
-                    bo = backward[i0 + 1 + b] if last else t.empty_like(bi)
-                    # the clip of create_flow rides on the store of the LAST pass (elementwise: same values as a pass of its
-                    # own over both arrays afterwards, which cost 23 ms per 144 x 5424^2 stack)
-                    _lib.check(L.tf_smooth_flow_step_clip(_lib.ptr(fi), _lib.ptr(bi), H, W, interp, _lib.ptr(fo), _lib.ptr(bo),
-                                                          max_value if last else float("inf"), _lib.stream_ptr()), "tf_smooth_flow_step")
-                    fi, bi = fo, bo
-
-        if by_part:
-            for b0 in range(0, B, per):
-                b1 = min(B, b0 + per)
-                of_model.calc_phase_dev(prev8[b0:b1], next8[b0:b1], f[b0:b1], bk[b0:b1], 2, (B, per))
-                if vr_steps > 0 or smoothing_passes > 0:
-                    refine_and_smooth(i0 + b0, b1 - b0, prev8[b0:b1], next8[b0:b1], f[b0:b1], bk[b0:b1])
-                yield i0 + b1
-            return
-        elif side is None:
-            refine_and_smooth()
-        else:
-            # The refinement / smoothing of this batch runs on a second stream while the main stream goes on with the
-            # NEXT batch's pyramids and iterations: the iteration kernel leaves CUs idle (coarse levels, the last round of
-            # a launch), the refinement kernels fill them.  Same kernels on the same data -- the results do not change.
-            ready = main.record_event()
-            for x in (prev8, next8, f, bk):
-                x.record_stream(side)            # allocated on `main`, last used on `side`
-            with t.cuda.stream(side):
-                side.wait_event(ready)
-                refine_and_smooth()
-        yield i0 + B
-    # a batch that does not fit (the budget above is an estimate; a caching allocator's free memory can be fragmented) is
-    # halved and tried again, and so are the batches after it
-    def finalize_ends():
-        # flow.py:425-426 (mirror the end frames); max_value = inf -> no clipping.  With smoothing the interior is already
-        # clipped (run_batch): only the two end frames are left to write
-        if smoothing_passes > 0 or max_value == float("inf"):
-            _lib.check(L.tf_flow_finalize_ends(_lib.ptr(forward), _lib.ptr(backward), T, H, W, max_value, _lib.stream_ptr()),
-                       "tf_flow_finalize_ends")
-        else:
-            _lib.check(L.tf_flow_finalize(_lib.ptr(forward), _lib.ptr(backward), T, H, W, max_value, _lib.stream_ptr()),
-                       "tf_flow_finalize")
-
-    if on_batch is not None and (side is not None or not on_device or not (smoothing_passes > 0 or max_value == float("inf"))):
-        raise ValueError("on_frames_ready needs device-resident input, the default single-stream schedule and either smoothing or no clipping")
-    pending = [(a_, b_ - a_) for a_, b_ in zip(starts[:-1], starts[1:])]
-    while pending:
-        i0, B = pending.pop(0)
-        work = run_batch(i0, B)
-        done = i0                                             # leading pairs that are final (and, with on_batch, handed out)
-        while True:
-            # ONLY the batch's own allocations and launches sit inside the handler: an out-of-memory error raised by the
-            # caller's callback (bench.py's allocates edge fields and flood scratch on a nearly full device) is the caller's,
-            # it must not be taken for "this batch's scratch did not fit" -- which used to release the workspace, recompute
-            # the batch at half size over frames already handed out and re-enter the callback with a smaller n (ADVICE r4)
-            try:
-                done_now = next(work, None)
-            except t.OutOfMemoryError:
-                if os.environ.get("TF_FLOW_DEBUG"):
-                    print("flow: batch of %d pairs does not fit (free %.1f GB, cached %.1f GB): halving" % (
-                        B, t.cuda.mem_get_info()[0] / 1e9, (t.cuda.memory_reserved() - t.cuda.memory_allocated()) / 1e9), flush=True)
-                if B <= 1:
-                    raise
-                work.close()
-                _lib.release_workspaces("farneback")
-                t.cuda.empty_cache()
-                half = B // 2
-                pool["B_max"] = half
-                # never re-run pairs whose frames have been handed out: the parts of this batch that are done stay done, the
-                # rest of it (from `done` on) and the batches after it are cut to the new size
-                todo, pending = [(done, i0 + B - done)] + pending, []
-                for j0, Bj in todo:
-                    while Bj > half:
-                        pending.append((j0, half))
-                        j0, Bj = j0 + half, Bj - half
-                    if Bj > 0:
-                        pending.append((j0, Bj))
-                break
-            if done_now is None:
-                break
-            done = done_now
-            if on_batch is not None and done < n_pairs:
-                # the first done + 1 frames are final but for the stack's own first frame, whose backward vectors are the
-                # mirror of its forward ones: written now (and, with the still unknown other end, once more at the end)
-                finalize_ends()
-                on_batch(forward, backward, done, n_pairs)
-    if side is not None:
-        main.wait_stream(side)
-    if n_batches > 0 and sizes and max(sizes) > 16:
+    def handed_out(done):
+        if on_batch is not None and done < n_pairs:
+            # the first done + 1 frames are final but for the stack's own first frame, whose backward vectors are the
+            # mirror of its forward ones: written now (and, with the still unknown other end, once more at the end)
+            runner.finalize_ends()
+            on_batch(forward, backward, done, n_pairs)
+    _drive_batches(list(zip(starts, sizes)), runner.work, handed_out, runner.release)
+    if max(sizes, default=0) > 16:
         # A large batch's scratch (tens of GB) stays allocated for the next call (carving one block of that size out of a
         # caching allocator's free fragments fails more often than not: measured, bench.py fell back to half batches from
         # its second step on) -- unless the device is nearly full: then the stages after the flow (Sobel, watershed, the
@@ -704,51 +629,47 @@ def _calculate_flow_impl(frame_pairs, T, shape, of_model, vr_steps, smoothing_pa
         free_now, total = t.cuda.mem_get_info()
         if free_now + (t.cuda.memory_reserved() - t.cuda.memory_allocated()) < 0.2 * total:
             _lib.release_workspaces("farneback")
-    finalize_ends()
+    runner.finalize_ends()
     # A stack whose flow holds NaN rows (a starved chain of the iteration kernel) must not be returned as if nothing had
-    # happened.  Host output: the download below synchronises anyway -- check behind it.  Device output: the caller's pipeline is
-    # asynchronous; the check is DEFERRED to an event recorded here (`deferred`): the Flow object polls it at every use and
-    # create_flow's callers with a synchronisation of their own (detect_stack_windows) wait for it there
-    deferred = of_model.deferred_check("create_flow / calculate_flow") if hasattr(of_model, "deferred_check") else None
+    # happened.  The caller's pipeline may be asynchronous: the check is DEFERRED to an event recorded here -- calculate_flow
+    # waits for it before it returns, create_flow's Flow object polls it at every use and callers with a synchronisation of
+    # their own (detect_stack_windows) wait for it there
+    check = of_model.deferred_check("create_flow / calculate_flow")
     if on_batch is not None:
         on_batch(forward, backward, n_pairs, n_pairs)
-    if on_device:
-        if check_out is not None and deferred is not None:
-            check_out.append(deferred)
-        elif deferred is not None:
-            deferred(block=True)                  # (a caller that cannot take the deferred check gets the synchronous one)
-        return forward, backward
-    out = _lib.to_host(forward), _lib.to_host(backward)
-    if deferred is not None:
-        deferred(block=True)
-    return out
+    return forward, backward, check
 
 
-def calculate_flow(data, model: str = "Farneback", vr_steps: int = 0, smoothing_passes: int = 0,
-                   interp_method: str = "linear", normalisation_method: str = "linear", **normalisation_kwargs):
-    """Forward / backward flow for every consecutive frame pair of `data` (reference: flow.py:362-428).
-    forward[i] = flow i -> i+1, backward[i+1] = flow i+1 -> i; the end frames are mirrored."""
-    max_value = normalisation_kwargs.pop("_max_value", float("inf"))
-    on_batch = normalisation_kwargs.pop("_on_batch", None)
-    device_out = normalisation_kwargs.pop("_device_out", False)
-    workspace_gb = normalisation_kwargs.pop("_workspace_gb", None)
-    split_parts = normalisation_kwargs.pop("_split_parts", None)
-    check_out = normalisation_kwargs.pop("_check_out", None)
+def _checked(forward, backward, check, on_device):
+    """what calculate_flow returns: the check waited for -- behind the download, which synchronises anyway, for host input"""
+    if not on_device:
+        forward, backward = _lib.to_host(forward), _lib.to_host(backward)
+    check(block=True)
+    return forward, backward
+
+
+def _calculate_flow(data, model, vr_steps, smoothing_passes, interp_method, normalisation_method, normalisation_kwargs, sched):
+    """calculate_flow under the schedule `sched`, on the device: (forward, backward, deferred check)"""
     of_model = select_of_model(model)
     norm_method = select_normalisation_method(normalisation_method)
     t = _lib.torch()
     data = _unwrap_device_field(data)
     if _is_dataarray(data):
         data = data.compute().data if hasattr(data, "compute") else data.to_numpy()
-    on_device = isinstance(data, t.Tensor) or device_out
+    on_device = isinstance(data, t.Tensor) or sched.device_out
     d = _lib.to_dev(data, t.float32, share=True)          # (only read: the same array usually goes to detect_cores next)
     if d.dim() != 3:
         raise ValueError("data must have three dimensions (t, y, x)")
-    T = d.shape[0]
-    return _calculate_flow_impl(lambda i: (d[i], d[i + 1]), T, tuple(d.shape[1:]), of_model, vr_steps,
-                                smoothing_passes, interp_method, normalisation_method, norm_method,
-                                normalisation_kwargs, on_device, max_value, on_batch, workspace_gb, split_parts, check_out,
-                                stacks=(d,))
+    normalise = _pair_normaliser(lambda i: (d[i], d[i + 1]), (d,), on_device, normalisation_method, norm_method, normalisation_kwargs)
+    return _flow_of_pairs(normalise, tuple(d.shape), of_model, vr_steps, smoothing_passes, interp_method, on_device, sched)
+
+
+def calculate_flow(data, model: str = "Farneback", vr_steps: int = 0, smoothing_passes: int = 0,
+                   interp_method: str = "linear", normalisation_method: str = "linear", **normalisation_kwargs):
+    """Forward / backward flow for every consecutive frame pair of `data` (reference: flow.py:362-428).
+    forward[i] = flow i -> i+1, backward[i+1] = flow i+1 -> i; the end frames are mirrored."""
+    flows = _calculate_flow(data, model, vr_steps, smoothing_passes, interp_method, normalisation_method, normalisation_kwargs, _Schedule())
+    return _checked(*flows, on_device=isinstance(_unwrap_device_field(data), _lib.torch().Tensor))
 
 
 def calculate_flow_2(a, b, model: str = "Farneback", vr_steps: int = 0, smoothing_passes: int = 0,
@@ -764,10 +685,9 @@ def calculate_flow_2(a, b, model: str = "Farneback", vr_steps: int = 0, smoothin
         b = b.compute().data if hasattr(b, "compute") else b.to_numpy()
     on_device = isinstance(a, t.Tensor)
     da, db = _lib.to_dev(a, t.float32), _lib.to_dev(b, t.float32)
-    T = da.shape[0]
-    return _calculate_flow_impl(lambda i: (da[i], db[i]), T, tuple(da.shape[1:]), of_model, vr_steps,
-                                smoothing_passes, "linear", normalisation_method, norm_method,
-                                normalisation_kwargs, on_device, stacks=(da, db))
+    normalise = _pair_normaliser(lambda i: (da[i], db[i]), (da, db), on_device, normalisation_method, norm_method, normalisation_kwargs)
+    return _checked(*_flow_of_pairs(normalise, tuple(da.shape), of_model, vr_steps, smoothing_passes, "linear", on_device, _Schedule()),
+                    on_device=on_device)
 
 
 def calculate_flow_frame(prev_frame, next_frame, of_model, vr_steps: int = 0, smoothing_steps: int = 0,
