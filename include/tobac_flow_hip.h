@@ -606,6 +606,29 @@ int tf_relabel_merge(const int32_t *own, int64_t T, int64_t hw, const int32_t *l
                      const int32_t *prev, int64_t T_prev, const int32_t *prev_frame, const int32_t *lut_prev, int n_prev,
                      const int32_t *next, int64_t T_next, const int32_t *next_frame, const int32_t *lut_next, int n_next,
                      int32_t *out, uint64_t *status, void *stream);
+/* tf_field_stats (version 112): tobac_flow/dataset.py:19-148 -- get_bulk_stats, get_spatial_stats, get_temporal_stats of a
+ *   contiguous (T, H, W) field of dtype TF_F32 or TF_F64: per slice the number of non-NaN values and their np.nanmean,
+ *   np.nanstd (ddof 0), np.nanmedian, np.nanmax, np.nanmin.  The slices, S of them:
+ *     TF_FIELD_ALL    everything, S = 1 (any shape, given as T H W values; the median is np.median's: NaN if any value is NaN)
+ *     TF_FIELD_FRAME  the H W values of every frame, S = T (all frames in the same launches)
+ *     TF_FIELD_TIME   the T values of every pixel, S = H W
+ *   count: int64[S].  stats: five planes of S doubles -- mean, std, median, max, min, in the reference's order; a slice
+ *   without a non-NaN value gives count 0 and NaN five times.  Count, median, max and min are exact (the median is the mean
+ *   of the two middle values computed in the field's dtype, as NumPy computes it, then widened); mean and std are float64
+ *   sums combined in an order fixed by the shape (no float atomics: identical bits from run to run), std from a second
+ *   sweep of (x - mean)^2.  Infinities follow IEEE arithmetic.  64-bit indices and counts.  TF_FIELD_TIME reads the
+ *   volume once while T <= TF_FIELD_STATS_LDS_FRAMES_F32 / _F64 and 19 (float32) or 35 (float64) times beyond; the other
+ *   two read it 5 (float32) or 8 (float64) times.  The workspace is used by TF_FIELD_ALL and TF_FIELD_FRAME only.
+ *   TF_EINVAL before any launch: null pointers, another dtype, an unknown geometry, an extent < 1, more than 2^40 values,
+ *   more than 65535 frames for TF_FIELD_FRAME; TF_ENOMEM: ws_bytes below tf_field_stats_workspace_bytes (0 for bad arguments). */
+#define TF_FIELD_ALL 0
+#define TF_FIELD_FRAME 1
+#define TF_FIELD_TIME 2
+#define TF_FIELD_STATS_LDS_FRAMES_F32 64
+#define TF_FIELD_STATS_LDS_FRAMES_F64 32
+size_t tf_field_stats_workspace_bytes(int dtype, int64_t T, int64_t H, int64_t W, int over);
+int tf_field_stats(const void *field, int dtype, int64_t T, int64_t H, int64_t W, int over, int64_t *count, double *stats,
+                   void *ws, size_t ws_bytes, void *stream);
 /* The elementwise glue of detect_anvils' seeds (tobac_flow/detection.py:547-561, 590-617) in two passes:
  * tf_field_masks: ge1 = field >= 1, le0_or_nan = (field <= 0) | isnan(field), isnan_out = isnan(field) as 0 / 1 bytes;
  * tf_merge_seeds: seeds = (bg | isnan) ? -1 : comp. */

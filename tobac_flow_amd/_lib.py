@@ -172,6 +172,8 @@ _PROTOS = {
     "tf_apply_lut_keep_nonpositive": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int, _P, _P]),
     "tf_relabel_merge": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _c.c_int64, _P, _P, _c.c_int,
                                     _P, _c.c_int64, _P, _P, _c.c_int, _P, _P, _P]),
+    "tf_field_stats_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int]),
+    "tf_field_stats": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_size_t, _P]),
     "tf_field_masks": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P]),
     "tf_merge_seeds": (_c.c_int, [_P, _P, _P, _c.c_int64, _P, _P]),
     "tf_label_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64]),

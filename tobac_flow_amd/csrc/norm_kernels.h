@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/tobac_flow_hip.h"
+#include "radix_select.h"
 
 #define NM_LANES 256                   // lanes per workgroup of every kernel here
 #define NM_MAX_PARTIALS 1024           // workgroups of a reduction = partials the finish stage combines
@@ -264,28 +265,21 @@ __host__ __device__ inline void nm_col_finish_lane(int64_t lane, int64_t H, int6
 
 // ---- uniform: exact order statistics by a multi-rank radix select, then a digitising map -------------------------------
 // np.quantile(pair, np.linspace(0, 1, Q + 1)) (method "linear") reads two order statistics per edge: R = 2 (Q + 1) ranks.
-// They are found on the order-preserving 32-bit keys in three passes of 11 + 11 + 10 bits.  Every rank carries the key
+// They are found on the order-preserving 32-bit keys in three passes of 11 + 11 + 10 bits (the keys, the digit plan, the
+// histogram scan and the rank look-up are radix_select.h's, shared with field_stats.hip).  Every rank carries the key
 // prefix found so far and its residual rank among the keys with that prefix; the distinct prefixes of a pass are its
 // "active" slots (sorted, at most R), each with a histogram of the pass's digit.  A workgroup counts the first
 // NM_LDS_SLOTS slots in LDS and adds them to the global counters at its end -- one slot in the first pass, a handful in
 // the second for a field whose values share their leading bits -- and the others, which few keys reach, directly.
 #define NM_MAX_RANKS (2 * (TF_NORM_MAX_QUANTILES + 1))
-#define NM_BINS 2048
+#define NM_BINS RS_BINS
 #define NM_LDS_SLOTS 4
 #define NM_RANKS_PER_LANE ((NM_MAX_RANKS + NM_LANES - 1) / NM_LANES)
 
-__host__ __device__ inline unsigned nm_key(float v)
-{
-    union { float f; unsigned u; } c; c.f = v;
-    return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
-}
-__host__ __device__ inline float nm_unkey(unsigned k)
-{
-    union { float f; unsigned u; } c; c.u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return c.f;
-}
-__host__ __device__ inline int nm_prefix_shift(int pass) { return pass == 0 ? 32 : pass == 1 ? 21 : 10; }
-__host__ __device__ inline int nm_digit_bits(int pass) { return pass == 2 ? 10 : 11; }
+static_assert(NM_LANES == RS_LANES, "the shared histogram scan is written for this workgroup");
+#define NM_KEY_BITS 32
+__host__ __device__ inline int nm_prefix_shift(int pass) { return rs_prefix_shift(NM_KEY_BITS, pass); }
+__host__ __device__ inline int nm_digit_bits(int pass) { return rs_digit_bits(NM_KEY_BITS, pass); }
 
 struct NmSelect {
     unsigned *resid, *prefix, *active;      // per rank: residual rank, key prefix; the sorted distinct prefixes
@@ -317,7 +311,7 @@ __host__ __device__ inline void nm_hist_lane(const float *__restrict__ f0, const
     const int pshift = nm_prefix_shift(pass), dshift = pshift - nm_digit_bits(pass);
     const unsigned dmask = (1u << nm_digit_bits(pass)) - 1u;
     for (int64_t i = first; i < 2 * n; i += stride) {
-        const unsigned key = nm_key(i < n ? f0[i] : f1[i - n]);
+        const unsigned key = rs_key(i < n ? f0[i] : f1[i - n]);
         const unsigned prefix = (unsigned)((unsigned long long)key >> pshift), digit = (key >> dshift) & dmask;
         int lo = 0, hi = nactive;
         while (lo < hi) { const int mid = (lo + hi) >> 1; if (active[mid] < prefix) lo = mid + 1; else hi = mid; }
@@ -333,23 +327,6 @@ __host__ __device__ inline void nm_hist_flush(int tid, int nactive, const unsign
     for (int i = tid; i < m; i += NM_LANES) if (lds_hist[i]) atomicAdd(&hist[i], lds_hist[i]);
 }
 
-// exclusive running sum of one slot's NM_BINS counters, in place: lane t owns bins 8 t .. 8 t + 7 (two phases, `part` in LDS)
-__host__ __device__ inline void nm_scan_sum(int tid, const unsigned *h, unsigned *part)
-{
-    unsigned s = 0;
-    for (int i = 0; i < NM_BINS / NM_LANES; i++) s += h[tid * (NM_BINS / NM_LANES) + i];
-    part[tid] = s;
-}
-__host__ __device__ inline void nm_scan_write(int tid, unsigned *h, const unsigned *part)
-{
-    unsigned run = 0;
-    for (int t = 0; t < tid; t++) run += part[t];
-    for (int i = 0; i < NM_BINS / NM_LANES; i++) {
-        unsigned *p = h + tid * (NM_BINS / NM_LANES) + i;
-        const unsigned c = *p; *p = run; run += c;
-    }
-}
-
 // Resolve, one workgroup, lane t owns ranks NM_RANKS_PER_LANE t ...: (1) the digit of each rank from its slot's running
 // sums -- the last bin that starts at or below the residual rank -- into newp (LDS); (2) the number of ranks in the lane's
 // block whose prefix differs from the previous rank's (the ranks ascend, so equal prefixes are neighbours) into cnt (LDS);
@@ -360,9 +337,7 @@ __host__ __device__ inline void nm_resolve_digit(int tid, int R, int pass, NmSel
     for (int j = tid * NM_RANKS_PER_LANE; j < (tid + 1) * NM_RANKS_PER_LANE && j < R; j++) {
         const unsigned *cum = s.hist + (size_t)s.slot[j] * NM_BINS;
         const unsigned r = s.resid[j];
-        int lo = 0, hi = bins;                                   // first bin whose start exceeds r
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (cum[mid] <= r) lo = mid + 1; else hi = mid; }
-        const int b = lo - 1;                                    // >= 0: cum[0] == 0
+        const int b = rs_rank_bin(cum, bins, r);
         s.resid[j] = r - cum[b];
         newp[j] = (pass == 0 ? 0u : s.prefix[j] << nm_digit_bits(pass)) | (unsigned)b;
     }
@@ -390,7 +365,7 @@ __host__ __device__ inline void nm_resolve_slots(int tid, int R, NmSelect s, con
 __host__ __device__ inline void nm_edge_lane(int k, int Q, NmSelect s, const unsigned *keys)
 {
     if (k > Q) return;
-    const float a = nm_unkey(keys[2 * k]), b = nm_unkey(keys[2 * k + 1]);
+    const float a = rs_unkey(keys[2 * k]), b = rs_unkey(keys[2 * k + 1]);
     const double t = s.gamma[k], diff = (double)(b - a);
     double e = t >= 0.5 ? (double)b - diff * (1 - t) : (double)a + diff * t;
     if (k == Q) e = e + 1;

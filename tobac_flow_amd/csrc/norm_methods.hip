@@ -127,9 +127,9 @@ k_nm_scan(NmSelect sel)
     __shared__ unsigned part[NM_LANES];
     if ((int)blockIdx.x >= *sel.nactive) return;
     unsigned *h = sel.hist + (size_t)blockIdx.x * NM_BINS;
-    nm_scan_sum(threadIdx.x, h, part);
+    rs_scan_sum(threadIdx.x, h, part);
     __syncthreads();
-    nm_scan_write(threadIdx.x, h, part);
+    rs_scan_write(threadIdx.x, h, part);
 }
 
 __global__ void __launch_bounds__(NM_LANES)

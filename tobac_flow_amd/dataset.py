@@ -11,6 +11,9 @@ What the reference does per label in Python (scipy.ndimage.labeled_comprehension
 bincount or a mode per label) is ONE pair-count pass over the two volumes on the GPU (tf_pair_counts, label.hip) and a
 small host reduction over the distinct pairs; the per-step relabelling is tf_slice_labels; LUT applications are
 tf_apply_lut.  Ties are broken as the reference's tools do (np.argmax / scipy.stats.mode: the smallest label wins).
+
+The per-field summaries that go into the product beside the labels -- get_bulk_stats, get_spatial_stats,
+get_temporal_stats (dataset.py:19-148) -- are here too: a device field is reduced in HBM by tf_field_stats.
 """
 import numpy as np
 
@@ -376,6 +379,63 @@ def calculate_label_properties(dataset):
     add_steps("thin_anvil", "loc")
 
 
-__all__ = ("LabelDataset", "add_step_labels", "add_label_coords", "find_max_overlap", "link_cores_and_anvils",
+_FIELD_STATS = ("mean", "std", "median", "max", "min")
+
+
+def _host_field_stats(a, over):
+    """the five statistics as the reference computes them on the host: get_bulk_stats' own NumPy calls (dataset.py:19-60);
+    xarray's float defaults skipna=True, ddof=0 -- NumPy's nan-functions over the named axes -- for the other two"""
+    if over == "all":
+        return np.nanmean(a), np.nanstd(a), np.median(a), np.nanmax(a), np.nanmin(a)
+    if a.ndim != 3:
+        raise ValueError(f"the field must be a (t, y, x) volume, not {a.shape}")
+    axis = (1, 2) if over == "frame" else 0
+    return tuple(f(a, axis) for f in (np.nanmean, np.nanstd, np.nanmedian, np.nanmax, np.nanmin))
+
+
+def _field_stats(da, ds, name, over, infix, dims):
+    from tobac_flow_amd import ndimage_dev
+    if isinstance(da, str):
+        name = da if name is None else name
+        da = ds[da]
+    if ds is not None and name is None:
+        raise ValueError("an array passed with ds needs name= (there is no DataArray.name here)")
+    if _lib.is_tensor(getattr(da, "data", None)):                 # a detection.DeviceField
+        da = da.data
+    if _lib.is_tensor(da):
+        got = ndimage_dev.field_stats(da, over)
+        out = tuple(got[k].to(da.dtype) for k in _FIELD_STATS)
+    else:
+        a = np.asarray(da)
+        out = tuple(np.asarray(v).astype(a.dtype) for v in _host_field_stats(a, over))
+    if ds is not None:
+        for k, v in zip(_FIELD_STATS, out):
+            ds.add(f"{name}_{infix}{k}", v, dims)
+    return out
+
+
+def get_bulk_stats(da, ds=None, name=None):
+    """(mean, std, median, max, min) of a field over everything, each of shape () and of the field's dtype: np.nanmean,
+    np.nanstd, np.median (NaN if any value is NaN), np.nanmax, np.nanmin (reference: dataset.py:19-60).  `da`: a NumPy
+    array, a device tensor, a detection.DeviceField, or the name of a variable of `ds`; with `ds` (a LabelDataset) the five
+    are also added as `{name}_mean`, `_std`, `_median`, `_max`, `_min` (an array then needs name=).  NumPy in, NumPy out
+    through the reference's own calls; a float32 / float64 tensor of any shape stays on the GPU
+    (ndimage_dev.field_stats: count, median, max and min exact, mean and std float64 sums rounded to the field's dtype)."""
+    return _field_stats(da, ds, name, "all", "", ())
+
+
+def get_spatial_stats(da, ds=None, name=None):
+    """The same five per frame of a (t, y, x) field, NaN values ignored (nanmedian), each of shape (t,):
+    `{name}_spatial_mean`, ... on ("t",) (reference: dataset.py:63-104).  A frame without a value gives NaN."""
+    return _field_stats(da, ds, name, "frame", "spatial_", ("t",))
+
+
+def get_temporal_stats(da, ds=None, name=None):
+    """The same five per pixel along t of a (t, y, x) field, NaN values ignored, each of shape (y, x):
+    `{name}_temporal_mean`, ... on ("y", "x") (reference: dataset.py:107-148).  A pixel without a value gives NaN."""
+    return _field_stats(da, ds, name, "time", "temporal_", ("y", "x"))
+
+
+__all__ = ("LabelDataset", "get_bulk_stats", "get_spatial_stats", "get_temporal_stats", "add_step_labels", "add_label_coords", "find_max_overlap", "link_cores_and_anvils",
            "link_step_labels", "find_edge_labels", "flag_edge_labels", "flag_nan_adjacent_labels",
            "calculate_label_properties")

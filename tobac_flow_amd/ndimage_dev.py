@@ -675,3 +675,58 @@ def label_order(labels, field, ids):
     held = (ids > _INT32_MIN) & (ids <= _INT32_MAX)
     got = mid[t.from_numpy(np.where(held, ids - lo, 0)).to(mid.device)]
     return t.where(t.from_numpy(held).to(mid.device)[:, None], got, out)
+
+
+# ---- field statistics (tf_field_stats) ---------------------------------------------------------------------------------
+class _FramesByDtype(dict):
+    """read-only {dtype name: frames}; looked up by a torch dtype, a NumPy dtype or a name"""
+
+    def __getitem__(self, dtype):
+        return dict.__getitem__(self, str(getattr(dtype, "name", dtype)).replace("torch.", ""))
+
+    def _read_only(self, *args, **kwargs):
+        raise TypeError("FIELD_STATS_LDS_FRAMES is a constant")
+
+    __setitem__ = __delitem__ = clear = pop = popitem = setdefault = update = _read_only
+
+
+# the largest T of which tf_field_stats' per-pixel form keeps a workgroup's tile in LDS and reads the volume once
+# (TF_FIELD_STATS_LDS_FRAMES_F32 / _F64 of include/tobac_flow_hip.h)
+FIELD_STATS_LDS_FRAMES = _FramesByDtype(float32=64, float64=32)
+FIELD_STATS_OVER = {"all": 0, "frame": 1, "time": 2}
+
+
+def field_stats(x, over="all"):
+    """tf_field_stats: the statistics of get_bulk_stats / get_spatial_stats / get_temporal_stats (dataset.py) of a float32
+    or float64 device tensor, NaN values ignored, as a dict of device tensors: `count` (int64, the non-NaN values of each
+    slice) and `mean`, `std` (ddof 0), `median`, `max`, `min` (float64).  over="all": one slice, results of shape (), any
+    shape of `x`, and the median is np.median's (NaN if any value is NaN); "frame": (t, y, x) -> (t,); "time": (t, y, x) ->
+    (y, x).  Count, median, max and min are exact -- the median is computed in the dtype of `x` and widened --; mean and std
+    are float64 sums with identical bits from run to run.  A slice without a non-NaN value gives NaN five times.  Any view
+    is made contiguous first.  An empty tensor is a ValueError, another dtype a TypeError."""
+    t = _lib.torch()
+    if over not in FIELD_STATS_OVER:
+        raise ValueError(f"over must be one of {tuple(FIELD_STATS_OVER)}, not {over!r}")
+    if x.dtype not in (t.float32, t.float64):
+        raise TypeError(f"field statistics on the GPU take torch.float32 and torch.float64 tensors, not {x.dtype}: "
+                        "pass a NumPy array for the host path")
+    if x.numel() == 0:
+        raise ValueError("field statistics need at least one value")
+    if over == "all":
+        T, H, W, shape = 1, 1, x.numel(), ()
+    else:
+        if x.dim() != 3:
+            raise ValueError(f"over={over!r} takes a (t, y, x) volume, not {tuple(x.shape)}")
+        T, H, W = (int(n) for n in x.shape)
+        shape = (T,) if over == "frame" else (H, W)
+    L = _lib.lib()
+    x = _lib.to_dev(x)
+    code = _lib.TF_F32 if x.dtype == t.float32 else _lib.TF_F64
+    S = int(np.prod(shape, dtype=np.int64))
+    count, stats = _lib.empty((S,), t.int64), _lib.empty((5, S), t.float64)
+    ws = _lib.workspace(L.tf_field_stats_workspace_bytes(code, T, H, W, FIELD_STATS_OVER[over]), "field_stats")
+    _lib.check(L.tf_field_stats(_lib.ptr(x), code, T, H, W, FIELD_STATS_OVER[over], _lib.ptr(count), _lib.ptr(stats),
+                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "tf_field_stats")
+    out = {"count": count.reshape(shape)}
+    out.update((name, stats[k].reshape(shape)) for k, name in enumerate(("mean", "std", "median", "max", "min")))
+    return out

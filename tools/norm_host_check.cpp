@@ -114,8 +114,8 @@ static void uniform(const float *f0, const float *f1, int64_t n, const TfNormPar
         }
         for (int sl = 0; sl < nactive; sl++) {
             unsigned *h = hist.data() + (size_t)sl * NM_BINS;
-            for (int t = 0; t < NM_LANES; t++) nm_scan_sum(t, h, part.data());
-            for (int t = 0; t < NM_LANES; t++) nm_scan_write(t, h, part.data());
+            for (int t = 0; t < NM_LANES; t++) rs_scan_sum(t, h, part.data());
+            for (int t = 0; t < NM_LANES; t++) rs_scan_write(t, h, part.data());
         }
         for (int t = 0; t < NM_LANES; t++) nm_resolve_digit(t, R, pass, sel, newp.data());
         for (int t = 0; t < NM_LANES; t++) nm_resolve_count(t, R, newp.data(), cnt.data());
@@ -135,7 +135,7 @@ int main(int argc, char **argv)
     // keys: order-preserving, and back
     const float vals[] = {-INFINITY, -3.5f, -1e-40f, -0.0f, 0.0f, 1e-40f, 2.25f, INFINITY};
     for (size_t a = 0; a + 1 < sizeof vals / sizeof *vals; a++)
-        if (!(nm_key(vals[a]) < nm_key(vals[a + 1])) || nm_unkey(nm_key(vals[a])) != vals[a]) { printf("FAILED key order at %zu\n", a); failures++; }
+        if (!(rs_key(vals[a]) < rs_key(vals[a + 1])) || rs_unkey(rs_key(vals[a])) != vals[a]) { printf("FAILED key order at %zu\n", a); failures++; }
     while (std::getline(manifest, line)) {
         if (line.empty()) continue;
         std::istringstream in(line);
