@@ -629,6 +629,60 @@ int tf_relabel_merge(const int32_t *own, int64_t T, int64_t hw, const int32_t *l
 size_t tf_field_stats_workspace_bytes(int dtype, int64_t T, int64_t H, int64_t W, int over);
 int tf_field_stats(const void *field, int dtype, int64_t T, int64_t H, int64_t W, int over, int64_t *count, double *stats,
                    void *ws, size_t ws_bytes, void *stream);
+/* tf_group_reduce (version 113): tobac_flow/utils/stats_utils.py:171-349, utils/filter_utils.py:33-289 and
+ *   postprocess.py:313-1170 -- the per-object reductions of the third stage over N step records.  `ids` (N values, TF_I32
+ *   or TF_I64: arbitrary, sparse, in any order) names every record's group; `coord` holds the G group ids, strictly
+ *   ascending, in the same type.  A record's group is the rank of its id in `coord`; the members of a group are walked in
+ *   the record order of the input (xarray's groupby order), so sums are float64 sums in that order and every result has the
+ *   same bits from run to run.  `ops` is a HOST table of 0 .. TF_GROUP_MAX_OPS entries evaluated over the one grouping:
+ *     f, w, aux   device columns of N elements; f_dtype / w_dtype / aux_dtype TF_F32, TF_F64 or TF_I64 (below).  Float
+ *                 columns are evaluated in float64
+ *     out         G elements of 8 bytes on the device: float64, or int64 where marked [i]
+ *     TF_GROUP_COUNT                 [i] records of the group (no column)
+ *     TF_GROUP_SUM / MEAN            of f skipping NaN (xarray's skipna): all NaN gives 0 / NaN
+ *     TF_GROUP_MIN / MAX             of f skipping NaN, NaN when all are; f TF_I64 gives [i]
+ *     TF_GROUP_PICK_ARGMIN / ARGMAX  [i] original position of np.argmin / np.argmax of f (float or TF_I64): first
+ *                                    occurrence, the first NaN when there is one
+ *     TF_GROUP_PICK_IDXMIN / IDXMAX  [i] the same skipping NaN; -1 when all are NaN
+ *     TF_GROUP_WEIGHTED_AVERAGE      sum f w / sum w (np.average: NaN propagates); NaN for a zero weight sum
+ *     TF_GROUP_COMBINED_MEAN         calc_combined_mean(f = step means, w = step areas), over records with both finite
+ *     TF_GROUP_COMBINED_STD          calc_combined_std(f = step stds, aux = step means, w = step areas)
+ *     TF_GROUP_AVERAGE_UNCERTAINTY   weighted_average_uncertainty(f = errors, w = weights)
+ *     TF_GROUP_FIRST_MINUS_LAST / LAST_MINUS_FIRST   of f in record order; f TF_I64 gives [i]
+ *     TF_GROUP_MAX_DIFF              max(np.diff(f)) in record order, 0 for one record; f TF_I64 gives [i]
+ *     TF_GROUP_ANY_NAN               [i] 1 when some f is NaN
+ *     TF_GROUP_GRADIENT_MIN          min, skipping NaN, of np.gradient(f, aux, edge_order=1) with aux (times, float or
+ *                                    TF_I64) converted to float64; NaN for a group of one record
+ *     TF_GROUP_GRADIENT_PICK_IDXMIN  [i] original position of that minimum (first occurrence), -1 where there is none
+ *   status (device, two uint64): [0] = records whose id is not in `coord` (they join no group), [1] = groups without a
+ *   record (their outputs are those of an empty run).  Requires N, G < 2^31 - 2.  TF_EINVAL before any launch: null
+ *   pointers, an unknown op or a dtype the op does not take, more than 16 ops; TF_ENOMEM: workspace below
+ *   tf_group_reduce_workspace_bytes (0 for sizes out of range). */
+#define TF_I64 6         /* tf_group_reduce only: ids, times */
+#define TF_GROUP_MAX_OPS 16
+#define TF_GROUP_COUNT 0
+#define TF_GROUP_SUM 1
+#define TF_GROUP_MEAN 2
+#define TF_GROUP_MIN 3
+#define TF_GROUP_MAX 4
+#define TF_GROUP_PICK_ARGMIN 5
+#define TF_GROUP_PICK_ARGMAX 6
+#define TF_GROUP_PICK_IDXMIN 7
+#define TF_GROUP_PICK_IDXMAX 8
+#define TF_GROUP_WEIGHTED_AVERAGE 9
+#define TF_GROUP_COMBINED_MEAN 10
+#define TF_GROUP_COMBINED_STD 11
+#define TF_GROUP_AVERAGE_UNCERTAINTY 12
+#define TF_GROUP_FIRST_MINUS_LAST 13
+#define TF_GROUP_LAST_MINUS_FIRST 14
+#define TF_GROUP_MAX_DIFF 15
+#define TF_GROUP_ANY_NAN 16
+#define TF_GROUP_GRADIENT_MIN 17
+#define TF_GROUP_GRADIENT_PICK_IDXMIN 18
+typedef struct { int op; int f_dtype; int w_dtype; int aux_dtype; const void *f; const void *w; const void *aux; void *out; } tf_group_op;
+size_t tf_group_reduce_workspace_bytes(int64_t N, int64_t G);
+int tf_group_reduce(const void *ids, int id_dtype, int64_t N, const void *coord, int64_t G, const tf_group_op *ops, int n_ops,
+                    uint64_t *status, void *workspace, size_t workspace_bytes, void *stream);
 /* The elementwise glue of detect_anvils' seeds (tobac_flow/detection.py:547-561, 590-617) in two passes:
  * tf_field_masks: ge1 = field >= 1, le0_or_nan = (field <= 0) | isnan(field), isnan_out = isnan(field) as 0 / 1 bytes;
  * tf_merge_seeds: seeds = (bg | isnan) ? -1 : comp. */

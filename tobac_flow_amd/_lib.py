@@ -74,6 +74,17 @@ class LabelCriterion(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int), ("op", ctypes.c_int), ("threshold", ctypes.c_double)]
 
 
+class GroupOp(ctypes.Structure):
+    """tf_group_op of include/tobac_flow_hip.h"""
+    _fields_ = [("op", ctypes.c_int), ("f_dtype", ctypes.c_int), ("w_dtype", ctypes.c_int), ("aux_dtype", ctypes.c_int),
+                ("f", ctypes.c_void_p), ("w", ctypes.c_void_p), ("aux", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+
+
+TF_I64, GROUP_MAX_OPS = 6, 16
+GROUP_OPS = {name: code for code, name in enumerate((
+    "COUNT", "SUM", "MEAN", "MIN", "MAX", "PICK_ARGMIN", "PICK_ARGMAX", "PICK_IDXMIN", "PICK_IDXMAX", "WEIGHTED_AVERAGE",
+    "COMBINED_MEAN", "COMBINED_STD", "AVERAGE_UNCERTAINTY", "FIRST_MINUS_LAST", "LAST_MINUS_FIRST", "MAX_DIFF", "ANY_NAN",
+    "GRADIENT_MIN", "GRADIENT_PICK_IDXMIN"))}
 CMP_OPS = {">=": 0, ">": 1, "<=": 2, "<": 3}
 BIN_RULE_NUMPY, BIN_RULE_SCIPY, BIN_FINITE_VALUE = 0, 1, 1
 BIN_STATUS_COORD, BIN_STATUS_VALUE, BIN_STATUS_RULES_DIFFER = 1, 2, 4
@@ -174,6 +185,8 @@ _PROTOS = {
                                     _P, _c.c_int64, _P, _P, _c.c_int, _P, _P, _P]),
     "tf_field_stats_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int]),
     "tf_field_stats": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_group_reduce_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    "tf_group_reduce": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_int64, _c.POINTER(GroupOp), _c.c_int, _P, _P, _c.c_size_t, _P]),
     "tf_field_masks": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P]),
     "tf_merge_seeds": (_c.c_int, [_P, _P, _P, _c.c_int64, _P, _P]),
     "tf_label_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64]),

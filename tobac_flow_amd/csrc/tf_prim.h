@@ -27,6 +27,13 @@ static inline hipError_t tf_sort_pairs(void *tmp, size_t &bytes, const K *keys_i
 {
     return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 8 * sizeof(K), s);
 }
+// the same (stable) sort over the key bits [begin_bit, end_bit) only: keys known to stay below 2^end_bit need no more passes
+template <typename K, typename V>
+static inline hipError_t tf_sort_pairs_bits(void *tmp, size_t &bytes, const K *keys_in, K *keys_out, const V *vals_in, V *vals_out, size_t n,
+                                            unsigned begin_bit, unsigned end_bit, hipStream_t s = 0)
+{
+    return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, s);
+}
 template <typename K, typename V, typename NOut>
 static inline hipError_t tf_sum_by_key(void *tmp, size_t &bytes, const K *keys_in, K *unique_out, const V *vals_in, V *sums_out, NOut n_out, size_t n, hipStream_t s = 0)
 {

@@ -9,9 +9,11 @@ formulas are those of utils.stats_utils (weighted_stats, weighted_stats_and_unce
 which remain the per-region host forms and the fallback for what the kernels do not take.
 
 xarray is not in this image: names, dimension names and values are the reference's, `attrs` are not carried, and a flag
-array's `flag_values` and `name` are keyword arguments because there is no DataArray to read them from.  The `*_groupby`
-helpers, `process_*_properties`, `add_cre_to_dataset` and `add_validity_flags` of the reference's module are out of scope
-(DESIGN.md)."""
+array's `flag_values` and `name` are keyword arguments because there is no DataArray to read them from.
+
+The third stage is at the end of the module: process_core_properties, process_thick_anvil_properties,
+process_thin_anvil_properties and add_validity_flags (postprocess.py:313-1314) over the step records of a LabelDataset
+table, as batches of tf_group_reduce operations.  `add_cre_to_dataset` of the reference's module is out of scope."""
 from functools import partial
 
 import numpy as np
@@ -272,5 +274,220 @@ def add_weighted_proportions_to_dataset(dcc_dataset, flag_da, weights, dim, dim_
     return dcc_dataset
 
 
+# ---- the third stage: object properties from step records (reference: postprocess.py:313-1314) ---------------------------
+# The reference makes one xarray.groupby per variable; here every function plans its column operations first and hands
+# them to _groups.reduce_groups together: one grouping per dimension, sixteen operations per tf_group_reduce call.  With
+# device columns nothing but the coordinates (and, where `geod_inv` is given, its inputs) is seen by the host.
+_SUFFIX_OPS = (("_mean_uncertainty", "AVERAGE_UNCERTAINTY"), ("_mean_combined_error", None), ("_min_error", "PICK_ARGMIN"),
+               ("_max_error", "PICK_ARGMAX"), ("_mean", "COMBINED_MEAN"), ("_std", "COMBINED_STD"), ("_min", "MIN"), ("_max", "MAX"))
+
+
+def _as_like(x, like):
+    """a host array as a device tensor where the table's columns are device tensors"""
+    if _is_tensor(like) and not _is_tensor(x):
+        x = np.asarray(x)
+        x = x.view(np.int64) if x.dtype.kind in "mM" else x
+        return _lib().torch().from_numpy(np.ascontiguousarray(x)).to(like.device)
+    return x
+
+
+def _azimuth_and_speed(lons, lats, t, geod_inv):
+    """get_mean_object_azimuth_and_speed (reference: utils/geo_utils.py:62-84) with the geodesic inverse handed in"""
+    from scipy.stats import circmean
+    order = np.argsort(t)
+    seconds = np.diff(t[order]).astype(np.int64) / 1e9
+    azimuths, _, distances = geod_inv(lons[order][:-1], lats[order][:-1], lons[order][1:], lats[order][1:])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        speeds = np.asarray(distances) / seconds
+    keep = np.isfinite(azimuths) & np.isfinite(speeds)
+    if not keep.any():
+        return np.nan, np.nan
+    return circmean(np.asarray(azimuths)[keep], high=180, low=-180), np.mean(speeds[keep])
+
+
+def _propagation(dataset, step, index_name, parent, geod_inv):
+    groups, coord = _host(dataset[index_name]), np.asarray(dataset.coords[parent])
+    lons, lats = _host(dataset[f"{step}_lon"]), _host(dataset[f"{step}_lat"])
+    t = _host(dataset[f"{step}_t"])
+    t = np.asarray(t).astype("datetime64[ns]").view(np.int64) if np.asarray(t).dtype.kind == "M" else np.asarray(t)
+    order = np.argsort(groups, kind="stable")
+    bounds = np.searchsorted(groups[order], coord, side="left"), np.searchsorted(groups[order], coord, side="right")
+    out = np.full((coord.size, 2), np.nan)
+    for k, (b, e) in enumerate(zip(*bounds)):
+        if e - b > 1:
+            members = order[b:e]
+            out[k] = _azimuth_and_speed(lons[members], lats[members], t[members], geod_inv)
+    return out[:, 0], out[:, 1]
+
+
+def _object_properties(dataset, kind, parent, extremes, rates, geod_inv=None, propagation=None):
+    from tobac_flow_amd import _groups
+    step = f"{kind}_step"
+    index_name = f"{step}_{parent}_index"
+    groups, coord = dataset[index_name], dataset.coords[parent]
+    steps = _as_like(dataset.coords[step], groups)
+    t_column = dataset[f"{step}_t"]
+    t, area = _groups.as_ticks(t_column), dataset[f"{step}_area"]
+    ops, finish = [], []
+
+    def plan(op, then):
+        ops.append(op)
+        finish.append(then)
+
+    def put(name):
+        return lambda value: dataset.add(name, value, (parent,))
+
+    def put_at(name, column):
+        return lambda pick: dataset.add(name, _groups.take(column, pick), (parent,))
+
+    def start_end(which, op):
+        def then(pick):
+            if kind == "core" and which == "start":
+                dataset.add("core_initial_core_step_index", _groups.take(steps, pick), (parent,))
+            for c in ("x", "y", "lat", "lon", "t"):
+                dataset.add(f"{kind}_{which}_{c}", _groups.take(dataset[f"{step}_{c}"], pick), (parent,))
+        plan((op, t), then)
+
+    start_end("start", "PICK_ARGMIN")
+    start_end("end", "PICK_ARGMAX")
+    for c in ("x", "y", "lat", "lon"):
+        plan(("WEIGHTED_AVERAGE", dataset[f"{step}_{c}"], area), put(f"{kind}_average_{c}"))
+    plan(("MEAN", area), put(f"{kind}_average_area"))
+    plan(("SUM", area), put(f"{kind}_total_area"))
+    plan(("MAX", area), put(f"{kind}_max_area"))
+    plan(("PICK_ARGMAX", area), put_at(f"{kind}_max_area_t", t_column))
+    plan(("PICK_IDXMAX", area), put_at(f"{kind}_max_area_{step}_index", steps))
+    for field, largest, t_name in extremes:
+        if f"{step}_{field}_mean" not in dataset:
+            continue
+        column = dataset[f"{step}_{field}_mean"]
+        word = "max" if largest else "min"
+        plan(("PICK_ARGMAX" if largest else "PICK_ARGMIN", column), put_at(t_name or f"{kind}_{word}_{field}_t", t_column))
+        plan(("PICK_IDXMAX" if largest else "PICK_IDXMIN", column), put_at(f"{kind}_{word}_{field}_{step}_index", steps))
+        if field in rates:
+            falling = -column if largest else column              # a height grows where its negative cools
+            plan(("GRADIENT_MIN", falling, None, t), lambda value, name=rates[field]: dataset.add(name, -value * 6e10, (parent,)))
+            plan(("GRADIENT_PICK_IDXMIN", falling, None, t), put_at(f"{rates[field]}_{step}_index", steps))
+
+    combined_errors = []
+    for var in [v for v in dataset if dataset.dims.get(v) == (step,)]:
+        suffix, op = next(((s, o) for s, o in _SUFFIX_OPS if var.endswith(s)), (None, None))
+        if suffix is None:
+            continue
+        new_var = f"{kind}_" + var[len(step) + 1:]
+        if suffix == "_mean":
+            plan((op, dataset[var], area), put(new_var))
+        elif suffix == "_std":
+            plan((op, dataset[var], area, dataset[var[:-3] + "mean"]), put(new_var))
+        elif suffix in ("_min", "_max"):
+            plan((op, dataset[var]), put(new_var))
+        elif suffix == "_mean_uncertainty":
+            plan((op, dataset[var], area), put(new_var))
+        elif suffix == "_mean_combined_error":
+            std_var = f"{kind}_" + var[len(step) + 1:-len("_mean_combined_error")] + "_std"
+            slot = {}
+            plan(("AVERAGE_UNCERTAINTY", dataset[var], area), lambda value, slot=slot: slot.update(uncertainty=value))
+            plan(("COUNT",), lambda value, slot=slot: slot.update(counts=value.double() if _is_tensor(value) else value.astype(np.float64)))
+            combined_errors.append((new_var, std_var, slot))
+        else:                                                     # _min_error / _max_error: the error at the extreme of var[:-6]
+            plan((op, dataset[var[:-6]]), put_at(new_var, dataset[var]))
+
+    for then, value in zip(finish, _groups.reduce_groups(groups, coord, ops)):
+        then(value)
+    dataset.add(f"{kind}_lifetime", dataset[f"{kind}_end_t"] - dataset[f"{kind}_start_t"], (parent,))
+    for new_var, std_var, slot in combined_errors:
+        dataset.add(new_var, ((dataset[std_var] / slot["counts"] ** 0.5) ** 2 + slot["uncertainty"] ** 2) ** 0.5, (parent,))
+    if geod_inv is not None and propagation is not None:
+        direction, speed = _propagation(dataset, step, index_name, parent, geod_inv)
+        dataset.add(f"{propagation}_propagation_direction", _as_like(direction, groups), (parent,))
+        dataset.add(f"{propagation}_propagation_speed", _as_like(speed, groups), (parent,))
+    return dataset
+
+
+_CORE_EXTREMES = (("bt", False, None), ("ctt", False, None), ("ctt_corrected", False, None), ("cth", True, None),
+                  ("cth_corrected", True, None))
+_CORE_RATES = {"bt": "core_max_cooling_rate", "ctt": "core_ctt_cooling_rate", "ctt_corrected": "core_ctt_corrected_cooling_rate",
+               "cth": "core_cth_growth_rate", "cth_corrected": "core_cth_corrected_growth_rate"}
+
+
+def process_core_properties(dataset, time_steps=3, *, geod_inv=None):
+    """Per core, from its core_step records (reference: postprocess.py:313-640): start / end position and time, lifetime,
+    area-weighted average position, average / total / max area and when it was reached; for each of bt, ctt,
+    ctt_corrected, cth, cth_corrected step means present, the time and step of the extreme and the steepest cooling (or
+    growth) rate in K (or height) per minute with its step; and per core_step variable, by suffix, the combined _mean and
+    _std, _min, _max, _mean_uncertainty, _mean_combined_error, _min_error and _max_error.  `time_steps` is accepted and
+    unused, as in the reference.  A step index is 0 where the reference would yield NaN (utils.stats_utils.idxmin_groupby).
+
+    core_propagation_direction and core_propagation_speed need pyproj's geodesic inverse, which this package does not
+    depend on: pass `geod_inv`, a callable with `pyproj.Geod.inv`'s signature (lons1, lats1, lons2, lats2) ->
+    (azimuths, back azimuths, distances), and they are computed on the host per core after
+    get_mean_object_azimuth_and_speed; with None they are left out.  Returns `dataset`."""
+    return _object_properties(dataset, "core", "core", _CORE_EXTREMES, _CORE_RATES, geod_inv, "core")
+
+
+def process_thick_anvil_properties(dataset, *, geod_inv=None):
+    """process_core_properties for the anvils' thick_anvil_step records, without rates (reference: postprocess.py:643-922).
+    anvil_propagation_direction / _speed are written only with `geod_inv` (see process_core_properties)."""
+    extremes = (("bt", False, None), ("ctt", False, None), ("ctt_corrected", False, None), ("cth", True, None),
+                # the reference's one misnamed assignment (postprocess.py:808): the time of the largest cth_corrected is written
+                # to thick_anvil_min_ctt_corrected_t, over the value of the ctt_corrected branch; reproduced
+                ("cth_corrected", True, "thick_anvil_min_ctt_corrected_t"))
+    return _object_properties(dataset, "thick_anvil", "anvil", extremes, {}, geod_inv, "anvil")
+
+
+def process_thin_anvil_properties(dataset):
+    """process_core_properties for the anvils' thin_anvil_step records, without rates and propagation (reference:
+    postprocess.py:925-1170)"""
+    return _object_properties(dataset, "thin_anvil", "anvil", _CORE_EXTREMES, {})
+
+
+def add_validity_flags(dataset):
+    """core_has_anvil_flag, core_anvil_removed (core_anvil_index set to 0 for those), anvil_core_count,
+    anvil_initial_core_index, anvil_no_growth_flag, anvil_no_initial_core_flag, core_is_valid, anvil_invalid_core_flag,
+    thick_anvil_is_valid, thin_anvil_is_valid (reference: postprocess.py:1173-1314).  Needs the outputs of
+    process_core_properties and process_thick_anvil_properties; every anvil must have a core (filter_anvils)."""
+    from tobac_flow_amd import _groups
+    from tobac_flow_amd.utils.filter_utils import _flag
+    from tobac_flow_amd.utils.xarray_utils import isin_coord, mask_positions
+    anvil = dataset.coords["anvil"]
+    core_anvil = dataset["core_anvil_index"]
+    has_anvil = isin_coord(core_anvil, anvil)
+    dataset.add("core_has_anvil_flag", has_anvil, ("core",))
+    dataset.add("core_anvil_removed", ~has_anvil & (core_anvil != 0), ("core",))
+    core_anvil = core_anvil * has_anvil.to(core_anvil.dtype) if _is_tensor(core_anvil) else np.where(has_anvil, core_anvil, 0)
+    dataset.add("core_anvil_index", core_anvil, ("core",))
+
+    def flag(name):
+        return _flag(dataset[name], has_anvil)
+
+    invalid_core = flag("core_edge_label_flag") | flag("core_start_label_flag") | flag("core_end_label_flag")
+    if "core_nan_flag" in dataset:
+        invalid_core = invalid_core | flag("core_nan_flag")
+    dataset.add("core_is_valid", ~invalid_core, ("core",))
+
+    with_anvil = mask_positions(has_anvil)
+    valid = (~invalid_core)[with_anvil]
+    valid = valid.to(_lib().torch().float64) if _is_tensor(valid) else valid.astype(np.float64)
+    counts, first_core, all_valid = _groups.reduce_groups(
+        core_anvil[with_anvil], anvil, [("COUNT",), ("PICK_ARGMIN", _groups.as_ticks(dataset["core_start_t"])[with_anvil]), ("MIN", valid)])
+    dataset.add("anvil_core_count", counts, ("anvil",))
+    first_core = _groups.take(with_anvil, first_core)             # position among all cores
+    dataset.add("anvil_initial_core_index", _groups.take(_as_like(dataset.coords["core"], has_anvil), first_core), ("anvil",))
+    no_growth = dataset["thick_anvil_max_area_t"] <= _groups.take(dataset["core_end_t"], first_core)
+    no_initial_core = dataset["thick_anvil_start_t"] < _groups.take(dataset["core_start_t"], first_core)
+    dataset.add("anvil_no_growth_flag", no_growth, ("anvil",))
+    dataset.add("anvil_no_initial_core_flag", no_initial_core, ("anvil",))
+    invalid_cores = all_valid != 1
+    dataset.add("anvil_invalid_core_flag", invalid_cores, ("anvil",))
+    for kind in ("thick_anvil", "thin_anvil"):
+        invalid = invalid_cores | no_growth | no_initial_core | flag(f"{kind}_edge_label_flag") | flag(f"{kind}_start_label_flag") | \
+            flag(f"{kind}_end_label_flag")
+        if f"{kind}_nan_flag" in dataset:
+            invalid = invalid | flag(f"{kind}_nan_flag")
+        dataset.add(f"{kind}_is_valid", ~invalid, ("anvil",))
+    return dataset
+
+
 __all__ = ("weighted_label_stats", "add_weighted_stats_to_dataset", "get_weighted_proportions_da",
-           "add_weighted_proportions_to_dataset")
+           "add_weighted_proportions_to_dataset", "process_core_properties", "process_thick_anvil_properties",
+           "process_thin_anvil_properties", "add_validity_flags")

@@ -10,10 +10,14 @@ from tobac_flow_amd.utils.label_utils import (apply_func_to_labels, find_overlap
                                               relabel_objects, remap_labels, slice_labels)
 from tobac_flow_amd.utils.normalisation_utils import (inverse_log_norm, linear_norm, linearise_field, local_linear_norm,
                                                       log_norm, select_normalisation_method, to_8bit, uniform_norm, z_norm)
-from tobac_flow_amd.utils.stats_utils import (find_overlap_mode, get_weighted_proportions, mse, n_unique_along_axis, weighted_average_and_std,
-                                              weighted_average_uncertainty, weighted_stats,
+from tobac_flow_amd.utils.stats_utils import (argmax_groupby, argmin_groupby, calc_combined_mean, calc_combined_std,
+                                              combined_mean_groupby, combined_std_groupby, cooling_rate_groupby, counts_groupby,
+                                              find_overlap_mode, get_weighted_proportions, idxmax_cooling_rate_groupby,
+                                              idxmax_groupby, idxmin_groupby, mse, n_unique_along_axis, weighted_average_and_std,
+                                              weighted_average_groupby, weighted_average_uncertainty,
+                                              weighted_average_uncertainty_groupby, weighted_stats,
                                               weighted_stats_and_uncertainties, weighted_uncertainties)
-from tobac_flow_amd.utils.xarray_utils import get_coord_bin_edges
+from tobac_flow_amd.utils.xarray_utils import get_coord_bin_edges, isel_anvil, isel_core, sel_anvil, sel_core
 
 __all__ = (
     "get_datetime_from_coord", "get_time_diff_from_coord", "time_diff",
@@ -24,5 +28,8 @@ __all__ = (
     "select_normalisation_method", "to_8bit", "uniform_norm", "z_norm",
     "mse", "find_overlap_mode", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
     "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions",
-    "get_coord_bin_edges",
+    "calc_combined_mean", "calc_combined_std", "combined_mean_groupby", "combined_std_groupby", "weighted_average_groupby",
+    "weighted_average_uncertainty_groupby", "argmax_groupby", "argmin_groupby", "counts_groupby", "idxmin_groupby",
+    "idxmax_groupby", "cooling_rate_groupby", "idxmax_cooling_rate_groupby",
+    "get_coord_bin_edges", "sel_anvil", "isel_anvil", "sel_core", "isel_core",
 )

@@ -158,5 +158,107 @@ def get_weighted_proportions(data, weights, flag_values):
         return np.array([np.nansum(np.where(data == f, counted, 0.0)) for f in flag_values]) / total
 
 
+def calc_combined_mean(step_mean, step_area):
+    """area-weighted mean of one object's step means over the steps where mean and area are both finite; NaN where there
+    is none (reference: stats_utils.py:171-179)"""
+    step_mean, step_area = np.asarray(step_mean), np.asarray(step_area)
+    keep = np.isfinite(step_mean) & np.isfinite(step_area)
+    if not keep.any():
+        return np.nan
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sum(step_mean[keep] * step_area[keep]) / np.sum(step_area[keep])
+
+
+def calc_combined_std(step_std, step_mean, step_area):
+    """sqrt((sum a s + sum a (m - combined mean)^2) / sum a) over the steps where all three are finite, as the reference
+    writes it (the step value enters unsquared); NaN where there is none (reference: stats_utils.py:182-199)"""
+    step_std, step_mean, step_area = np.asarray(step_std), np.asarray(step_mean), np.asarray(step_area)
+    combined_mean = calc_combined_mean(step_mean, step_area)
+    keep = np.isfinite(step_std) & np.isfinite(step_mean) & np.isfinite(step_area)
+    if not keep.any():
+        return np.nan
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt((np.sum(step_area[keep] * step_std[keep]) + np.sum(step_area[keep] * (step_mean[keep] - combined_mean) ** 2))
+                       / np.sum(step_area[keep]))
+
+
+# ---- per-object reductions over step records (reference: stats_utils.py:202-349) -----------------------------------------
+# Every *_groupby takes 1-D record columns, the records' `groups` column (the *_step_*_index variable) and `coord`, the
+# sorted ids of the objects, and returns one value per id of `coord`: device tensors in, a device tensor out
+# (tf_group_reduce); NumPy arrays in, a NumPy array out.  Members of a group are taken in record order.  Unlike the
+# reference, a record whose id is missing from `coord` and a `coord` id without records raise ValueError.
+def _reduce(groups, coord, *ops):
+    from tobac_flow_amd import _groups
+    return _groups.reduce_groups(groups, coord, list(ops))
+
+
+def _take(column, pick, missing=0):
+    from tobac_flow_amd import _groups
+    return _groups.take(column, pick, missing)
+
+
+def combined_mean_groupby(means, area, groups, coord):
+    """calc_combined_mean per object"""
+    return _reduce(groups, coord, ("COMBINED_MEAN", means, area))[0]
+
+
+def combined_std_groupby(stds, means, area, groups, coord):
+    """calc_combined_std per object"""
+    return _reduce(groups, coord, ("COMBINED_STD", stds, area, means))[0]
+
+
+def weighted_average_uncertainty_groupby(field, area, groups, coord):
+    """weighted_average_uncertainty(errors=field, weights=area) per object"""
+    return _reduce(groups, coord, ("AVERAGE_UNCERTAINTY", field, area))[0]
+
+
+def weighted_average_groupby(field, area, groups, coord):
+    """np.average(field, weights=area) per object (NaN propagates); NaN where the weights sum to zero, which np.average
+    refuses"""
+    return _reduce(groups, coord, ("WEIGHTED_AVERAGE", field, area))[0]
+
+
+def argmax_groupby(field, find_max, groups, coord):
+    """per object, `field` at the step where `find_max` is largest (np.argmax: the first such step, the first NaN if any)"""
+    return _take(field, _reduce(groups, coord, ("PICK_ARGMAX", find_max))[0])
+
+
+def argmin_groupby(field, find_min, groups, coord):
+    """per object, `field` at the step where `find_min` is smallest (np.argmin: the first such step, the first NaN if any)"""
+    return _take(field, _reduce(groups, coord, ("PICK_ARGMIN", find_min))[0])
+
+
+def counts_groupby(groups, coord):
+    """number of step records per object; int64"""
+    return _reduce(groups, coord, ("COUNT",))[0]
+
+
+def idxmin_groupby(steps, field, groups, coord):
+    """per object, the step id (from the `steps` column, which the reference reads off the DataArray's index) at the
+    smallest non-NaN `field`.  An object whose `field` is NaN throughout gets step id 0 -- step ids start at 1 -- where
+    the reference would yield a float NaN."""
+    return _take(steps, _reduce(groups, coord, ("PICK_IDXMIN", field))[0])
+
+
+def idxmax_groupby(steps, field, groups, coord):
+    """idxmin_groupby for the largest non-NaN `field`; step id 0 for an object that is NaN throughout"""
+    return _take(steps, _reduce(groups, coord, ("PICK_IDXMAX", field))[0])
+
+
+def cooling_rate_groupby(BT, times, groups, coord):
+    """per object, -min(np.gradient(BT, times, edge_order=1)) * 6e10 with `times` in nanoseconds (datetime64[ns] or int64
+    ticks, taken as float64): kelvin per minute.  NaN for an object of one step."""
+    return -_reduce(groups, coord, ("GRADIENT_MIN", BT, None, times))[0] * 6e10
+
+
+def idxmax_cooling_rate_groupby(steps, BT, times, groups, coord):
+    """the step id at that steepest cooling; step id 0 where there is none (one step, or NaN throughout), where the
+    reference would yield a float NaN"""
+    return _take(steps, _reduce(groups, coord, ("GRADIENT_PICK_IDXMIN", BT, None, times))[0])
+
+
 __all__ = ("mse", "find_overlap_mode", "n_unique_along_axis", "weighted_average_and_std", "weighted_stats", "weighted_average_uncertainty",
-           "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions")
+           "weighted_uncertainties", "weighted_stats_and_uncertainties", "get_weighted_proportions", "calc_combined_mean",
+           "calc_combined_std", "combined_mean_groupby", "combined_std_groupby", "weighted_average_uncertainty_groupby",
+           "weighted_average_groupby", "argmax_groupby", "argmin_groupby", "counts_groupby", "idxmin_groupby", "idxmax_groupby",
+           "cooling_rate_groupby", "idxmax_cooling_rate_groupby")
