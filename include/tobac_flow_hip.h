@@ -357,12 +357,15 @@ int tf_sobel_edge_field(const float *field, int64_t T, int64_t H, int64_t W, con
  *            floodable pixel (or at a seed next to one) is TF_EINVAL: the reference's heap order is undefined for NaN
  *   markers  (T, H, W) int32, non-zero = seed (negative allowed)
  *   mask     (T, H, W) int8 or NULL (= all ones)
- *   fwd, bwd (T, H, W, 2) float; rounded half-to-even to integer pixel offsets (watershed.py:121-141)
+ *   fwd, bwd (T, H, W, 2) float; rounded half-to-even to integer pixel offsets (watershed.py:121-141); NaN -> 0
  *   nbr_host n_nbr x 3 int8 (dt, dy, dx) neighbour list IN THE REFERENCE'S ORDER
  *            (skimage _offsets_to_raveled_neighbors, watershed.py:114-116)
  *   chain_depth  number of tie-break levels of the pop-order key (>= 1; 3 suffices for tie-free
  *            fields and for the plateau structure of detect_anvils; see DESIGN.md and the contract below)
  *   labels   (T, H, W) int32 out
+ * Alignment (tf_version() >= 114): fwd and bwd 8-byte aligned (a flow vector is read as one float2), field and markers
+ * 4-byte aligned; anything else is TF_EINVAL before any launch.  Arrays that are also 16-byte aligned (mask: 4-byte) take
+ * the four-voxels-per-thread set-up passes; the results do not depend on it.
  * No padding is needed: out-of-volume neighbours are rejected by coordinate tests, which is what
  * the reference's zero-padded mask achieves (watershed.py:111-113).
  * Workspace: the flood keys live in compact arrays over the RELEVANT pixels (floodable pixels +

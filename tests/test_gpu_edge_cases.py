@@ -155,17 +155,19 @@ def test_watershed_extreme_flows_and_seeds_outside_mask(tf, seed):
     are rounded to 0 here (the reference would crash on them), markers that lie outside the mask still seed"""
     from oracle import ws_oracle
     rng = np.random.default_rng(200 + seed)
-    shape = (4, 45, 50)
-    field = rand_field(rng, shape)
-    markers = seeds(rng, shape, 8)
-    mask = ndi.gaussian_filter(rng.normal(size=shape), (0, 2, 2)) > -0.1
-    fwd = rng.choice(np.array([-20, -7.5, -2.5, -0.5, 0, 0.5, 1.5, 3.5, 20], np.float32), size=shape + (2,))
-    bwd = rng.choice(np.array([-20, -7.5, -2.5, -0.5, 0, 0.5, 1.5, 3.5, 20], np.float32), size=shape + (2,))
-    conn = [1, 3][seed % 2]
-    got = tf.watershed(fwd, bwd, field, markers, mask=mask, connectivity=conn)
-    want = ws_oracle.watershed(fwd, bwd, field, markers, mask, conn)
-    assert np.array_equal(got, want), f"{int((got != want).sum())} px differ"
-    assert np.array_equal(got[markers != 0], markers[markers != 0])
+    values = np.array([-20, -7.5, -2.5, -0.5, 0, 0.5, 1.5, 3.5, 20, np.nan], np.float32)
+    for shape in ((4, 45, 50), (4, 45, 52)):           # W % 4 != 0: k_ws_relevant<6>; W % 4 == 0: the four-pixel k_ws_relevant6x4
+        field = rand_field(rng, shape)
+        markers = seeds(rng, shape, 8)
+        mask = ndi.gaussian_filter(rng.normal(size=shape), (0, 2, 2)) > -0.1
+        fwd = rng.choice(values, size=shape + (2,))
+        bwd = rng.choice(values, size=shape + (2,))
+        assert np.isnan(fwd).any() and np.isnan(bwd).any()
+        conn = [1, 3][seed % 2]
+        got = tf.watershed(fwd, bwd, field, markers, mask=mask, connectivity=conn)
+        want = ws_oracle.watershed(np.nan_to_num(fwd, nan=0.0), np.nan_to_num(bwd, nan=0.0), field, markers, mask, conn)
+        assert np.array_equal(got, want), f"{int((got != want).sum())} px differ"
+        assert np.array_equal(got[markers != 0], markers[markers != 0])
 
 
 def test_watershed_custom_structure_and_inf_field(tf):

@@ -22,11 +22,12 @@ def _flat(a, dtype, name):
 
 
 def watershed_raveled(image, marker_locations, structure, forward_offset, backward_offset, forward_offset_locations,
-                      backward_offset_locations, mask, strides, compactness, output, wsl, reference_order=True):
+                      backward_offset_locations, mask, strides, compactness, output, wsl, reference_order=True, stats=None):
     """Perform the watershed on a raveled image and neighbourhood (reference: _watershed.pyx:222-344).
     `reference_order` (not in the reference; default True since round 4): equal-valued markers pop in the order the
     reference's heap gives them (TF_WS_REFERENCE_ORDER, include/tobac_flow_hip.h) -- the result of the reference's own
-    call; False: marker_locations order + a warning when a label depends on it."""
+    call; False: marker_locations order + a warning when a label depends on it.
+    `stats` (not in the reference): a dict that receives what watershed_dev reports (stats["sweeps"][6] = relevant pixels)."""
     t = _lib.torch()
     L = _lib.lib()
     image = _flat(image, np.float32, "image")
@@ -49,7 +50,7 @@ def watershed_raveled(image, marker_locations, structure, forward_offset, backwa
     d_img, d_loc = _lib.to_dev(image), _lib.to_dev(marker_locations.astype(np.int64))
     d_fo, d_bo, d_mask, d_out = _lib.to_dev(forward_offset), _lib.to_dev(backward_offset), _lib.to_dev(mask), _lib.to_dev(out)
     st64 = np.ascontiguousarray(structure, np.int64)
-    stats = np.zeros(16, np.int64)
+    report, stats = stats, np.zeros(16, np.int64)
     guess = min(n, int(((d_out == 0) & (d_mask != 0)).sum().item() * 1.5) + 4096)
     for _ in range(2):
         ws = _lib.workspace(L.tf_watershed_raveled_workspace_bytes(n, structure.size, MAX_CHAIN_DEPTH, guess), "watershed")
@@ -63,6 +64,10 @@ def watershed_raveled(image, marker_locations, structure, forward_offset, backwa
             guess = int(stats[6])
             continue
         break
+    if report is not None:
+        report["sweeps"] = stats[:8].tolist()
+        report["chain_depth"] = int(stats[8])
+        report["ambiguous_pixels"] = int(stats[9])
     if rc == TF_EDEPTH:
         raise WatershedDepthError(f"watershed_raveled: {int(stats[11])} pixel(s) still tie at chain depth {int(stats[8])}")
     if rc == TF_WS_AMBIGUOUS:

@@ -231,24 +231,11 @@ k_ws_relevant6x4(const uint8_t *__restrict__ cls, const float *__restrict__ fwd,
     *(uint32_t *)(flag + ws_vpos(g, t, y, x0)) = rel;        // (x0 % 4 == 0: the quad lies in one tile row; padding positions zeroed by the caller)
 }
 
-// the same numbering for the (t, y, x) entry points, whose scan runs in tile order
-__global__ void __launch_bounds__(256)
-k_ws_cid_tiled(const uint8_t *__restrict__ cls, const uint8_t *__restrict__ flag, const int *__restrict__ scan, WsGeom g,
-               int *__restrict__ cid)
-{
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    const int64_t t = blockIdx.z;
-    if (x >= g.W || y >= g.H) return;
-    const int64_t p = t * g.plane + (int64_t)y * g.W + x, k = ws_vpos(g, t, y, x);
-    int c = -1;
-    if (flag[k]) c = cls[p] == 1 ? scan[k] : -2 - scan[k];
-    cid[p] = c;
-}
-
-// The same ids WITHOUT a device-wide scan over one int per voxel (1.9 GB written and read back per 16 x 5424^2 window): a
-// scan position block of 256 = one 16 x 16 tile of one frame.  k_ws_count_tiles counts the flags of every tile-frame, the
-// counts are scanned (NV / 256 values, 64-bit: the total is checked against 2^30 afterwards), and k_ws_cid_tiles -- one
-// wave per tile-frame -- adds the prefix inside the tile (ballots + popcounts).
+// The ids of the (t, y, x) entry points, whose scan runs in tile order, WITHOUT a device-wide scan over one int per voxel
+// (1.9 GB written and read back per 16 x 5424^2 window): a scan position block of 256 = one 16 x 16 tile of one frame.
+// k_ws_count_tiles counts the flags of every tile-frame, the counts are scanned (NV / 256 values, 64-bit: the total is
+// checked against 2^30 afterwards), and k_ws_cid_tiles -- one wave per tile-frame -- adds the prefix inside the tile
+// (ballots + popcounts).
 // One WAVE per tile-frame, a thread = four consecutive pixels of a tile row (one word of flags, one int4 of ids): the
 // prefix inside the tile comes from four ballots, no LDS, no barrier.
 __global__ void __launch_bounds__(256)
@@ -1795,6 +1782,9 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
     if (!rv) {
         TF_REQUIRE(fwd && bwd && nbr_host, "tf_watershed: null pointer");
         TF_REQUIRE(T > 0 && H > 0 && W > 0 && H < (1 << 15) && W < (1 << 15) && T < 65536, "tf_watershed: bad shape");
+        // the set-up reads a flow vector as one float2 (the four-pixel relevance pass: as float4 where it finds 16 bytes)
+        TF_REQUIRE((uintptr_t)fwd % 8 == 0 && (uintptr_t)bwd % 8 == 0, "tf_watershed: fwd and bwd must be 8-byte aligned");
+        TF_REQUIRE((uintptr_t)field % 4 == 0 && (uintptr_t)markers % 4 == 0, "tf_watershed: field and markers must be 4-byte aligned");
     }
     TF_REQUIRE(n_nbr > 0 && n_nbr <= WS_MAX_NBR, "tf_watershed: bad neighbour count");
     TF_REQUIRE(depth0 >= 1 && depth0 <= depth_max && depth_max <= WS_MAX_DEPTH, "tf_watershed: bad chain_depth");
@@ -1828,7 +1818,6 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
     dim3 block(64, 4, 1), grid(rv ? 1 : (g.W + 63) / 64, rv ? 1 : (g.H + 3) / 4, rv ? 1 : (unsigned)T);
     const unsigned nb1 = (unsigned)((N + 255) / 256);
     int64_t R = 0;
-    bool tiles = false;
     {
         TfProfScope ps(TFK_WS_SETUP, 29.0 * (double)N, s);
         if (rv) {
@@ -1863,13 +1852,16 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
             else hipLaunchKernelGGL(k_ws_relevant<0>, grid, block, 0, s, cls, fwd, bwd, g, flag);
         }
         TF_CHECK_LAUNCH();
-        // tiled ids: per-tile counts + a scan of the counts (k_ws_cid_tiles adds the prefix inside a tile); the `scan` array
-        // (NV ints) holds the 64-bit counts and bases (2 x NV / 256 x 8 bytes)
-        const int64_t n_tiles = NV / 256;
-        size_t tile_scan_bytes = 0;
-        if (!rv) (void)tf_exclusive_sum(nullptr, tile_scan_bytes, (const long long *)nullptr, (long long *)nullptr, (size_t)n_tiles);
-        tiles = !rv && NV % 256 == 0 && n_tiles > 0 && n_tiles < 0x7fffffffll && tile_scan_bytes <= scan_bytes;
-        if (tiles) {
+        if (rv) {
+            const int rc_scan = ws_scan_flags(flag, scan, NV, scan_tmp, scan_bytes, s, &R);
+            if (rc_scan) return rc_scan;
+        } else {
+            // tiled ids: per-tile counts + a scan of the counts (k_ws_cid_tiles adds the prefix inside a tile); the `scan` array
+            // (NV ints) holds the 64-bit counts and bases (2 x NV / 256 x 8 bytes).  This form always applies: NV is padded to
+            // whole 16 x 16 tiles, so NV % 256 == 0 and n_tiles >= 1; n_tiles < 2^31 (H < 16 or W < 16 bounds NV by
+            // 2^16 * 16 * 2^15 = 2^35, otherwise NV < 4 N <= 2^38); and ws_scan_temp_bytes(NV) is already the maximum over
+            // this very 64-bit scan of NV / 256 counts, so scan_tmp has room for it.
+            const int64_t n_tiles = NV / 256;
             long long *t_count = (long long *)scan, *t_base = t_count + n_tiles;
             hipLaunchKernelGGL(k_ws_count_tiles, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, (const uint8_t *)flag, n_tiles, t_count);
             size_t tb = scan_bytes;
@@ -1880,9 +1872,6 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
             TF_CHECK_HIP(hipStreamSynchronize(s));
             R = h_last[0] + h_last[1];
             TF_REQUIRE(R <= 0x3fffff00ll, "tf_watershed: more than 2^30 relevant pixels in one call (use time windows)");
-        } else {
-            const int rc_scan = ws_scan_flags(flag, scan, NV, scan_tmp, scan_bytes, s, &R);
-            if (rc_scan) return rc_scan;
         }
     }
     st[6] = R;
@@ -1892,9 +1881,8 @@ static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers
         return TF_ENOMEM;
     }
     if (rv) hipLaunchKernelGGL(k_ws_cid, dim3(nb1), dim3(256), 0, s, cls, flag, scan, N, cid);
-    else if (tiles) hipLaunchKernelGGL(k_ws_cid_tiles, dim3((unsigned)((NV / 256 + 3) / 4)), dim3(256), 0, s, (const uint8_t *)cls, (const uint8_t *)flag,
-                                       (const long long *)((long long *)scan + NV / 256), NV / 256, g, cid);
-    else hipLaunchKernelGGL(k_ws_cid_tiled, grid, block, 0, s, (const uint8_t *)cls, (const uint8_t *)flag, (const int *)scan, g, cid);
+    else hipLaunchKernelGGL(k_ws_cid_tiles, dim3((unsigned)((NV / 256 + 3) / 4)), dim3(256), 0, s, (const uint8_t *)cls, (const uint8_t *)flag,
+                            (const long long *)((long long *)scan + NV / 256), NV / 256, g, cid);
     TF_CHECK_LAUNCH();
     WsC &c = j->c; memset(&c, 0, sizeof(c));
     c.R = R; c.n_nbr = n_nbr;
