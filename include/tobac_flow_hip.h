@@ -1108,6 +1108,56 @@ int tf_download(void *dst_host, const void *src, size_t bytes, void *stream);
 int tf_hash_host(const void *src_host, size_t bytes, uint64_t *hash_out_host);
 int tf_hash_dev(const void *src, size_t bytes, uint64_t *hash_out_host, void *stream);
 
+/* ---- geodesy (version 115) ------------------------------------------------------------------------------------------------
+ * What the reference does with pyproj on the host (abi.py:8-104, geo.py:14-246, utils/geo_utils.py:9-84, nexrad.py:60-77).
+ * Everything is float64 inside; angles of the Earth in degrees, scan angles in radians, lengths in the unit of `a`.  No
+ * atomics: every output is identical from run to run.  Formulas, contract and divergences: DESIGN.md, "Geodesy".
+ *
+ * TfGeos: PROJ's `geos` projection on the ellipsoid (a, rf = inverse flattening, 0 = a sphere) seen from h above the
+ *   equator at lon_0; sweep_y = 0 the GOES convention (sweep "x"), 1 Meteosat's.  lat_0 != 0 is TF_EINVAL, as PROJ refuses
+ *   it.  flags & TF_GEOS_INF: an off-disk ray gives +inf (Proj.__call__) where it otherwise gives NaN (get_abi_lat_lon).
+ * tf_geos_inverse: x (W), y (H) scan angles -> lat, lon (H, W), float64 or float32 (out_dtype TF_F64 / TF_F32: the float64
+ *   result rounded once).  A lane takes four consecutive pixels of the raveled grid and stores 16 bytes at a time where lat
+ *   and lon are 16-byte aligned.  tf_geos_inverse_points: n pairs.
+ * tf_geos_forward: n points (lat, lon) -> scan angles (x, y); beyond the limb (PROJ's visibility test) +inf.  With alt
+ *   (metres, may be NULL) the parallax step of map_nexrad_to_goes runs in the same launch: project, shift lat and lon by
+ *   degrees(alt tan(...) / 6.371e6), project again.
+ * tf_geod_inverse: Geod.inv of n pairs -- az12 (at point 1 towards 2), az21 (at point 2 back towards 1, pyproj's
+ *   convention) in degrees, dist in the unit of a; each output may be NULL.  Vincenty's iteration, at most 24 steps.  NaN
+ *   in: NaN out.  Coincident points: dist 0, (az12, az21) = (180, 0) for lat1 >= 0 and (0, -180) below, as GeographicLib
+ *   gives.  A pair that does not converge (near the antipode) is NaN in all three outputs and counted: *status (device
+ *   uint32, written, not accumulated) is their number.  Workspace: tf_geod_inverse_workspace_bytes(n), TF_ENOMEM below.
+ * tf_grid_spacing: lat, lon (H, W) -> dx, dy (km), area (km2), each may be NULL: the reference's rule (the first pixel of a
+ *   row or column keeps its own raw spacing, an interior one the mean of its two, the last one the previous; a one-pixel
+ *   axis 0).  Every raw spacing is computed once, into the workspace.  NaN propagates as in the reference; *status counts
+ *   the raw spacings that did not converge.
+ * tf_view_angles: one pixel per lane, operations in the reference's order.  scalars (host): TF_VIEW_SZA delta, eqt, hours
+ *   -> out0 = zenith (rad); TF_VIEW_SZA_AZI declination, eqt, hour of day -> out0, out1 = zenith, azimuth (deg);
+ *   TF_VIEW_SATELLITE sat_lat, sat_lon, sat_alt (km) -> out0, out1 = zenith, azimuth (deg); TF_VIEW_ABI_ZENITH lat_0, lon_0
+ *   with x (W) and y (n / W) the grid's scan angles -> out0 (deg).  out1 is NULL for the one-angle modes. */
+#define TF_GEOS_INF 1
+#define TF_VIEW_SZA 0
+#define TF_VIEW_SZA_AZI 1
+#define TF_VIEW_SATELLITE 2
+#define TF_VIEW_ABI_ZENITH 3
+typedef struct TfGeos {
+    double h, lon_0, lat_0, a, rf;
+    int32_t sweep_y, flags;
+} TfGeos;
+int tf_geos_inverse(const TfGeos *geos, const double *x, int64_t W, const double *y, int64_t H, void *lat, void *lon, int out_dtype,
+                    void *stream);
+int tf_geos_inverse_points(const TfGeos *geos, const double *x, const double *y, int64_t n, double *lat, double *lon, void *stream);
+int tf_geos_forward(const TfGeos *geos, const double *lat, const double *lon, const double *alt, int64_t n, double *x, double *y,
+                    void *stream);
+size_t tf_geod_inverse_workspace_bytes(int64_t n);
+int tf_geod_inverse(double a, double rf, const double *lon1, const double *lat1, const double *lon2, const double *lat2, int64_t n,
+                    double *az12, double *az21, double *dist, uint32_t *status, void *ws, size_t ws_bytes, void *stream);
+size_t tf_grid_spacing_workspace_bytes(int64_t H, int64_t W);
+int tf_grid_spacing(double a, double rf, const double *lat, const double *lon, int64_t H, int64_t W, double *dx, double *dy,
+                    double *area, uint32_t *status, void *ws, size_t ws_bytes, void *stream);
+int tf_view_angles(int mode, const double *scalars, int n_scalars, const double *lat, const double *lon, int64_t n, const double *x,
+                   const double *y, int64_t W, double *out0, double *out1, void *stream);
+
 /* tf_copy16: dst = src, 16 bytes per lane per access -- the measured practical HBM ceiling of bench.py's roofline.
  * (Round 5's tf_stream_create_cu_mask / tf_stream_create_priority / tf_stream_destroy / tf_debug_cu_histogram served two
  * scheduling experiments that were not adopted; they live in tools/experiments/stream_experiments.hip now, outside the

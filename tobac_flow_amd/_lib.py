@@ -46,6 +46,16 @@ class BinPoints(ctypes.Structure):
                 ("sum_wv", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class Geos(ctypes.Structure):
+    """TfGeos of include/tobac_flow_hip.h"""
+    _fields_ = [("h", ctypes.c_double), ("lon_0", ctypes.c_double), ("lat_0", ctypes.c_double), ("a", ctypes.c_double),
+                ("rf", ctypes.c_double), ("sweep_y", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+GEOS_INF = 1
+VIEW_SZA, VIEW_SZA_AZI, VIEW_SATELLITE, VIEW_ABI_ZENITH = range(4)
+
+
 class FieldPlane(ctypes.Structure):
     """TfFieldPlane of include/tobac_flow_hip.h"""
     _fields_ = [("data", ctypes.c_void_p), ("frame_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64),
@@ -235,6 +245,14 @@ _PROTOS = {
                                  _P, _c.c_size_t, _P]),
     "tf_window_overlap_pairs": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_double, _P, _c.c_int64, _P, _P,
                                            _c.c_size_t, _P]),
+    "tf_geos_inverse": (_c.c_int, [_c.POINTER(Geos), _P, _c.c_int64, _P, _c.c_int64, _P, _P, _c.c_int, _P]),
+    "tf_geos_inverse_points": (_c.c_int, [_c.POINTER(Geos), _P, _P, _c.c_int64, _P, _P, _P]),
+    "tf_geos_forward": (_c.c_int, [_c.POINTER(Geos), _P, _P, _P, _c.c_int64, _P, _P, _P]),
+    "tf_geod_inverse_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
+    "tf_geod_inverse": (_c.c_int, [_c.c_double, _c.c_double, _P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_grid_spacing_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    "tf_grid_spacing": (_c.c_int, [_c.c_double, _c.c_double, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_view_angles": (_c.c_int, [_c.c_int, _P, _c.c_int, _P, _P, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P]),
     "tf_profile_enable": (_c.c_int, [_c.c_int]),
     "tf_profile_kernel_count": (_c.c_int, []),
     "tf_profile_kernel_name": (_c.c_char_p, [_c.c_int]),

@@ -1,9 +1,10 @@
 """GLM flashes onto the ABI grid on the GPU: the array-level form of tobac_flow/glm.py:77-145 (regrid_glm with
 get_uncorrected_glm_hist / get_corrected_glm_hist).  The reference opens every flash file inside the window of every
 frame and calls np.histogram2d once per frame; here the flashes of all files are binned onto the whole (T, H, W) stack by
-one launch of tf_bin_points (tobac_flow_amd.binning).  Reading the files, the projection to ABI coordinates
-(get_abi_x_y: pyproj) and the parallax correction stay with the caller, who hands in projected x and y: for the
-"corrected" grid, the corrected coordinates.
+one launch of tf_bin_points (tobac_flow_amd.binning).  Reading the files stays with the caller.  The projection to ABI
+coordinates is tobac_flow_amd.abi.get_abi_x_y (tf_geos_forward: device tensors in, device tensors out), whose x and y go
+in here as they are.  The GLM parallax correction (get_glm_parallax_offsets and the lmatools coordinate systems behind it)
+is not taken: for the "corrected" grid the caller hands in corrected coordinates.
 
 The counts equal the reference's bit for bit.  The result feeds tobac_flow_amd.validation (`glm_grid`)."""
 from datetime import datetime, timedelta

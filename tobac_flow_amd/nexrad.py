@@ -2,9 +2,10 @@
 get_site_grids, regrid_nexrad).  Per site and per frame the reference re-masks all gates of the site and makes two
 np.histogram2d calls and one scipy.stats.binned_statistic_dd; here one launch of tf_bin_points (tobac_flow_amd.binning)
 bins the gates of a site onto the whole (T, H, W) stack and gives the raw counts, the counts of valid gates and the sum of
-their reflectivity at once.  Reading the archives (pyart) and the projection with its parallax correction
-(map_nexrad_to_goes: pyproj) stay with the caller, who hands in the projected x and y of every gate.  get_3d_nexrad_hist
-is not taken: nothing in the reference calls it.
+their reflectivity at once.  Reading the archives (pyart) stays with the caller.  The projection of the gates with its
+parallax correction is map_nexrad_to_goes below (tf_geos_forward with the altitudes: one launch, device tensors in,
+device tensors out), whose x and y go into the functions here as they are.  get_3d_nexrad_hist is not taken: nothing in
+the reference calls it.
 
 Counts equal the reference's bit for bit.  The mean is sum / count in double of a sum that differs from SciPy's by the
 summation order only, and may differ in the last bits from run to run.  The counts follow np.histogram2d's
@@ -52,6 +53,17 @@ def _give(stacks, device, squeeze=False):
     lib = _lib()
     stacks = [s[0] if squeeze else s for s in stacks]
     return list(stacks) if device else [lib.to_host(s.contiguous()) for s in stacks]
+
+
+def map_nexrad_to_goes(nexrad_lat, nexrad_lon, nexrad_alt, goes_ds):
+    """nexrad.py:60-77: the scan angles `(x, y)` at which the ABI sees gates at (lat, lon) degrees and `alt` metres up --
+    project, shift latitude and longitude by degrees(alt tan(...) / 6.371e6), project again.  goes_ds: what
+    tobac_flow_amd.abi reads (`.goes_imager_projection`).  NumPy arrays in: NumPy out; device tensors in: one launch of
+    tf_geos_forward, device tensors out.  Gates beyond the limb give +inf (NaN where the shifted position is undefined)."""
+    from tobac_flow_amd.abi import get_abi_proj
+    if not _is_tensor(nexrad_lat) and not _is_tensor(nexrad_lon) and np.size(nexrad_lat) == np.size(nexrad_lon) == 0:
+        return np.array([]), np.array([])
+    return get_abi_proj(goes_ds).forward_points(nexrad_lat, nexrad_lon, nexrad_alt)
 
 
 def get_nexrad_hist(time, alt, x, y, ref, ref_valid, x_bins, y_bins, start_time, end_time, min_alt=2500, max_alt=15000):

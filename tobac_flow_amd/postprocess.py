@@ -305,7 +305,52 @@ def _azimuth_and_speed(lons, lats, t, geod_inv):
     return circmean(np.asarray(azimuths)[keep], high=180, low=-180), np.mean(speeds[keep])
 
 
+def _own_geod_inv(geod_inv):
+    """geod_inv is the `.inv` of the package's own Geod"""
+    from tobac_flow_amd import geo
+    return isinstance(getattr(geod_inv, "__self__", None), geo.Geod) and getattr(geod_inv, "__func__", None) is geo.Geod.inv
+
+
+def _propagation_batched(dataset, step, index_name, parent, geod_inv):
+    """_propagation with ONE inverse call over the consecutive-record pairs of all objects, records sorted by (object, t):
+    on the device where the coordinate columns are device tensors.  Then the circular mean per object, as
+    _azimuth_and_speed takes it."""
+    from scipy.stats import circmean
+    groups, coord = _host(dataset[index_name]), np.asarray(dataset.coords[parent])
+    t = _host(dataset[f"{step}_t"])
+    t = np.asarray(t).astype("datetime64[ns]").view(np.int64) if np.asarray(t).dtype.kind == "M" else np.asarray(t)
+    order = np.lexsort((t, groups))
+    g_sorted = groups[order]
+    pair = np.nonzero((g_sorted[1:] == g_sorted[:-1]) & np.isin(g_sorted[:-1], coord))[0]
+    first, second = order[pair], order[pair + 1]
+    lons, lats = dataset[f"{step}_lon"], dataset[f"{step}_lat"]
+    out = np.full((coord.size, 2), np.nan)
+    if pair.size == 0:
+        return out[:, 0], out[:, 1]
+    if _is_tensor(lons) and _is_tensor(lats):
+        torch = _lib().torch()
+        ia, ib = (torch.from_numpy(np.ascontiguousarray(i)).to(lons.device) for i in (first, second))
+        azimuths, _, distances = geod_inv(lons[ia], lats[ia], lons[ib], lats[ib])
+        azimuths, distances = _host(azimuths), _host(distances)
+    else:
+        lons, lats = _host(lons), _host(lats)
+        azimuths, _, distances = geod_inv(lons[first], lats[first], lons[second], lats[second])
+    seconds = (t[second] - t[first]).astype(np.int64) / 1e9
+    with np.errstate(divide="ignore", invalid="ignore"):
+        speeds = np.asarray(distances) / seconds
+    keep = np.isfinite(azimuths) & np.isfinite(speeds)
+    owner = g_sorted[pair]                                        # non-decreasing
+    bounds = np.searchsorted(owner, coord, side="left"), np.searchsorted(owner, coord, side="right")
+    for k, (b, e) in enumerate(zip(*bounds)):
+        sel = keep[b:e]
+        if sel.any():
+            out[k] = circmean(np.asarray(azimuths)[b:e][sel], high=180, low=-180), np.mean(speeds[b:e][sel])
+    return out[:, 0], out[:, 1]
+
+
 def _propagation(dataset, step, index_name, parent, geod_inv):
+    if _own_geod_inv(geod_inv):
+        return _propagation_batched(dataset, step, index_name, parent, geod_inv)
     groups, coord = _host(dataset[index_name]), np.asarray(dataset.coords[parent])
     lons, lats = _host(dataset[f"{step}_lon"]), _host(dataset[f"{step}_lat"])
     t = _host(dataset[f"{step}_t"])
@@ -418,10 +463,11 @@ def process_core_properties(dataset, time_steps=3, *, geod_inv=None):
     _std, _min, _max, _mean_uncertainty, _mean_combined_error, _min_error and _max_error.  `time_steps` is accepted and
     unused, as in the reference.  A step index is 0 where the reference would yield NaN (utils.stats_utils.idxmin_groupby).
 
-    core_propagation_direction and core_propagation_speed need pyproj's geodesic inverse, which this package does not
-    depend on: pass `geod_inv`, a callable with `pyproj.Geod.inv`'s signature (lons1, lats1, lons2, lats2) ->
-    (azimuths, back azimuths, distances), and they are computed on the host per core after
-    get_mean_object_azimuth_and_speed; with None they are left out.  Returns `dataset`."""
+    core_propagation_direction and core_propagation_speed need a geodesic inverse: pass `geod_inv`, a callable with
+    `pyproj.Geod.inv`'s signature (lons1, lats1, lons2, lats2) -> (azimuths, back azimuths, distances); with None they
+    are left out.  With `tobac_flow_amd.geo.Geod().inv` all consecutive-record pairs of all cores go into ONE inverse call
+    (on the device where the columns are device tensors), followed by the circular mean per core; any other callable is
+    called once per core on the host, after get_mean_object_azimuth_and_speed.  Returns `dataset`."""
     return _object_properties(dataset, "core", "core", _CORE_EXTREMES, _CORE_RATES, geod_inv, "core")
 
 
