@@ -1403,15 +1403,64 @@ void tf_ws_host_pool_release()                                      // tf_shutdo
 #define WSR_FREE(p) ws_pool_free(p)
 #include "ws_replay.h"
 
-// ---- one flood = a JOB in three parts ---------------------------------------------------------------------------------
-//   begin   (device)  classification / compaction, phase A, chain + root phases at increasing depth until the exactness
-//                     check finds no origin whose chains were cut off; with TF_WS_REFERENCE_ORDER and labels that hang on
-//                     the order of equal-valued markers: the tie value, the seed numbers and the sub-graph the replay can
-//                     reach, copied into pinned host memory
+// ---- one flood = a JOB: begin (device), replay (host), finish (device) -------------------------------------------------
+//   begin   (device)  argument checks and workspace carving; classification up to the count of relevant pixels; compaction
+//                     (and the NaN refusal); with TF_WS_REFERENCE_ORDER and a tie value the caller guessed: the EXPORT for
+//                     that value (ws_job_export); then the sweeps (ws_job_sweeps: phase A, the speculative root phase, the
+//                     chain levels below the job's depth) -- unless TF_WS_DEFER_SWEEPS leaves them to tf_watershed_sweeps
 //   replay  (host)    the reference heap's mechanics for the pop ranks -- no HIP call, any thread: the replays of several
 //                     windows run side by side while the device floods the next ones
-//   finish  (device)  pop ranks up, root phase repeated with them, labels written
-// tf_watershed_ex2 and friends run the three back to back; tf_watershed_begin / _replay / _finish expose them.
+//   finish  (device)  what the job's STAGE says is still to do, in the order of the enum, then the labels
+// tf_watershed_ex2 and friends run the three back to back; tf_watershed_begin / _sweeps / _replay / _finish expose them.
+//
+// Two enums carry the state.  WsJobStage: what finish still has to do.  WsRanks: where the pop ranks of the current export come
+// from -- an export (ws_job_export) is made for ONE tie value, either before the sweeps for a guessed value or by the ROOT
+// stage for the value it found; a second export discards the first (ws_job_root).
+//
+//   stage        | event                                                                        | next stage
+//   -------------+------------------------------------------------------------------------------+-------------------------
+//   (begin)      | no relevant pixel                                                            | LABELS
+//   (begin)      | otherwise (after the export on a guess, if one was given)                    | SWEEPS
+//   SWEEPS       | the speculative root phase finds no origin (or max_depth is 1): final         | LABELS
+//   SWEEPS       | otherwise (or TF_WS_SKIP_FAST_PATH): chain levels below the job's depth run   | ROOT
+//   ROOT         | no label hangs on the order of equal-valued markers, or no                   |
+//                |   TF_WS_REFERENCE_ORDER, or the ranks of the export on a guess cover the tie | LABELS
+//   ROOT         | otherwise: export for the tie value found; ranks from the device             | RANKED_ROOT (finish goes on)
+//   ROOT         |   ... ranks from a host replay: finish returns TF_WS_REPLAY_PENDING, the job  |
+//                |   lives on, the caller replays on any thread and enters finish again        | RANKED_ROOT
+//   RANKED_ROOT  | ranks up, root phase repeated with them                                      | LABELS
+//   LABELS       | labels written; finish returns for good                                      | --
+enum WsJobStage {
+    WS_STAGE_SWEEPS,             // phase A, the speculative root phase, the chain levels below the job's depth (ws_job_sweeps)
+    WS_STAGE_ROOT,               // the root phase at the job's depth, deeper while the cut-off leaves ties, and the tie value (ws_job_root)
+    WS_STAGE_RANKED_ROOT,        // the ranks of an export made AFTER the root phase, and the root phase again with them (ws_ranked_root)
+    WS_STAGE_LABELS
+};
+enum WsRanks {
+    WS_RANKS_NONE,               // no export
+    WS_RANKS_DEVICE,             // the small items were one value class: rank_dev filled on the device (k_ws_tie_*), no host replay
+    WS_RANKS_HOST_SPARSE,        // host replay over the small seeds alone: heap position, key, id of each
+    WS_RANKS_HOST_CODED,         // host replay over every seed (dense): 2 bits per seed + the exceptions
+    WS_RANKS_HOST_LIST           // host replay over every seed (dense): the 8-byte heap entries themselves
+};
+static bool ws_ranks_on_host(WsRanks r) { return r >= WS_RANKS_HOST_SPARSE; }
+
+// reference order: the current export and what became of it
+struct WsRef {
+    WsRanks ranks;
+    bool plain;                  // dense forms: replay every item as the reference keeps it (TF_WS_REFERENCE_DENSE=2)
+    bool identity;               // the exported sub-graph is the whole compact set with its own ids (else: ids from subid)
+    bool speculative;            // the export ran before the root phase, for a tie value the caller guessed
+    bool replay_done, applied;   // the host replay has run; the labels ARE the reference's
+    bool has_tie, spec_hit;      // finish found labels that hang on a tie (true_vmax); the guessed value covered it
+    unsigned vmax, true_vmax;    // the tie value exported for / found
+    int64_t M, S, nQ;            // seeds, seeds at or below vmax, pixels of the exported sub-graph
+    u64 code_d; int64_t code_words, n_exc;
+    WsHostBuf hb_val, hb_nbr, hb_rank, hb_sk, hb_sval, hb_sid;
+    int64_t popped; int n_ranked; int replay_rc;
+    double ms_export, ms_replay, ms_detour;
+};
+
 struct tf_ws_job {
     const float *field; const int32_t *markers; const int8_t *mask;
     int64_t T, H, W, N, NV, R;
@@ -1421,35 +1470,68 @@ struct tf_ws_job {
     WsGeom g;
     uint8_t *cls, *flag; int *scan, *cid; char *scan_tmp; size_t scan_bytes;
     int *d_flags; unsigned long long *d_cnt; char *seed_blocks;
-    WsC c; WsQueues Q; int *org, *rank_dev;
+    WsC c; WsQueues Q; int *org, *rank_dev, *subid;
     int h_cnt[WS_BATCH + 8];
-    int depth; int64_t max_sweeps;
-    unsigned long long h_amb[4];
-    int64_t st[TF_WS_NSTATS];
-    // reference order
-    bool need_replay, replay_done, applied, sparse, plain, identity, coded;
-    bool speculative;            // the export ran before the root phase, for a tie value the caller guessed (spec_vmax)
-    bool root_pending;           // finish starts with the root phase (begin has run phase A and the chain levels below `depth`)
-    bool sweeps_pending;         // TF_WS_DEFER_SWEEPS: begin returned after the set-up and the export; phase A and the chain levels are tf_watershed_sweeps' (or finish's)
-    bool speculate_fast; int levels_done;
-    unsigned true_vmax; bool has_tie, spec_hit; int *subid;
-    bool ranked, late_export; double ms_detour;
-    bool device_ranks;           // the small items were one value class: rank_dev filled on the device (k_ws_tie_*), no host replay
-    u64 code_d; int64_t code_words, n_exc;
-    int64_t M, S, nQ; unsigned vmax;
-    WsHostBuf hb_val, hb_nbr, hb_rank, hb_sk, hb_sval, hb_sid;
-    int64_t popped; int n_ranked; int replay_rc;
-    double ms_export, ms_replay;
+    WsJobStage stage;
+    int depth, levels_done; int64_t max_sweeps;
+    bool ranked;                 // rank_dev holds the pop ranks of the current export and the root phase runs with them: root keys are
+                                 // (pop rank << 32) | compact id.  False again from the moment that export is discarded (a ranked root phase follows)
+    unsigned long long h_amb[4]; // the last exactness check: [0] pixels whose label depends on a last-resort tie-break, [1] origins of such
+                                 // ties between equal-valued markers, [2] origins left by the depth cut-off
+    int64_t sweeps_a, sweeps_fast, sweeps_chain[3], processed, root_phases;
+    int probe;                   // the speculative root phase: -1 not run (TF_WS_SKIP_FAST_PATH), else whether it found an origin
+    WsRef ref;
 };
 
 static double ws_now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
-static bool ws_env(const char *name) { return getenv(name) != nullptr; }
+static unsigned ws_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// the slots of stats_host and of tf_watershed_job_info, numbered as include/tobac_flow_hip.h documents them
+enum { WS_ST_SWEEPS_A, WS_ST_SWEEPS_FAST, WS_ST_SWEEPS_CHAIN /* 2 .. 4 */, WS_ST_PROBE = 5, WS_ST_RELEVANT, WS_ST_PROCESSED, WS_ST_DEPTH,
+       WS_ST_AMBIGUOUS, WS_ST_TIE_ORIGINS, WS_ST_DEPTH_ORIGINS, WS_ST_ROOT_PHASES, WS_ST_POPPED, WS_ST_SEEDS, WS_ST_DETOUR_US };
+enum { WS_INFO_FORM, WS_INFO_SEEDS, WS_INFO_SMALL_SEEDS, WS_INFO_SUBGRAPH, WS_INFO_RELEVANT, WS_INFO_EXPORT_US, WS_INFO_REPLAY_US,
+       WS_INFO_TIE_KEY, WS_INFO_GUESSED, WS_INFO_GUESS_COVERED, WS_INFO_EXPORT_KEY, WS_INFO_DEVICE_RANKS };
+static_assert(WS_ST_DETOUR_US + 1 == TF_WS_NSTATS && WS_INFO_DEVICE_RANKS + 1 == 12, "slots as the header numbers them");
+
+// the job's state -> the caller's arrays (either may be null); every entry point reports through here
+static void ws_publish(const tf_ws_job *j, int64_t *st, int64_t *info)
+{
+    const WsRef &r = j->ref;
+    if (st) {
+        st[WS_ST_SWEEPS_A] = j->sweeps_a; st[WS_ST_SWEEPS_FAST] = j->sweeps_fast;
+        for (int i = 0; i < 3; i++) st[WS_ST_SWEEPS_CHAIN + i] = j->sweeps_chain[i];
+        st[WS_ST_PROBE] = j->probe; st[WS_ST_RELEVANT] = j->R; st[WS_ST_PROCESSED] = j->processed;
+        st[WS_ST_DEPTH] = j->depth;
+        st[WS_ST_AMBIGUOUS] = (int64_t)j->h_amb[0]; st[WS_ST_TIE_ORIGINS] = (int64_t)j->h_amb[1]; st[WS_ST_DEPTH_ORIGINS] = (int64_t)j->h_amb[2];
+        st[WS_ST_ROOT_PHASES] = j->root_phases;
+        // the detour: reported once its ranks are in a root phase
+        st[WS_ST_POPPED] = j->ranked ? r.popped : 0;
+        st[WS_ST_SEEDS] = !j->ranked ? 0 : (r.ranks == WS_RANKS_HOST_CODED || r.ranks == WS_RANKS_HOST_LIST) ? r.M : r.S;
+        st[WS_ST_DETOUR_US] = j->ranked ? (int64_t)(r.ms_detour * 1000.0) : 0;
+    }
+    if (info) {
+        info[WS_INFO_FORM] = r.ranks == WS_RANKS_NONE ? 0 : r.ranks == WS_RANKS_DEVICE ? 3 : r.ranks == WS_RANKS_HOST_SPARSE ? 1 : 2;
+        info[WS_INFO_SEEDS] = r.M; info[WS_INFO_SMALL_SEEDS] = r.S; info[WS_INFO_SUBGRAPH] = r.nQ; info[WS_INFO_RELEVANT] = j->R;
+        info[WS_INFO_EXPORT_US] = (int64_t)(r.ms_export * 1000.0);
+        info[WS_INFO_REPLAY_US] = r.replay_done ? (int64_t)(r.ms_replay * 1000.0) : -1;
+        info[WS_INFO_TIE_KEY] = r.has_tie ? (int64_t)r.true_vmax : -1;
+        info[WS_INFO_GUESSED] = r.speculative ? 1 : 0; info[WS_INFO_GUESS_COVERED] = r.spec_hit ? 1 : 0;
+        info[WS_INFO_EXPORT_KEY] = r.ranks != WS_RANKS_NONE ? (int64_t)r.vmax : -1;
+        info[WS_INFO_DEVICE_RANKS] = r.ranks == WS_RANKS_DEVICE ? 1 : 0;
+    }
+}
+
+// the pinned host buffers of the current export go back to the pool
+static void ws_ref_give_buffers(WsRef &r)
+{
+    ws_host_give(r.hb_val); ws_host_give(r.hb_nbr); ws_host_give(r.hb_rank);
+    ws_host_give(r.hb_sk); ws_host_give(r.hb_sval); ws_host_give(r.hb_sid);
+}
 
 static void ws_job_free(tf_ws_job *j)
 {
     if (!j) return;
-    ws_host_give(j->hb_val); ws_host_give(j->hb_nbr); ws_host_give(j->hb_rank);
-    ws_host_give(j->hb_sk); ws_host_give(j->hb_sval); ws_host_give(j->hb_sid);
+    ws_ref_give_buffers(j->ref);
     delete j;
 }
 
@@ -1460,256 +1542,328 @@ static int ws_to_host(void *dst, const void *src, size_t bytes, hipStream_t s)
     TF_CHECK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
     return TF_OK;
 }
-
-// begin, part 2: what the host replay needs (see tf_ws_job)
-static int ws_job_export(tf_ws_job *j)
+static int ws_no_host_memory()
 {
-    const double t_enter = ws_now_ms();
-    j->device_ranks = false;
+    tf_set_error("tf_watershed: out of host memory for the reference-order replay");
+    return TF_ENOMEM;
+}
+
+// ---- the export: what the pop ranks need, for the tie value ref.vmax (ws_job_export at the end calls these in order) -----
+// A/B and test aids, read once per export (the tests toggle them between floods).  Each forces a path the input would not
+// select by itself; the plain form is the tests' reference.
+struct WsExportAids {
+    bool dense;                  // TF_WS_REFERENCE_DENSE: the dense form whatever the seed counts ...
+    bool plain;                  // ... =2: and the plain replay over it
+    bool host;                   // TF_WS_REFERENCE_HOST: the host replay also where the device's closed form applies
+    bool no_codes;               // TF_WS_REFERENCE_NO_CODES: the dense form's seeds as 8-byte entries also where the 2-bit codes fit
+};
+static WsExportAids ws_export_aids()
+{
+    const char *dense = getenv("TF_WS_REFERENCE_DENSE");
+    return WsExportAids{dense != nullptr, dense && atoi(dense) == 2, getenv("TF_WS_REFERENCE_HOST") != nullptr, getenv("TF_WS_REFERENCE_NO_CODES") != nullptr};
+}
+
+// seed numbers: per-block (256 voxels) counts of seeds / small seeds and their 64-bit scans, in seed_blocks; the h_* land
+// with the stream's next synchronise (ws_mark_subgraph)
+struct WsSeedNumbers {
+    int64_t nb256;
+    int *n_seed, *n_small; long long *base_seed, *base_small;
+    int *d_any;                                                         // [0] a seed below the tie value, [1] a floodable pixel below it
+    long long h_base[2]; int h_count[2]; int h_any[2];                  // last block's base + count = the total: [0] seeds (M), [1] small seeds (S)
+};
+static int ws_number_seeds(tf_ws_job *j, WsSeedNumbers &n)
+{
     hipStream_t s = j->s;
-    const WsC &c = j->c;
-    const int64_t R = j->R, N = j->N;
-    const int nn = j->n_nbr;
-    const unsigned nbr_blocks = (unsigned)((R + 255) / 256);
-    // A/B and test aid (read per call: the tests toggle it): TF_WS_REFERENCE_DENSE=1 the dense form whatever the seed counts, =2 the plain form
-    const char *dense_env = getenv("TF_WS_REFERENCE_DENSE");
-    const bool force_dense = dense_env != nullptr;
-    j->plain = dense_env && atoi(dense_env) == 2;
-    // the largest marker value at which the order of equal-valued markers decides a label (the caller's: j->vmax)
-    const unsigned h_vmax = j->vmax;
-    // seed numbers: per-block counts of seeds / small seeds and their 64-bit scans, in the idle flag array
-    const int64_t nb256 = (N + 255) / 256;
+    const int64_t N = j->N;
+    const unsigned h_vmax = j->ref.vmax;
+    const int64_t nb256 = n.nb256 = (N + 255) / 256;
     TF_REQUIRE(nb256 < 0x7fffffffll, "tf_watershed: too many voxels for the seed numbering");
-    int *n_seed = (int *)j->seed_blocks, *n_small = n_seed + nb256;
-    long long *base_seed = (long long *)(((uintptr_t)(n_small + nb256) + 15) & ~(uintptr_t)15), *base_small = base_seed + nb256;
+    n.n_seed = (int *)j->seed_blocks; n.n_small = n.n_seed + nb256;
+    n.base_seed = (long long *)(((uintptr_t)(n.n_small + nb256) + 15) & ~(uintptr_t)15); n.base_small = n.base_seed + nb256;
     size_t need = 0;
     (void)tf_exclusive_sum(nullptr, need, WsCountIter((const int *)nullptr, WsIntToLL()), (long long *)nullptr, (size_t)nb256);
     TF_REQUIRE(need <= j->scan_bytes, "tf_watershed: scan scratch too small for the seed numbering");
-    int *d_any = j->d_flags + WS_BATCH + 6;                             // [0] a seed below the tie value, [1] a floodable pixel below it
-    TF_CHECK_HIP(hipMemsetAsync(d_any, 0, 2 * sizeof(int), s));
-    hipLaunchKernelGGL(k_ws_seed_counts, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, j->field, N, h_vmax, n_seed, n_small, d_any);
+    n.d_any = j->d_flags + WS_BATCH + 6;
+    TF_CHECK_HIP(hipMemsetAsync(n.d_any, 0, 2 * sizeof(int), s));
+    hipLaunchKernelGGL(k_ws_seed_counts, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, j->field, N, h_vmax, n.n_seed, n.n_small, n.d_any);
     TF_CHECK_LAUNCH();
     size_t tb = j->scan_bytes;
-    TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, WsCountIter(n_seed, WsIntToLL()), base_seed, (size_t)nb256, s));
+    TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, WsCountIter(n.n_seed, WsIntToLL()), n.base_seed, (size_t)nb256, s));
     tb = j->scan_bytes;
-    TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, WsCountIter(n_small, WsIntToLL()), base_small, (size_t)nb256, s));
-    long long h_last[4] = {0, 0, 0, 0}; int h_lastc[2] = {0, 0};
-    TF_CHECK_HIP(hipMemcpyAsync(&h_last[0], base_seed + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
-    TF_CHECK_HIP(hipMemcpyAsync(&h_last[1], base_small + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
-    TF_CHECK_HIP(hipMemcpyAsync(&h_lastc[0], n_seed + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    TF_CHECK_HIP(hipMemcpyAsync(&h_lastc[1], n_small + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    // the sub-graph: Q = poppable pixels + their out-neighbours (flags in the idle scan array, ids in subid)
-    uint8_t *in_q = (uint8_t *)j->scan;
-    int *subid = j->subid;
-    TF_CHECK_HIP(hipMemsetAsync(in_q, 0, (size_t)R, s));
-    hipLaunchKernelGGL(k_ws_sub_mark, dim3(nbr_blocks), dim3(256), 0, s, c, h_vmax, in_q, d_any + 1);
-    TF_CHECK_LAUNCH();
-    int h_any[2] = {0, 0};
-    TF_CHECK_HIP(hipMemcpyAsync(h_any, d_any, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    int64_t nQ = 0;
-    {
-        const int rc = ws_scan_flags(in_q, subid, R, j->scan_tmp, j->scan_bytes, s, &nQ);       // synchronises
-        if (rc) return rc;
-    }
-    j->M = h_last[0] + h_lastc[0]; j->S = h_last[1] + h_lastc[1];
-    {
-        // ONE VALUE CLASS?  Then the pop ranks have a closed form and are computed here, on the device (k_ws_tie_*).
-        const bool force_host = ws_env("TF_WS_REFERENCE_HOST");                          // A/B and test aid (read per call: the tests toggle it)
-        const int64_t S = j->S;
-        char *tie_base = (char *)j->scan + tf_align_up((size_t)R, 256);
-        const size_t tie_room = (size_t)j->NV * 4 > tf_align_up((size_t)R, 256) ? (size_t)j->NV * 4 - tf_align_up((size_t)R, 256) : 0;
-        const size_t tie_need = tf_align_up((size_t)S * 8, 256) + 5 * tf_align_up((size_t)S * 4, 256) + 256;
-        if (!force_host && !force_dense && !h_any[0] && !h_any[1] && S > 0 && S <= R && S < 0x3fffffffll && tie_need <= tie_room) {
-            long long *stg_k = (long long *)c.Rt; unsigned *stg_val = (unsigned *)c.Llo; int *stg_id = c.Lhi;
-            hipLaunchKernelGGL(k_ws_small_list, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, h_vmax,
-                               (const long long *)base_seed, (const long long *)base_small, (const int *)nullptr, stg_k, stg_val, stg_id);
-            TF_CHECK_LAUNCH();
-            long long k_max = 0;
-            TF_CHECK_HIP(hipMemcpyAsync(&k_max, stg_k + S - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            if (k_max < j->M - S) {                                     // no small seed among the last S positions: every replacement item is large
-                TfArena ta(tie_base, tie_room);
-                WsTie t;
-                t.k = stg_k; t.sid = stg_id; t.S = (int)S; t.M = j->M;
-                t.pos = ta.take<long long>(S); t.tj = ta.take<int>(S); t.c0 = ta.take<int>(S); t.c1 = ta.take<int>(S);
-                t.size = ta.take<int>(S); t.pre = ta.take<int>(S); t.n_nodes = ta.take<int>(4);
-                if (ta.ok()) {
-                    const long long h_pos0 = 0; const int h_init[2] = {1, 0};      // node 0 = the root, taken by the first small seed; pre-order index 0
-                    TF_CHECK_HIP(hipMemcpyAsync(t.pos, &h_pos0, sizeof(long long), hipMemcpyHostToDevice, s));
-                    TF_CHECK_HIP(hipMemsetAsync(t.tj, 0, sizeof(int), s));
-                    TF_CHECK_HIP(hipMemsetAsync(t.pre, 0, sizeof(int), s));
-                    TF_CHECK_HIP(hipMemcpyAsync(t.n_nodes, h_init, sizeof(int), hipMemcpyHostToDevice, s));
-                    int offs[80]; int n_lev = 0, lo = 0, hi = 1;
-                    offs[0] = 0;
-                    while (hi > lo && n_lev < 78) {
-                        hipLaunchKernelGGL(k_ws_tie_level, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, s, t, lo, hi);
-                        TF_CHECK_LAUNCH();
-                        int h_n = 0;
-                        TF_CHECK_HIP(hipMemcpyAsync(&h_n, t.n_nodes, sizeof(int), hipMemcpyDeviceToHost, s));
-                        TF_CHECK_HIP(hipStreamSynchronize(s));
-                        offs[++n_lev] = hi;
-                        lo = hi; hi = h_n < (int)S ? h_n : (int)S;
-                        if (h_n > (int)S) { lo = hi = -1; break; }      // (cannot happen: every seed takes exactly one node)
-                    }
-                    if (hi == (int)S && lo == hi) {                     // every small seed has its node
-                        for (int l = n_lev - 1; l >= 0; l--)
-                            hipLaunchKernelGGL(k_ws_tie_sizes, dim3((unsigned)((offs[l + 1] - offs[l] + 255) / 256)), dim3(256), 0, s, t, offs[l], offs[l + 1]);
-                        for (int l = 0; l < n_lev; l++)
-                            hipLaunchKernelGGL(k_ws_tie_pre, dim3((unsigned)((offs[l + 1] - offs[l] + 255) / 256)), dim3(256), 0, s, t, offs[l], offs[l + 1]);
-                        hipLaunchKernelGGL(k_ws_tie_default_ranks, dim3(nbr_blocks), dim3(256), 0, s, R, (int)S, j->rank_dev);
-                        hipLaunchKernelGGL(k_ws_tie_scatter, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, t, j->rank_dev);
-                        TF_CHECK_LAUNCH();
-                        TF_CHECK_HIP(hipStreamSynchronize(s));
-                        j->device_ranks = true;
-                        j->need_replay = false;
-                        j->popped = S; j->n_ranked = (int)S;
-                        j->ms_export = ws_now_ms() - t_enter;
-                        return TF_OK;
-                    }
-                }
-            }
-        }
-    }
-    // compact export if the translated rows fit the staging room (the two idle frontier queues), else the whole compact
-    // set with its own ids
-    j->identity = nQ * nn > 2 * R + 64;
-    if (j->identity) nQ = R;
-    j->nQ = nQ;
-    // the small seeds are staged in Rt / Llo / Lhi (idle until the root phase is repeated): R entries each
-    j->sparse = !force_dense && j->S <= R;
-    j->hb_val = ws_host_take((size_t)nQ * sizeof(unsigned), true);
-    j->hb_nbr = ws_host_take((size_t)nQ * nn * sizeof(int), true);
-    j->hb_rank = ws_host_take((size_t)nQ * sizeof(int), true);
-    // sparse: heap position, key, id of the small seeds (the dense form takes its buffers below)
-    if (j->sparse) {
-        j->hb_sk = ws_host_take((size_t)j->S * sizeof(long long), true);
-        j->hb_sval = ws_host_take((size_t)j->S * sizeof(unsigned), true); j->hb_sid = ws_host_take((size_t)j->S * sizeof(int), true);
-    }
-    if (!j->hb_val.p || !j->hb_nbr.p || !j->hb_rank.p || (j->sparse && (!j->hb_sk.p || !j->hb_sval.p || !j->hb_sid.p))) {
-        tf_set_error("tf_watershed: out of host memory for the reference-order replay");
-        return TF_ENOMEM;
-    }
-    if (j->identity) {
-        if (ws_to_host(j->hb_val.p, c.val, (size_t)R * sizeof(unsigned), s) || ws_to_host(j->hb_nbr.p, c.nbr, (size_t)R * nn * sizeof(int), s)) return TF_EHIP;
-    } else {
-        unsigned *stg_val = (unsigned *)j->Q.q[0]; int *stg_nbr = j->Q.q[1];
-        hipLaunchKernelGGL(k_ws_sub_export, dim3(nbr_blocks), dim3(256), 0, s, c, h_vmax, (const uint8_t *)in_q, (const int *)subid, stg_val, stg_nbr);
-        TF_CHECK_LAUNCH();
-        if (ws_to_host(j->hb_val.p, stg_val, (size_t)nQ * sizeof(unsigned), s) || ws_to_host(j->hb_nbr.p, stg_nbr, (size_t)nQ * nn * sizeof(int), s)) return TF_EHIP;
-    }
-    const int *subid_or_null = j->identity ? nullptr : subid;
-    if (j->sparse) {
-        long long *stg_k = (long long *)c.Rt; unsigned *stg_val = (unsigned *)c.Llo; int *stg_id = c.Lhi;
-        hipLaunchKernelGGL(k_ws_small_list, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, h_vmax,
-                           (const long long *)base_seed, (const long long *)base_small, subid_or_null, stg_k, stg_val, stg_id);
-        TF_CHECK_LAUNCH();
-        if (ws_to_host(j->hb_sk.p, stg_k, (size_t)j->S * sizeof(long long), s) || ws_to_host(j->hb_sval.p, stg_val, (size_t)j->S * sizeof(unsigned), s) ||
-            ws_to_host(j->hb_sid.p, stg_id, (size_t)j->S * sizeof(int), s)) return TF_EHIP;
-        TF_CHECK_HIP(hipStreamSynchronize(s));
-    } else {
-        // DENSE form: every seed has to be in the replay's heap (more small seeds than staging room, or TF_WS_REFERENCE_DENSE).
-        TF_CHECK_HIP(hipStreamSynchronize(s));                          // the sub-graph has left the queues
-        // 2 bits per seed + the exceptions (k_ws_seed_codes) if the two bitmaps fit a frontier queue ...
-        const int64_t W = (j->M + 31) / 32 + 8;                         // words per bitmap
-        j->coded = 2 * W <= 2 * R + 64 && !ws_env("TF_WS_REFERENCE_NO_CODES");
-        if (j->coded) {
-            u64 *d_sample = (u64 *)j->Q.q[1];
-            hipLaunchKernelGGL(k_ws_entry_sample, dim3(1), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, h_vmax, d_sample);
-            TF_CHECK_LAUNCH();
-            u64 h_sample[256];
-            TF_CHECK_HIP(hipMemcpyAsync(h_sample, d_sample, sizeof(h_sample), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            u64 D = 0ull; int best = 0;
-            for (int a = 0; a < 256; a++) {
-                if (!h_sample[a]) continue;
-                int cnt = 0;
-                for (int b = 0; b < 256; b++) cnt += h_sample[b] == h_sample[a];
-                if (cnt > best) { best = cnt; D = h_sample[a]; }
-            }
-            j->code_d = D;
-            int *n_exc = n_small; long long *base_exc = base_small;      // (the small-seed counts have served)
-            hipLaunchKernelGGL(k_ws_code_counts, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, h_vmax, D, n_exc);
-            TF_CHECK_LAUNCH();
-            tb = j->scan_bytes;
-            TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, WsCountIter(n_exc, WsIntToLL()), base_exc, (size_t)nb256, s));
-            long long h_e = 0; int h_ec = 0;
-            TF_CHECK_HIP(hipMemcpyAsync(&h_e, base_exc + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipMemcpyAsync(&h_ec, n_exc + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            const int64_t E = h_e + h_ec;
-            j->code_words = W; j->n_exc = E;
-            j->hb_sval = ws_host_take((size_t)2 * W * sizeof(unsigned), true);
-            j->hb_sid = ws_host_take((size_t)(E > 0 ? E : 1) * sizeof(u64), true);
-            j->hb_sk = ws_host_take((size_t)(j->M + nQ + 1) * sizeof(u64), false);       // the heap itself: plain memory, filled by the replay
-            if (!j->hb_sval.p || !j->hb_sid.p || !j->hb_sk.p) { tf_set_error("tf_watershed: out of host memory for the reference-order replay"); return TF_ENOMEM; }
-            unsigned *d_bits = (unsigned *)j->Q.q[0];
-            TF_CHECK_HIP(hipMemsetAsync(d_bits, 0, (size_t)2 * W * sizeof(unsigned), s));
-            const int64_t cap = R + 32;
-            bool first = true;
-            for (int64_t c0 = 0; first || c0 < E; c0 += cap, first = false) {
-                const int64_t cnt = E - c0 < cap ? E - c0 : cap;
-                u64 *stg = (u64 *)j->Q.q[1];
-                hipLaunchKernelGGL(k_ws_seed_codes, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, h_vmax, D,
-                                   (const long long *)base_seed, (const long long *)base_exc, subid_or_null, first ? 1 : 0, d_bits, d_bits + W, c0, cap, stg);
-                TF_CHECK_LAUNCH();
-                if (cnt > 0 && ws_to_host((u64 *)j->hb_sid.p + c0, stg, (size_t)cnt * sizeof(u64), s)) return TF_EHIP;
-                if (first && ws_to_host(j->hb_sval.p, d_bits, (size_t)2 * W * sizeof(unsigned), s)) return TF_EHIP;
-                TF_CHECK_HIP(hipStreamSynchronize(s));                  // (the staging queue is written again by the next chunk)
-            }
-        } else {
-            // ... else as the 8-byte heap entries themselves, through the two frontier queues in turn, R entries at a time
-            j->hb_sk = ws_host_take((size_t)(j->M + nQ + 1) * sizeof(u64), true);
-            if (!j->hb_sk.p) { tf_set_error("tf_watershed: out of host memory for the reference-order replay"); return TF_ENOMEM; }
-            const int64_t cap = R + 32;
-            int turn = 0;
-            for (int64_t c0 = 0; c0 < j->M; c0 += cap, turn ^= 1) {
-                const int64_t cnt = j->M - c0 < cap ? j->M - c0 : cap;
-                u64 *stg = (u64 *)j->Q.q[turn];
-                hipLaunchKernelGGL(k_ws_seed_list, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N,
-                                   (const long long *)base_seed, c0, cap, subid_or_null, h_vmax, stg);
-                TF_CHECK_LAUNCH();
-                if (ws_to_host((u64 *)j->hb_sk.p + c0, stg, (size_t)cnt * sizeof(u64), s)) return TF_EHIP;
-                if (turn) TF_CHECK_HIP(hipStreamSynchronize(s));        // (the stream orders kernel k + 2 after copy k anyway; bound the queue of copies)
-            }
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-        }
-    }
-    j->need_replay = true;
-    j->ms_export = ws_now_ms() - t_enter;
+    TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, WsCountIter(n.n_small, WsIntToLL()), n.base_small, (size_t)nb256, s));
+    n.h_base[0] = n.h_base[1] = 0; n.h_count[0] = n.h_count[1] = 0; n.h_any[0] = n.h_any[1] = 0;
+    TF_CHECK_HIP(hipMemcpyAsync(&n.h_base[0], n.base_seed + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipMemcpyAsync(&n.h_base[1], n.base_small + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipMemcpyAsync(&n.h_count[0], n.n_seed + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipMemcpyAsync(&n.h_count[1], n.n_small + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
     return TF_OK;
 }
+
+// the sub-graph the replay can reach: Q = poppable pixels + their out-neighbours (flags in the idle scan array, ids in
+// subid).  Synchronises: the seed numbers are on the host afterwards.
+static int ws_mark_subgraph(tf_ws_job *j, WsSeedNumbers &n, int64_t *nQ)
+{
+    hipStream_t s = j->s;
+    uint8_t *in_q = (uint8_t *)j->scan;
+    TF_CHECK_HIP(hipMemsetAsync(in_q, 0, (size_t)j->R, s));
+    hipLaunchKernelGGL(k_ws_sub_mark, dim3(ws_blocks(j->R)), dim3(256), 0, s, j->c, j->ref.vmax, in_q, n.d_any + 1);
+    TF_CHECK_LAUNCH();
+    TF_CHECK_HIP(hipMemcpyAsync(n.h_any, n.d_any, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    return ws_scan_flags(in_q, j->subid, j->R, j->scan_tmp, j->scan_bytes, s, nQ);       // synchronises
+}
+
+// ONE VALUE CLASS?  Then the pop ranks have a closed form and are computed here, on the device (k_ws_tie_*): *done, and
+// rank_dev is filled.  Not applicable (*done stays false) when a smaller item exists, a small seed sits among the last S heap
+// positions, or the idle part of the scan array has no room for the tree.
+static int ws_try_device_ranks(tf_ws_job *j, const WsSeedNumbers &n, bool *done)
+{
+    hipStream_t s = j->s;
+    const WsC &c = j->c;
+    WsRef &r = j->ref;
+    const int64_t R = j->R, S = r.S;
+    char *tie_base = (char *)j->scan + tf_align_up((size_t)R, 256);     // (behind the sub-graph's flags)
+    const size_t tie_room = (size_t)j->NV * 4 > tf_align_up((size_t)R, 256) ? (size_t)j->NV * 4 - tf_align_up((size_t)R, 256) : 0;
+    const size_t tie_need = tf_align_up((size_t)S * 8, 256) + 5 * tf_align_up((size_t)S * 4, 256) + 256;
+    if (n.h_any[0] || n.h_any[1] || S <= 0 || S > R || S >= 0x3fffffffll || tie_need > tie_room) return TF_OK;
+    // the small seeds are staged in Rt / Llo / Lhi (idle until the root phase is repeated): R entries each
+    long long *stg_k = (long long *)c.Rt; unsigned *stg_val = (unsigned *)c.Llo; int *stg_id = c.Lhi;
+    hipLaunchKernelGGL(k_ws_small_list, dim3((unsigned)n.nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, j->N, r.vmax,
+                       (const long long *)n.base_seed, (const long long *)n.base_small, (const int *)nullptr, stg_k, stg_val, stg_id);
+    TF_CHECK_LAUNCH();
+    long long k_max = 0;
+    TF_CHECK_HIP(hipMemcpyAsync(&k_max, stg_k + S - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    if (k_max >= r.M - S) return TF_OK;                                 // a small seed among the last S positions: a replacement item could be small
+    TfArena ta(tie_base, tie_room);
+    WsTie t;
+    t.k = stg_k; t.sid = stg_id; t.S = (int)S; t.M = r.M;
+    t.pos = ta.take<long long>(S); t.tj = ta.take<int>(S); t.c0 = ta.take<int>(S); t.c1 = ta.take<int>(S);
+    t.size = ta.take<int>(S); t.pre = ta.take<int>(S); t.n_nodes = ta.take<int>(4);
+    if (!ta.ok()) return TF_OK;
+    const long long h_pos0 = 0; const int h_init[2] = {1, 0};           // node 0 = the root, taken by the first small seed; pre-order index 0
+    TF_CHECK_HIP(hipMemcpyAsync(t.pos, &h_pos0, sizeof(long long), hipMemcpyHostToDevice, s));
+    TF_CHECK_HIP(hipMemsetAsync(t.tj, 0, sizeof(int), s));
+    TF_CHECK_HIP(hipMemsetAsync(t.pre, 0, sizeof(int), s));
+    TF_CHECK_HIP(hipMemcpyAsync(t.n_nodes, h_init, sizeof(int), hipMemcpyHostToDevice, s));
+    int offs[80]; int n_lev = 0, lo = 0, hi = 1;
+    offs[0] = 0;
+    while (hi > lo && n_lev < 78) {
+        hipLaunchKernelGGL(k_ws_tie_level, dim3(ws_blocks(hi - lo)), dim3(256), 0, s, t, lo, hi);
+        TF_CHECK_LAUNCH();
+        int h_n = 0;
+        TF_CHECK_HIP(hipMemcpyAsync(&h_n, t.n_nodes, sizeof(int), hipMemcpyDeviceToHost, s));
+        TF_CHECK_HIP(hipStreamSynchronize(s));
+        offs[++n_lev] = hi;
+        lo = hi; hi = h_n < (int)S ? h_n : (int)S;
+        if (h_n > (int)S) { lo = hi = -1; break; }                      // (cannot happen: every seed takes exactly one node)
+    }
+    if (!(hi == (int)S && lo == hi)) return TF_OK;                      // not every small seed has its node
+    for (int l = n_lev - 1; l >= 0; l--)
+        hipLaunchKernelGGL(k_ws_tie_sizes, dim3(ws_blocks(offs[l + 1] - offs[l])), dim3(256), 0, s, t, offs[l], offs[l + 1]);
+    for (int l = 0; l < n_lev; l++)
+        hipLaunchKernelGGL(k_ws_tie_pre, dim3(ws_blocks(offs[l + 1] - offs[l])), dim3(256), 0, s, t, offs[l], offs[l + 1]);
+    hipLaunchKernelGGL(k_ws_tie_default_ranks, dim3(ws_blocks(R)), dim3(256), 0, s, R, (int)S, j->rank_dev);
+    hipLaunchKernelGGL(k_ws_tie_scatter, dim3(ws_blocks(S)), dim3(256), 0, s, t, j->rank_dev);
+    TF_CHECK_LAUNCH();
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    r.popped = S; r.n_ranked = (int)S;
+    r.ranks = WS_RANKS_DEVICE;
+    *done = true;
+    return TF_OK;
+}
+
+// the sub-graph to the host: compact (translated rows, staged in the two idle frontier queues) if they fit that room, else
+// the whole compact set with its own ids (identity)
+static int ws_export_subgraph(tf_ws_job *j, int64_t nQ)
+{
+    hipStream_t s = j->s;
+    const WsC &c = j->c;
+    WsRef &r = j->ref;
+    const int64_t R = j->R;
+    const int nn = j->n_nbr;
+    r.identity = nQ * nn > 2 * R + 64;
+    if (r.identity) nQ = R;
+    r.nQ = nQ;
+    r.hb_val = ws_host_take((size_t)nQ * sizeof(unsigned), true);
+    r.hb_nbr = ws_host_take((size_t)nQ * nn * sizeof(int), true);
+    r.hb_rank = ws_host_take((size_t)nQ * sizeof(int), true);
+    if (!r.hb_val.p || !r.hb_nbr.p || !r.hb_rank.p) return ws_no_host_memory();
+    if (r.identity) {
+        if (ws_to_host(r.hb_val.p, c.val, (size_t)R * sizeof(unsigned), s) || ws_to_host(r.hb_nbr.p, c.nbr, (size_t)R * nn * sizeof(int), s)) return TF_EHIP;
+    } else {
+        unsigned *stg_val = (unsigned *)j->Q.q[0]; int *stg_nbr = j->Q.q[1];
+        hipLaunchKernelGGL(k_ws_sub_export, dim3(ws_blocks(R)), dim3(256), 0, s, c, r.vmax, (const uint8_t *)j->scan, (const int *)j->subid, stg_val, stg_nbr);
+        TF_CHECK_LAUNCH();
+        if (ws_to_host(r.hb_val.p, stg_val, (size_t)nQ * sizeof(unsigned), s) || ws_to_host(r.hb_nbr.p, stg_nbr, (size_t)nQ * nn * sizeof(int), s)) return TF_EHIP;
+    }
+    return TF_OK;
+}
+
+// the seeds, SPARSE: heap position, key, id of the small seeds, staged in Rt / Llo / Lhi (idle until the root phase is
+// repeated): R entries each, so S <= R
+static int ws_export_seeds_sparse(tf_ws_job *j, const WsSeedNumbers &n)
+{
+    hipStream_t s = j->s;
+    const WsC &c = j->c;
+    WsRef &r = j->ref;
+    r.hb_sk = ws_host_take((size_t)r.S * sizeof(long long), true);
+    r.hb_sval = ws_host_take((size_t)r.S * sizeof(unsigned), true); r.hb_sid = ws_host_take((size_t)r.S * sizeof(int), true);
+    if (!r.hb_sk.p || !r.hb_sval.p || !r.hb_sid.p) return ws_no_host_memory();
+    long long *stg_k = (long long *)c.Rt; unsigned *stg_val = (unsigned *)c.Llo; int *stg_id = c.Lhi;
+    hipLaunchKernelGGL(k_ws_small_list, dim3((unsigned)n.nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, j->N, r.vmax,
+                       (const long long *)n.base_seed, (const long long *)n.base_small, r.identity ? (const int *)nullptr : (const int *)j->subid, stg_k, stg_val, stg_id);
+    TF_CHECK_LAUNCH();
+    if (ws_to_host(r.hb_sk.p, stg_k, (size_t)r.S * sizeof(long long), s) || ws_to_host(r.hb_sval.p, stg_val, (size_t)r.S * sizeof(unsigned), s) ||
+        ws_to_host(r.hb_sid.p, stg_id, (size_t)r.S * sizeof(int), s)) return TF_EHIP;
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    r.ranks = WS_RANKS_HOST_SPARSE;
+    return TF_OK;
+}
+
+// the seeds, DENSE and CODED: 2 bits per seed + the exceptions (k_ws_seed_codes); the two bitmaps of W words each fit one
+// frontier queue.  The sub-graph has left the queues (the caller has synchronised).
+static int ws_export_seeds_coded(tf_ws_job *j, const WsSeedNumbers &n, int64_t W)
+{
+    hipStream_t s = j->s;
+    WsRef &r = j->ref;
+    const int64_t R = j->R, N = j->N, nb256 = n.nb256;
+    const int *subid_or_null = r.identity ? nullptr : j->subid;
+    u64 *d_sample = (u64 *)j->Q.q[1];
+    hipLaunchKernelGGL(k_ws_entry_sample, dim3(1), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, r.vmax, d_sample);
+    TF_CHECK_LAUNCH();
+    u64 h_sample[256];
+    TF_CHECK_HIP(hipMemcpyAsync(h_sample, d_sample, sizeof(h_sample), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    u64 D = 0ull; int best = 0;
+    for (int a = 0; a < 256; a++) {
+        if (!h_sample[a]) continue;
+        int cnt = 0;
+        for (int b = 0; b < 256; b++) cnt += h_sample[b] == h_sample[a];
+        if (cnt > best) { best = cnt; D = h_sample[a]; }
+    }
+    r.code_d = D;
+    int *n_exc = n.n_small; long long *base_exc = n.base_small;         // (the small-seed counts have served)
+    hipLaunchKernelGGL(k_ws_code_counts, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, r.vmax, D, n_exc);
+    TF_CHECK_LAUNCH();
+    size_t tb = j->scan_bytes;
+    TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, WsCountIter(n_exc, WsIntToLL()), base_exc, (size_t)nb256, s));
+    long long h_e = 0; int h_ec = 0;
+    TF_CHECK_HIP(hipMemcpyAsync(&h_e, base_exc + nb256 - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipMemcpyAsync(&h_ec, n_exc + nb256 - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    const int64_t E = h_e + h_ec;
+    r.code_words = W; r.n_exc = E;
+    r.hb_sval = ws_host_take((size_t)2 * W * sizeof(unsigned), true);
+    r.hb_sid = ws_host_take((size_t)(E > 0 ? E : 1) * sizeof(u64), true);
+    r.hb_sk = ws_host_take((size_t)(r.M + r.nQ + 1) * sizeof(u64), false);             // the heap itself: plain memory, filled by the replay
+    if (!r.hb_sval.p || !r.hb_sid.p || !r.hb_sk.p) return ws_no_host_memory();
+    unsigned *d_bits = (unsigned *)j->Q.q[0];
+    TF_CHECK_HIP(hipMemsetAsync(d_bits, 0, (size_t)2 * W * sizeof(unsigned), s));
+    const int64_t cap = R + 32;
+    bool first = true;
+    for (int64_t c0 = 0; first || c0 < E; c0 += cap, first = false) {
+        const int64_t cnt = E - c0 < cap ? E - c0 : cap;
+        u64 *stg = (u64 *)j->Q.q[1];
+        hipLaunchKernelGGL(k_ws_seed_codes, dim3((unsigned)nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, N, r.vmax, D,
+                           (const long long *)n.base_seed, (const long long *)base_exc, subid_or_null, first ? 1 : 0, d_bits, d_bits + W, c0, cap, stg);
+        TF_CHECK_LAUNCH();
+        if (cnt > 0 && ws_to_host((u64 *)r.hb_sid.p + c0, stg, (size_t)cnt * sizeof(u64), s)) return TF_EHIP;
+        if (first && ws_to_host(r.hb_sval.p, d_bits, (size_t)2 * W * sizeof(unsigned), s)) return TF_EHIP;
+        TF_CHECK_HIP(hipStreamSynchronize(s));                          // (the staging queue is written again by the next chunk)
+    }
+    r.ranks = WS_RANKS_HOST_CODED;
+    return TF_OK;
+}
+
+// the seeds, DENSE as a LIST: the 8-byte heap entries themselves, through the two frontier queues in turn, R entries at a
+// time.  The sub-graph has left the queues (the caller has synchronised).
+static int ws_export_seeds_list(tf_ws_job *j, const WsSeedNumbers &n)
+{
+    hipStream_t s = j->s;
+    WsRef &r = j->ref;
+    r.hb_sk = ws_host_take((size_t)(r.M + r.nQ + 1) * sizeof(u64), true);
+    if (!r.hb_sk.p) return ws_no_host_memory();
+    const int64_t cap = j->R + 32;
+    int turn = 0;
+    for (int64_t c0 = 0; c0 < r.M; c0 += cap, turn ^= 1) {
+        const int64_t cnt = r.M - c0 < cap ? r.M - c0 : cap;
+        u64 *stg = (u64 *)j->Q.q[turn];
+        hipLaunchKernelGGL(k_ws_seed_list, dim3((unsigned)n.nb256), dim3(256), 0, s, (const uint8_t *)j->cls, (const int *)j->cid, j->field, j->N,
+                           (const long long *)n.base_seed, c0, cap, r.identity ? (const int *)nullptr : (const int *)j->subid, r.vmax, stg);
+        TF_CHECK_LAUNCH();
+        if (ws_to_host((u64 *)r.hb_sk.p + c0, stg, (size_t)cnt * sizeof(u64), s)) return TF_EHIP;
+        if (turn) TF_CHECK_HIP(hipStreamSynchronize(s));                // (the stream orders kernel k + 2 after copy k anyway; bound the queue of copies)
+    }
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    r.ranks = WS_RANKS_HOST_LIST;
+    return TF_OK;
+}
+
+// The export for the tie value ref.vmax (the caller's: the largest marker value at which the order of equal-valued markers
+// decides a label, found by the ROOT stage or guessed): pop ranks on the device where they have a closed form, else the
+// sub-graph and the seeds to pinned host memory for the replay.  ref.ranks says which.
+static int ws_job_export(tf_ws_job *j)
+{
+    const double t_enter = ws_now_ms();
+    WsRef &r = j->ref;
+    const WsExportAids aids = ws_export_aids();
+    r.ranks = WS_RANKS_NONE;
+    r.plain = aids.plain;
+    WsSeedNumbers n;
+    int64_t nQ = 0;
+    int rc = ws_number_seeds(j, n);
+    if (!rc) rc = ws_mark_subgraph(j, n, &nQ);
+    if (rc) return rc;
+    r.M = n.h_base[0] + n.h_count[0]; r.S = n.h_base[1] + n.h_count[1];
+    bool done = false;
+    if (!aids.host && !aids.dense) rc = ws_try_device_ranks(j, n, &done);
+    if (!rc && !done) rc = ws_export_subgraph(j, nQ);
+    if (!rc && !done) {
+        if (!aids.dense && r.S <= j->R) rc = ws_export_seeds_sparse(j, n);
+        else {
+            // DENSE: every seed has to be in the replay's heap (more small seeds than staging room, or TF_WS_REFERENCE_DENSE)
+            TF_CHECK_HIP(hipStreamSynchronize(j->s));                   // the sub-graph has left the queues
+            const int64_t W = (r.M + 31) / 32 + 8;                      // words per bitmap
+            rc = (2 * W <= 2 * j->R + 64 && !aids.no_codes) ? ws_export_seeds_coded(j, n, W) : ws_export_seeds_list(j, n);
+        }
+    }
+    r.ms_export = ws_now_ms() - t_enter;
+    return rc;
+}
+
+// ---- the sweeps ----------------------------------------------------------------------------------------------------------
+static int64_t &ws_chain_sweeps(tf_ws_job *j, int k) { return j->sweeps_chain[k < 3 ? k - 1 : 2]; }     // of chain level k, or of a root phase at depth k
 
 // chain levels C_{levels_done + 1} .. C_{depth - 1} (final once computed)
 static int ws_chain_levels(tf_ws_job *j)
 {
-    const unsigned nbr_blocks = (unsigned)((j->R + 255) / 256);
     for (int k = j->levels_done + 1; k < j->depth; k++) {
-        hipLaunchKernelGGL(k_ws_init_level, dim3(nbr_blocks), dim3(256), 0, j->s, j->c.pix, j->c.C[k], j->R, 0, (const int *)nullptr);
+        hipLaunchKernelGGL(k_ws_init_level, dim3(ws_blocks(j->R)), dim3(256), 0, j->s, j->c.pix, j->c.C[k], j->R, 0, (const int *)nullptr);
         TF_CHECK_LAUNCH();
         int64_t sw = 0;
         const int rc = ws_run_phase(j->c, k, j->depth_max + 1, j->Q, j->s, j->max_sweeps, &sw);      // k < "depth": a chain level
         if (rc) return rc;
-        j->st[2 + (k < 3 ? k - 1 : 2)] += sw;
+        ws_chain_sweeps(j, k) += sw;
         j->levels_done = k;
     }
     return TF_OK;
 }
 
-// the root phase at the job's depth (root keys: raster indices, or pop ranks from rank_dev) + the exactness check -> h_amb
-static int ws_root_and_check(tf_ws_job *j, bool ranked)
+// the root phase at the job's depth (root keys: raster indices, or pop ranks from rank_dev if `ranked`) + the exactness check -> h_amb
+static int ws_root_and_check(tf_ws_job *j)
 {
     hipStream_t s = j->s;
     const WsC &c = j->c;
     const int64_t R = j->R;
-    const unsigned nbr_blocks = (unsigned)((R + 255) / 256);
-    hipLaunchKernelGGL(k_ws_init_level, dim3(nbr_blocks), dim3(256), 0, s, c.pix, c.Rt, R, 1, ranked ? (const int *)j->rank_dev : (const int *)nullptr);
+    const unsigned nbr_blocks = ws_blocks(R);
+    hipLaunchKernelGGL(k_ws_init_level, dim3(nbr_blocks), dim3(256), 0, s, c.pix, c.Rt, R, 1, j->ranked ? (const int *)j->rank_dev : (const int *)nullptr);
     hipLaunchKernelGGL(k_ws_init_labelset, dim3(nbr_blocks), dim3(256), 0, s, c.pix, j->markers, c.Llo, c.Lhi, R);
     TF_CHECK_LAUNCH();
     int64_t sw = 0;
     const int rc = ws_run_phase(c, j->depth, j->depth, j->Q, s, j->max_sweeps, &sw);              // k == depth: the root phase
     if (rc) return rc;
-    if (j->speculate_fast && j->depth == 1) j->st[1] = sw; else j->st[2 + (j->depth < 3 ? j->depth - 1 : 2)] += sw;
-    j->st[12] += 1;
+    if (j->probe >= 0 && j->depth == 1) j->sweeps_fast = sw; else ws_chain_sweeps(j, j->depth) += sw;
+    j->root_phases += 1;
     TF_CHECK_HIP(hipMemsetAsync(j->org, 0, (size_t)R * sizeof(int), s));
     TF_CHECK_HIP(hipMemsetAsync(j->d_cnt, 0, 4 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_ws_origins, dim3(nbr_blocks), dim3(256), 0, s, c, j->depth, j->org);
@@ -1720,19 +1874,17 @@ static int ws_root_and_check(tf_ws_job *j, bool ranked)
     return TF_OK;
 }
 
-// begin, part 3: phase A, the edge masks, the speculative root phase or the chain levels below the job's depth.  Part of
+// stage SWEEPS: phase A, the edge masks, the speculative root phase or the chain levels below the job's depth.  Part of
 // tf_watershed_begin unless the caller asked for TF_WS_DEFER_SWEEPS: it then runs them through tf_watershed_sweeps (or leaves
 // them to finish) -- none of it reads the flow fields, the seeds' set-up of the NEXT window can run first, and the host replay
 // of an export on a guessed tie value is under way meanwhile.
 static int ws_job_sweeps(tf_ws_job *j)
 {
-    if (!j->sweeps_pending) return TF_OK;
-    j->sweeps_pending = false;
-    int64_t *st = j->st;
+    if (j->stage != WS_STAGE_SWEEPS) return TF_OK;
     const WsC &c = j->c;
     hipStream_t s = j->s;
-    const unsigned nbr_blocks = (unsigned)((j->R + 255) / 256);
-    int rc = ws_run_phase(c, 0, j->depth_max, j->Q, s, j->max_sweeps, &st[0], 29.0 * (double)j->N);
+    const unsigned nbr_blocks = ws_blocks(j->R);
+    int rc = ws_run_phase(c, 0, j->depth_max, j->Q, s, j->max_sweeps, &j->sweeps_a, 29.0 * (double)j->N);
     if (rc) return rc;
     {
         TfProfScope ps(TFK_WS_RELAX, 0.0, s);                                      // M1 from the final K2: work the sweeps used to do
@@ -1747,394 +1899,419 @@ static int ws_job_sweeps(tf_ws_job *j)
     // Speculative start: a root phase on K2 alone (depth 1).  If its exactness check finds no origin at all the
     // labelling cannot depend on any tie-break and is final (tie-free fields).  The caller's hint skips it for
     // inputs known to contain exact plateaus: the labels are the same either way, only the work differs.
-    j->speculate_fast = !((j->flags & TF_WS_SKIP_FAST_PATH) && j->depth0 > 1);
-    st[5] = j->speculate_fast ? 0 : -1;
+    const bool speculate_fast = !((j->flags & TF_WS_SKIP_FAST_PATH) && j->depth0 > 1);
+    j->probe = speculate_fast ? 0 : -1;
     j->depth = j->depth0;
-    j->root_pending = true;
-    if (j->speculate_fast) {
+    j->stage = WS_STAGE_ROOT;
+    if (speculate_fast) {
         j->depth = 1;
-        rc = ws_root_and_check(j, false);
+        rc = ws_root_and_check(j);
         if (rc) return rc;
-        st[5] = j->h_amb[2] != 0;
-        if (j->h_amb[2] == 0 || j->depth_max <= 1) j->root_pending = false;        // final (at depth 1 every origin counts as cut off)
+        j->probe = j->h_amb[2] != 0;
+        if (j->h_amb[2] == 0 || j->depth_max <= 1) j->stage = WS_STAGE_LABELS;     // final (at depth 1 every origin counts as cut off)
         else j->depth = j->depth0;
     }
-    if (j->root_pending) {
-        rc = ws_chain_levels(j);                                                    // C_1 .. C_{depth - 1}; the root phase is finish's
-        if (rc) return rc;
-    }
-    st[8] = j->depth; st[9] = (int64_t)j->h_amb[0]; st[10] = (int64_t)j->h_amb[1]; st[11] = (int64_t)j->h_amb[2];
+    if (j->stage == WS_STAGE_ROOT) return ws_chain_levels(j);                      // C_1 .. C_{depth - 1}; the root phase is finish's
     return TF_OK;
 }
 
-// `rv` != nullptr: the raveled form (tf_watershed_raveled): `field` = image, `markers` = `labels` = output (in place),
-// seeds = rv_locs; T, H, W, fwd, bwd, nbr_host unused.
-static int ws_job_begin(tf_ws_job *j, const float *field, const int32_t *markers, const int8_t *mask,
-                        const float *fwd, const float *bwd, int64_t T, int64_t H, int64_t W,
-                        const int8_t *nbr_host, int n_nbr, int depth0, int depth_max, int flags,
-                        void *ws, size_t ws_bytes, void *stream,
-                        const WsRavel *rv = nullptr, const int64_t *rv_locs = nullptr, int64_t rv_n_locs = 0, int64_t spec_key = -1)
+// ---- begin ---------------------------------------------------------------------------------------------------------------
+// what the entry points hand to begin.  `rv` != nullptr: the raveled form (tf_watershed_raveled): `field` = image, `markers`
+// = `labels` = output (in place), seeds = rv_locs; T, H, W, fwd, bwd, nbr_host unused.
+struct WsArgs {
+    const float *field; const int32_t *markers; const int8_t *mask; const float *fwd, *bwd;
+    int64_t T, H, W;
+    const int8_t *nbr_host; int n_nbr, depth0, depth_max, flags;
+    void *ws; size_t ws_bytes; void *stream;
+    const WsRavel *rv; const int64_t *rv_locs; int64_t rv_n_locs;
+    int64_t spec_key;            // the caller's guess of the tie value (ordered key), or -1
+};
+static const dim3 ws_block_2d(64, 4, 1);
+static dim3 ws_grid_2d(const tf_ws_job *j) { return j->raveled ? dim3(1, 1, 1) : dim3((j->g.W + 63) / 64, (j->g.H + 3) / 4, (unsigned)j->T); }
+
+// begin, part 1: argument checks, the job's geometry, the arrays over the whole volume carved from the workspace
+static int ws_begin_carve(tf_ws_job *j, const WsArgs &a, TfArena &ar)
 {
-    int64_t *st = j->st;
-    for (int i = 0; i < TF_WS_NSTATS; i++) st[i] = 0;
-    TF_REQUIRE((flags & ~(TF_WS_SKIP_FAST_PATH | TF_WS_REFERENCE_ORDER | TF_WS_DEFER_SWEEPS)) == 0, "tf_watershed: unknown flag");
-    TF_REQUIRE(field && markers && ws, "tf_watershed: null pointer");
+    const WsRavel *rv = a.rv;
+    const int64_t T = a.T, H = a.H, W = a.W;
+    TF_REQUIRE((a.flags & ~(TF_WS_SKIP_FAST_PATH | TF_WS_REFERENCE_ORDER | TF_WS_DEFER_SWEEPS)) == 0, "tf_watershed: unknown flag");
+    TF_REQUIRE(a.field && a.markers && a.ws, "tf_watershed: null pointer");
     if (!rv) {
-        TF_REQUIRE(fwd && bwd && nbr_host, "tf_watershed: null pointer");
+        TF_REQUIRE(a.fwd && a.bwd && a.nbr_host, "tf_watershed: null pointer");
         TF_REQUIRE(T > 0 && H > 0 && W > 0 && H < (1 << 15) && W < (1 << 15) && T < 65536, "tf_watershed: bad shape");
         // the set-up reads a flow vector as one float2 (the four-pixel relevance pass: as float4 where it finds 16 bytes)
-        TF_REQUIRE((uintptr_t)fwd % 8 == 0 && (uintptr_t)bwd % 8 == 0, "tf_watershed: fwd and bwd must be 8-byte aligned");
-        TF_REQUIRE((uintptr_t)field % 4 == 0 && (uintptr_t)markers % 4 == 0, "tf_watershed: field and markers must be 4-byte aligned");
+        TF_REQUIRE((uintptr_t)a.fwd % 8 == 0 && (uintptr_t)a.bwd % 8 == 0, "tf_watershed: fwd and bwd must be 8-byte aligned");
+        TF_REQUIRE((uintptr_t)a.field % 4 == 0 && (uintptr_t)a.markers % 4 == 0, "tf_watershed: field and markers must be 4-byte aligned");
     }
-    TF_REQUIRE(n_nbr > 0 && n_nbr <= WS_MAX_NBR, "tf_watershed: bad neighbour count");
-    TF_REQUIRE(depth0 >= 1 && depth0 <= depth_max && depth_max <= WS_MAX_DEPTH, "tf_watershed: bad chain_depth");
+    TF_REQUIRE(a.n_nbr > 0 && a.n_nbr <= WS_MAX_NBR, "tf_watershed: bad neighbour count");
+    TF_REQUIRE(a.depth0 >= 1 && a.depth0 <= a.depth_max && a.depth_max <= WS_MAX_DEPTH, "tf_watershed: bad chain_depth");
     const int64_t N = rv ? rv->n : T * H * W;
     // the raveled twin addresses voxels through int32 strides like the reference; the (T, H, W) entry points index in
     // 64 bits and are bounded by memory (and by 2^30 RELEVANT pixels, checked after the scan)
     TF_REQUIRE(N > 0 && (rv ? N <= 0x7fffffffll : N <= (1ll << 36)), "tf_watershed: too many voxels per call (use time windows)");
     const int64_t NV = rv ? N : ws_virtual_voxels(T, H, W);           // scan positions (tile order pads edge tiles)
-    if (ws_bytes < ws_full_bytes(N, NV) + ws_compact_bytes(1, n_nbr, depth_max)) { tf_set_error("tf_watershed: workspace too small"); return TF_ENOMEM; }
-    hipStream_t s = (hipStream_t)stream;
+    if (a.ws_bytes < ws_full_bytes(N, NV) + ws_compact_bytes(1, a.n_nbr, a.depth_max)) { tf_set_error("tf_watershed: workspace too small"); return TF_ENOMEM; }
     WsGeom &g = j->g;
-    g.T = T; g.H = (int)H; g.W = (int)W; g.plane = H * W; g.n_nbr = n_nbr; g.n_tx = (int)((W + WS_TILE - 1) / WS_TILE);
-    for (int i = 0; i < n_nbr && !rv; i++) {
-        g.dt[i] = nbr_host[i * 3]; g.dy[i] = nbr_host[i * 3 + 1]; g.dx[i] = nbr_host[i * 3 + 2];
+    g.T = T; g.H = (int)H; g.W = (int)W; g.plane = H * W; g.n_nbr = a.n_nbr; g.n_tx = (int)((W + WS_TILE - 1) / WS_TILE);
+    for (int i = 0; i < a.n_nbr && !rv; i++) {
+        g.dt[i] = a.nbr_host[i * 3]; g.dy[i] = a.nbr_host[i * 3 + 1]; g.dx[i] = a.nbr_host[i * 3 + 2];
         TF_REQUIRE(abs(g.dt[i]) <= 1 && abs(g.dy[i]) <= 1 && abs(g.dx[i]) <= 1, "tf_watershed: neighbour offset out of range");
     }
-    j->field = field; j->markers = markers; j->mask = mask; j->T = T; j->H = H; j->W = W; j->N = N; j->NV = NV;
-    j->n_nbr = n_nbr; j->depth0 = depth0; j->depth_max = depth_max; j->flags = flags; j->s = s; j->raveled = rv != nullptr;
-    TfArena ar(ws, ws_bytes);
-    uint8_t *cls = ar.take<uint8_t>(N), *flag = ar.take<uint8_t>(NV);
-    int *scan = ar.take<int>(NV), *cid = ar.take<int>(N);
-    const size_t scan_bytes = ws_scan_temp_bytes(NV);
-    char *scan_tmp = ar.take<char>(scan_bytes ? scan_bytes : 1);
-    int *d_flags = ar.take<int>(WS_BATCH + 8);
-    unsigned long long *d_cnt = ar.take<unsigned long long>(4);
+    j->field = a.field; j->markers = a.markers; j->mask = a.mask; j->T = T; j->H = H; j->W = W; j->N = N; j->NV = NV;
+    j->n_nbr = a.n_nbr; j->depth0 = a.depth0; j->depth_max = a.depth_max; j->flags = a.flags; j->s = (hipStream_t)a.stream; j->raveled = rv != nullptr;
+    j->cls = ar.take<uint8_t>(N); j->flag = ar.take<uint8_t>(NV);
+    j->scan = ar.take<int>(NV); j->cid = ar.take<int>(N);
+    j->scan_bytes = ws_scan_temp_bytes(NV);
+    j->scan_tmp = ar.take<char>(j->scan_bytes ? j->scan_bytes : 1);
+    j->d_flags = ar.take<int>(WS_BATCH + 8);
+    j->d_cnt = ar.take<unsigned long long>(4);
     j->seed_blocks = ar.take<char>((size_t)((N + 255) / 256) * 24 + 64);
     if (!ar.ok()) { tf_set_error("tf_watershed: workspace too small"); return TF_ENOMEM; }
-    j->cls = cls; j->flag = flag; j->scan = scan; j->cid = cid; j->scan_tmp = scan_tmp; j->scan_bytes = scan_bytes;
-    j->d_flags = d_flags; j->d_cnt = d_cnt;
+    return TF_OK;
+}
 
-    dim3 block(64, 4, 1), grid(rv ? 1 : (g.W + 63) / 64, rv ? 1 : (g.H + 3) / 4, rv ? 1 : (unsigned)T);
-    const unsigned nb1 = (unsigned)((N + 255) / 256);
+// begin, part 2: classification and the relevance pass, up to the count of relevant pixels R
+static int ws_begin_relevant(tf_ws_job *j, const WsArgs &a)
+{
+    const WsRavel *rv = a.rv;
+    hipStream_t s = j->s;
+    const WsGeom &g = j->g;
+    const int64_t T = j->T, H = j->H, W = j->W, N = j->N, NV = j->NV;
+    const int n_nbr = j->n_nbr;
+    const float *fwd = a.fwd, *bwd = a.bwd;
+    const int32_t *markers = j->markers; const int8_t *mask = j->mask;
+    uint8_t *cls = j->cls, *flag = j->flag;
+    const dim3 block = ws_block_2d, grid = ws_grid_2d(j);
+    const unsigned nb1 = ws_blocks(N);
     int64_t R = 0;
-    {
-        TfProfScope ps(TFK_WS_SETUP, 29.0 * (double)N, s);
-        if (rv) {
-            // `flag` doubles as the seed bitmap until the relevance pass overwrites it (cls is final by then)
-            int *d_bad = d_flags + WS_BATCH + 5;
-            TF_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-            TF_CHECK_HIP(hipMemsetAsync(flag, 0, (size_t)N, s));
-            if (rv_n_locs > 0)
-                hipLaunchKernelGGL(k_wsr_seeds, dim3((unsigned)((rv_n_locs + 255) / 256)), dim3(256), 0, s, rv_locs, rv_n_locs, N, flag, d_bad);
-            hipLaunchKernelGGL(k_wsr_classify, dim3(nb1), dim3(256), 0, s, (const uint8_t *)flag, markers, mask, N, cls, d_bad);
-            TF_CHECK_LAUNCH();
-            int h_bad = 0;
-            TF_CHECK_HIP(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            TF_REQUIRE(h_bad != 1, "tf_watershed_raveled: marker_locations must be strictly ascending indices into the arrays (np.flatnonzero order)");
-            TF_REQUIRE(h_bad != 2, "tf_watershed_raveled: output must be non-zero at every marker location (_watershed.pyx:241-244)");
-            hipLaunchKernelGGL(k_wsr_relevant, dim3(nb1), dim3(256), 0, s, (const uint8_t *)cls, *rv, flag);
-        } else {
-            if ((uintptr_t)markers % 16 == 0 && (uintptr_t)cls % 4 == 0 && (!mask || (uintptr_t)mask % 4 == 0))
-                hipLaunchKernelGGL(k_ws_classify4, dim3((unsigned)(((N + 3) / 4 + 255) / 256)), dim3(256), 0, s, markers, mask, N, cls);
-            else hipLaunchKernelGGL(k_ws_classify, dim3(nb1), dim3(256), 0, s, markers, mask, N, cls);
-            if (NV > N) TF_CHECK_HIP(hipMemsetAsync(flag, 0, (size_t)NV, s));   // padding positions of the edge tiles
-            bool faces = n_nbr == 6;                        // the six face neighbours, in any order?
-            for (int i = 0; faces && i < 6; i++) faces = abs(g.dt[i]) + abs(g.dy[i]) + abs(g.dx[i]) == 1;
-            for (int i = 0; faces && i < 6; i++) for (int k = 0; k < i; k++) faces = faces && !(g.dt[i] == g.dt[k] && g.dy[i] == g.dy[k] && g.dx[i] == g.dx[k]);
-            if (faces && W % 4 == 0 && (uintptr_t)cls % 4 == 0 && (uintptr_t)flag % 4 == 0 && (uintptr_t)fwd % 16 == 0 && (uintptr_t)bwd % 16 == 0)
-                hipLaunchKernelGGL(k_ws_relevant6x4, dim3((unsigned)((W / 4 + 63) / 64), (unsigned)((H + 3) / 4), (unsigned)T), block, 0, s,
-                                   (const uint8_t *)cls, fwd, bwd, g, flag);
-            else if (n_nbr == 6) hipLaunchKernelGGL(k_ws_relevant<6>, grid, block, 0, s, cls, fwd, bwd, g, flag);
-            else if (n_nbr == 18) hipLaunchKernelGGL(k_ws_relevant<18>, grid, block, 0, s, cls, fwd, bwd, g, flag);
-            else if (n_nbr == 26) hipLaunchKernelGGL(k_ws_relevant<26>, grid, block, 0, s, cls, fwd, bwd, g, flag);
-            else hipLaunchKernelGGL(k_ws_relevant<0>, grid, block, 0, s, cls, fwd, bwd, g, flag);
-        }
+    TfProfScope ps(TFK_WS_SETUP, 29.0 * (double)N, s);
+    if (rv) {
+        // `flag` doubles as the seed bitmap until the relevance pass overwrites it (cls is final by then)
+        int *d_bad = j->d_flags + WS_BATCH + 5;
+        TF_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        TF_CHECK_HIP(hipMemsetAsync(flag, 0, (size_t)N, s));
+        if (a.rv_n_locs > 0)
+            hipLaunchKernelGGL(k_wsr_seeds, dim3(ws_blocks(a.rv_n_locs)), dim3(256), 0, s, a.rv_locs, a.rv_n_locs, N, flag, d_bad);
+        hipLaunchKernelGGL(k_wsr_classify, dim3(nb1), dim3(256), 0, s, (const uint8_t *)flag, markers, mask, N, cls, d_bad);
         TF_CHECK_LAUNCH();
-        if (rv) {
-            const int rc_scan = ws_scan_flags(flag, scan, NV, scan_tmp, scan_bytes, s, &R);
-            if (rc_scan) return rc_scan;
-        } else {
-            // tiled ids: per-tile counts + a scan of the counts (k_ws_cid_tiles adds the prefix inside a tile); the `scan` array
-            // (NV ints) holds the 64-bit counts and bases (2 x NV / 256 x 8 bytes).  This form always applies: NV is padded to
-            // whole 16 x 16 tiles, so NV % 256 == 0 and n_tiles >= 1; n_tiles < 2^31 (H < 16 or W < 16 bounds NV by
-            // 2^16 * 16 * 2^15 = 2^35, otherwise NV < 4 N <= 2^38); and ws_scan_temp_bytes(NV) is already the maximum over
-            // this very 64-bit scan of NV / 256 counts, so scan_tmp has room for it.
-            const int64_t n_tiles = NV / 256;
-            long long *t_count = (long long *)scan, *t_base = t_count + n_tiles;
-            hipLaunchKernelGGL(k_ws_count_tiles, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, (const uint8_t *)flag, n_tiles, t_count);
-            size_t tb = scan_bytes;
-            TF_CHECK_HIP(tf_exclusive_sum(scan_tmp, tb, (const long long *)t_count, t_base, (size_t)n_tiles, s));
-            long long h_last[2] = {0, 0};
-            TF_CHECK_HIP(hipMemcpyAsync(&h_last[0], t_base + n_tiles - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipMemcpyAsync(&h_last[1], t_count + n_tiles - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            R = h_last[0] + h_last[1];
-            TF_REQUIRE(R <= 0x3fffff00ll, "tf_watershed: more than 2^30 relevant pixels in one call (use time windows)");
-        }
+        int h_bad = 0;
+        TF_CHECK_HIP(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        TF_CHECK_HIP(hipStreamSynchronize(s));
+        TF_REQUIRE(h_bad != 1, "tf_watershed_raveled: marker_locations must be strictly ascending indices into the arrays (np.flatnonzero order)");
+        TF_REQUIRE(h_bad != 2, "tf_watershed_raveled: output must be non-zero at every marker location (_watershed.pyx:241-244)");
+        hipLaunchKernelGGL(k_wsr_relevant, dim3(nb1), dim3(256), 0, s, (const uint8_t *)cls, *rv, flag);
+    } else {
+        if ((uintptr_t)markers % 16 == 0 && (uintptr_t)cls % 4 == 0 && (!mask || (uintptr_t)mask % 4 == 0))
+            hipLaunchKernelGGL(k_ws_classify4, dim3((unsigned)(((N + 3) / 4 + 255) / 256)), dim3(256), 0, s, markers, mask, N, cls);
+        else hipLaunchKernelGGL(k_ws_classify, dim3(nb1), dim3(256), 0, s, markers, mask, N, cls);
+        if (NV > N) TF_CHECK_HIP(hipMemsetAsync(flag, 0, (size_t)NV, s));   // padding positions of the edge tiles
+        bool faces = n_nbr == 6;                        // the six face neighbours, in any order?
+        for (int i = 0; faces && i < 6; i++) faces = abs(g.dt[i]) + abs(g.dy[i]) + abs(g.dx[i]) == 1;
+        for (int i = 0; faces && i < 6; i++) for (int k = 0; k < i; k++) faces = faces && !(g.dt[i] == g.dt[k] && g.dy[i] == g.dy[k] && g.dx[i] == g.dx[k]);
+        if (faces && W % 4 == 0 && (uintptr_t)cls % 4 == 0 && (uintptr_t)flag % 4 == 0 && (uintptr_t)fwd % 16 == 0 && (uintptr_t)bwd % 16 == 0)
+            hipLaunchKernelGGL(k_ws_relevant6x4, dim3((unsigned)((W / 4 + 63) / 64), (unsigned)((H + 3) / 4), (unsigned)T), block, 0, s,
+                               (const uint8_t *)cls, fwd, bwd, g, flag);
+        else if (n_nbr == 6) hipLaunchKernelGGL(k_ws_relevant<6>, grid, block, 0, s, cls, fwd, bwd, g, flag);
+        else if (n_nbr == 18) hipLaunchKernelGGL(k_ws_relevant<18>, grid, block, 0, s, cls, fwd, bwd, g, flag);
+        else if (n_nbr == 26) hipLaunchKernelGGL(k_ws_relevant<26>, grid, block, 0, s, cls, fwd, bwd, g, flag);
+        else hipLaunchKernelGGL(k_ws_relevant<0>, grid, block, 0, s, cls, fwd, bwd, g, flag);
     }
-    st[6] = R;
+    TF_CHECK_LAUNCH();
+    if (rv) {
+        const int rc_scan = ws_scan_flags(flag, j->scan, NV, j->scan_tmp, j->scan_bytes, s, &R);
+        if (rc_scan) return rc_scan;
+    } else {
+        // tiled ids: per-tile counts + a scan of the counts (k_ws_cid_tiles adds the prefix inside a tile); the `scan` array
+        // (NV ints) holds the 64-bit counts and bases (2 x NV / 256 x 8 bytes).  This form always applies: NV is padded to
+        // whole 16 x 16 tiles, so NV % 256 == 0 and n_tiles >= 1; n_tiles < 2^31 (H < 16 or W < 16 bounds NV by
+        // 2^16 * 16 * 2^15 = 2^35, otherwise NV < 4 N <= 2^38); and ws_scan_temp_bytes(NV) is already the maximum over
+        // this very 64-bit scan of NV / 256 counts, so scan_tmp has room for it.
+        const int64_t n_tiles = NV / 256;
+        long long *t_count = (long long *)j->scan, *t_base = t_count + n_tiles;
+        hipLaunchKernelGGL(k_ws_count_tiles, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, (const uint8_t *)flag, n_tiles, t_count);
+        size_t tb = j->scan_bytes;
+        TF_CHECK_HIP(tf_exclusive_sum(j->scan_tmp, tb, (const long long *)t_count, t_base, (size_t)n_tiles, s));
+        long long h_tiles[2] = {0, 0};
+        TF_CHECK_HIP(hipMemcpyAsync(&h_tiles[0], t_base + n_tiles - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
+        TF_CHECK_HIP(hipMemcpyAsync(&h_tiles[1], t_count + n_tiles - 1, sizeof(long long), hipMemcpyDeviceToHost, s));
+        TF_CHECK_HIP(hipStreamSynchronize(s));
+        R = h_tiles[0] + h_tiles[1];
+        TF_REQUIRE(R <= 0x3fffff00ll, "tf_watershed: more than 2^30 relevant pixels in one call (use time windows)");
+    }
     j->R = R;
-    if (ws_bytes < ws_full_bytes(N, NV) + ws_compact_bytes(R > 0 ? R : 1, n_nbr, depth_max)) {
+    return TF_OK;
+}
+
+// begin, part 3: compact ids, the compact arrays carved for R pixels, compaction, the NaN refusal
+static int ws_begin_compact(tf_ws_job *j, const WsArgs &a, TfArena &ar)
+{
+    const WsRavel *rv = a.rv;
+    hipStream_t s = j->s;
+    const WsGeom &g = j->g;
+    const int64_t N = j->N, NV = j->NV, R = j->R;
+    const int n_nbr = j->n_nbr, depth_max = j->depth_max;
+    const float *field = j->field, *fwd = a.fwd, *bwd = a.bwd;
+    int *cid = j->cid;
+    const dim3 block = ws_block_2d, grid = ws_grid_2d(j);
+    const unsigned nb1 = ws_blocks(N);
+    if (a.ws_bytes < ws_full_bytes(N, NV) + ws_compact_bytes(R > 0 ? R : 1, n_nbr, depth_max)) {
         tf_set_error("tf_watershed: workspace too small for %lld relevant pixels", (long long)R);
         return TF_ENOMEM;
     }
-    if (rv) hipLaunchKernelGGL(k_ws_cid, dim3(nb1), dim3(256), 0, s, cls, flag, scan, N, cid);
-    else hipLaunchKernelGGL(k_ws_cid_tiles, dim3((unsigned)((NV / 256 + 3) / 4)), dim3(256), 0, s, (const uint8_t *)cls, (const uint8_t *)flag,
-                            (const long long *)((long long *)scan + NV / 256), NV / 256, g, cid);
+    if (rv) hipLaunchKernelGGL(k_ws_cid, dim3(nb1), dim3(256), 0, s, j->cls, j->flag, j->scan, N, cid);
+    else hipLaunchKernelGGL(k_ws_cid_tiles, dim3((unsigned)((NV / 256 + 3) / 4)), dim3(256), 0, s, (const uint8_t *)j->cls, (const uint8_t *)j->flag,
+                            (const long long *)((long long *)j->scan + NV / 256), NV / 256, g, cid);
     TF_CHECK_LAUNCH();
     WsC &c = j->c; memset(&c, 0, sizeof(c));
     c.R = R; c.n_nbr = n_nbr;
     j->org = nullptr; j->rank_dev = nullptr;
     j->depth = 0;
-    if (R > 0) {
-        u64 *pix = ar.take<u64>(R); unsigned *val = ar.take<unsigned>(R); int *nbr = ar.take<int>(R * n_nbr);
-        c.pix = pix; c.val = val; c.nbr = nbr;
-        c.K2 = ar.take<u64>(R); c.M1 = ar.take<u64>(R);
-        for (int k = 1; k < depth_max; k++) c.C[k] = ar.take<u64>(R);
-        c.Rt = ar.take<u64>(R);
-        c.Llo = ar.take<int>(R); c.Lhi = ar.take<int>(R); j->org = ar.take<int>(R);
-        j->rank_dev = ar.take<int>(R);
-        u64 *emask = ar.take<u64>(R);
-        c.emask = emask;
-        WsQueues &Q = j->Q;
-        Q.qcap = (int)(2 * R < 0x7fffff00ll ? 2 * R : 0x7fffff00ll);
-        Q.q[0] = ar.take<int>(2 * R + 64); Q.q[1] = ar.take<int>(2 * R + 64);
-        j->subid = ar.take<int>(R);
-        Q.cnt = d_flags; Q.h_cnt = j->h_cnt; Q.processed = &st[7];
-        if (!ar.ok()) { tf_set_error("tf_watershed: workspace too small"); return TF_ENOMEM; }
-        int *d_nan = d_flags + WS_BATCH + 4;
-        TF_CHECK_HIP(hipMemsetAsync(d_nan, 0, sizeof(int), s));
-        {
-            TfProfScope ps(TFK_WS_SETUP, 0.0, s);
-            if (rv) hipLaunchKernelGGL(k_wsr_compact, dim3(nb1), dim3(256), 0, s, field, (const int *)cid, *rv, pix, val, nbr, c.K2, c.M1, d_nan);
-            else if (n_nbr == 6) hipLaunchKernelGGL(k_ws_compact<6>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
-            else if (n_nbr == 18) hipLaunchKernelGGL(k_ws_compact<18>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
-            else if (n_nbr == 26) hipLaunchKernelGGL(k_ws_compact<26>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
-            else hipLaunchKernelGGL(k_ws_compact<0>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
-        }
-        TF_CHECK_LAUNCH();
-        {   // the reference's `smaller()` (_watershed.pyx:161-164) is not an order on NaN: its heap then pops in an order
-            // that depends on the array state, and no closed form exists.  Refuse instead of returning something else.
-            int h_nan = 0;
-            TF_CHECK_HIP(hipMemcpyAsync(&h_nan, d_nan, sizeof(int), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            if (h_nan) {
-                tf_set_error("tf_watershed: the field is NaN at a floodable pixel or at a seed next to one; the pop order of the "
-                             "reference's heap is undefined for NaN keys (detection.get_combined_edge_field maps NaN to +inf)");
-                return TF_EINVAL;
-            }
-        }
-        // a front advances at least one pixel per sweep, so a phase needs at most "longest flood path" sweeps: bounded by
-        // T + H + W times a detour factor on a (T, H, W) grid; the raveled form knows no shape, there the only safe bound
-        // is the number of relevant pixels itself (a snake-shaped mask floods one pixel per sweep)
-        const int64_t max_sweeps = rv ? 4096 + 2 * R : 4096 + 512 * (T + H + W);
-        j->max_sweeps = max_sweeps;
-        if ((flags & TF_WS_REFERENCE_ORDER) && spec_key >= 0) {
-            // SPECULATIVE EXPORT (round 4).  The replay needs nothing the relaxation phases compute -- seeds, keys and the
-            // neighbour table exist now -- except the tie value, and any value at or above the true one gives the ranks of
-            // every marker that can matter.  With the caller's guess (the previous window's tie value) the export happens
-            // here, the host replay runs beside phase A and the chain phases, and finish runs ONE root phase, with the pop
-            // ranks; it checks the guess against the tie value it then finds and falls back on the export-after-the-root-phase
-            // order if the guess was too low.
-            j->vmax = (unsigned)spec_key;
-            j->speculative = true;
-            const int rc_x = ws_job_export(j);
-            if (rc_x) return rc_x;
-        }
-        j->sweeps_pending = true;
-        if (flags & TF_WS_DEFER_SWEEPS) return TF_OK;                               // phase A and the chain levels: tf_watershed_sweeps / finish
-        return ws_job_sweeps(j);
+    if (R == 0) return TF_OK;
+    u64 *pix = ar.take<u64>(R); unsigned *val = ar.take<unsigned>(R); int *nbr = ar.take<int>(R * n_nbr);
+    c.pix = pix; c.val = val; c.nbr = nbr;
+    c.K2 = ar.take<u64>(R); c.M1 = ar.take<u64>(R);
+    for (int k = 1; k < depth_max; k++) c.C[k] = ar.take<u64>(R);
+    c.Rt = ar.take<u64>(R);
+    c.Llo = ar.take<int>(R); c.Lhi = ar.take<int>(R); j->org = ar.take<int>(R);
+    j->rank_dev = ar.take<int>(R);
+    c.emask = ar.take<u64>(R);
+    WsQueues &Q = j->Q;
+    Q.qcap = (int)(2 * R < 0x7fffff00ll ? 2 * R : 0x7fffff00ll);
+    Q.q[0] = ar.take<int>(2 * R + 64); Q.q[1] = ar.take<int>(2 * R + 64);
+    j->subid = ar.take<int>(R);
+    Q.cnt = j->d_flags; Q.h_cnt = j->h_cnt; Q.processed = &j->processed;
+    if (!ar.ok()) { tf_set_error("tf_watershed: workspace too small"); return TF_ENOMEM; }
+    int *d_nan = j->d_flags + WS_BATCH + 4;
+    TF_CHECK_HIP(hipMemsetAsync(d_nan, 0, sizeof(int), s));
+    {
+        TfProfScope ps(TFK_WS_SETUP, 0.0, s);
+        if (rv) hipLaunchKernelGGL(k_wsr_compact, dim3(nb1), dim3(256), 0, s, field, (const int *)cid, *rv, pix, val, nbr, c.K2, c.M1, d_nan);
+        else if (n_nbr == 6) hipLaunchKernelGGL(k_ws_compact<6>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
+        else if (n_nbr == 18) hipLaunchKernelGGL(k_ws_compact<18>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
+        else if (n_nbr == 26) hipLaunchKernelGGL(k_ws_compact<26>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
+        else hipLaunchKernelGGL(k_ws_compact<0>, grid, block, 0, s, field, fwd, bwd, cid, g, pix, val, nbr, c.K2, c.M1, d_nan);
     }
-    st[8] = j->depth; st[9] = (int64_t)j->h_amb[0]; st[10] = (int64_t)j->h_amb[1]; st[11] = (int64_t)j->h_amb[2];
+    TF_CHECK_LAUNCH();
+    // the reference's `smaller()` (_watershed.pyx:161-164) is not an order on NaN: its heap then pops in an order
+    // that depends on the array state, and no closed form exists.  Refuse instead of returning something else.
+    int h_nan = 0;
+    TF_CHECK_HIP(hipMemcpyAsync(&h_nan, d_nan, sizeof(int), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    if (h_nan) {
+        tf_set_error("tf_watershed: the field is NaN at a floodable pixel or at a seed next to one; the pop order of the "
+                     "reference's heap is undefined for NaN keys (detection.get_combined_edge_field maps NaN to +inf)");
+        return TF_EINVAL;
+    }
+    // a front advances at least one pixel per sweep, so a phase needs at most "longest flood path" sweeps: bounded by
+    // T + H + W times a detour factor on a (T, H, W) grid; the raveled form knows no shape, there the only safe bound
+    // is the number of relevant pixels itself (a snake-shaped mask floods one pixel per sweep)
+    j->max_sweeps = rv ? 4096 + 2 * R : 4096 + 512 * (j->T + j->H + j->W);
     return TF_OK;
 }
 
-// host only: no HIP call, any thread
-static int ws_job_replay(tf_ws_job *j)
+static int ws_job_begin(tf_ws_job *j, const WsArgs &a)
 {
-    if (!j->need_replay || j->replay_done) return j->replay_rc;
-    const double t0 = ws_now_ms();
-    int n_ranked = 0;
-    if (j->sparse)
-        j->popped = ws_reference_ranks_sparse(j->M, j->S, (const long long *)j->hb_sk.p, (const unsigned *)j->hb_sval.p, (const int *)j->hb_sid.p,
-                                              j->nQ, (const unsigned *)j->hb_val.p, (const int *)j->hb_nbr.p, j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked);
-    else {
-        const WsSeedCodes codes{(const uint32_t *)j->hb_sval.p, (const uint32_t *)j->hb_sval.p + (j->coded ? j->code_words : 0), j->code_d, (const u64 *)j->hb_sid.p};
-        if (j->plain) {
-            if (j->coded) wsr_expand(j->M, codes, (u64 *)j->hb_sk.p);
-            j->popped = ws_reference_ranks_plain(j->M, (const u64 *)j->hb_sk.p, nullptr, j->nQ, (const unsigned *)j->hb_val.p,
-                                                 (const int *)j->hb_nbr.p, j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked);
-        } else
-            j->popped = ws_reference_ranks_dense(j->M, (u64 *)j->hb_sk.p, j->nQ, (const unsigned *)j->hb_val.p, (const int *)j->hb_nbr.p,
-                                                 j->n_nbr, j->vmax, (int *)j->hb_rank.p, &n_ranked, j->coded ? &codes : nullptr);
+    TfArena ar(a.ws, a.ws_bytes);
+    int rc = ws_begin_carve(j, a, ar);
+    if (!rc) rc = ws_begin_relevant(j, a);
+    if (!rc) rc = ws_begin_compact(j, a, ar);
+    if (rc) return rc;
+    j->stage = WS_STAGE_LABELS;
+    if (j->R == 0) return TF_OK;
+    // begin, part 4: the export on a guess, and the sweeps
+    if ((a.flags & TF_WS_REFERENCE_ORDER) && a.spec_key >= 0) {
+        // SPECULATIVE EXPORT.  The replay needs nothing the relaxation phases compute -- seeds, keys and the neighbour table
+        // exist now -- except the tie value, and any value at or above the true one gives the ranks of every marker that can
+        // matter.  With the caller's guess (the previous window's tie value) the export happens here, the host replay runs
+        // beside phase A and the chain phases, and finish runs ONE root phase, with the pop ranks; the ROOT stage checks the
+        // guess against the tie value it then finds and exports again if the guess was too low.
+        j->ref.vmax = (unsigned)a.spec_key;
+        j->ref.speculative = true;
+        rc = ws_job_export(j);
+        if (rc) return rc;
     }
-    j->n_ranked = n_ranked;
-    j->replay_done = true;
-    j->ms_replay = ws_now_ms() - t0;
-    if (j->popped < 0) { tf_set_error("tf_watershed: out of host memory for the reference-order replay"); j->replay_rc = TF_ENOMEM; }
-    return j->replay_rc;
+    j->stage = WS_STAGE_SWEEPS;
+    if (a.flags & TF_WS_DEFER_SWEEPS) return TF_OK;                                 // phase A and the chain levels: tf_watershed_sweeps / finish
+    return ws_job_sweeps(j);
 }
 
+// ---- replay (host only: no HIP call, any thread) ---------------------------------------------------------------------------
+static int ws_job_replay(tf_ws_job *j)
+{
+    WsRef &r = j->ref;
+    if (!ws_ranks_on_host(r.ranks) || r.replay_done) return r.replay_rc;
+    const double t0 = ws_now_ms();
+    const unsigned *val = (const unsigned *)r.hb_val.p; const int *nbr = (const int *)r.hb_nbr.p; int *rank = (int *)r.hb_rank.p;
+    int n_ranked = 0;
+    if (r.ranks == WS_RANKS_HOST_SPARSE)
+        r.popped = ws_reference_ranks_sparse(r.M, r.S, (const long long *)r.hb_sk.p, (const unsigned *)r.hb_sval.p, (const int *)r.hb_sid.p,
+                                             r.nQ, val, nbr, j->n_nbr, r.vmax, rank, &n_ranked);
+    else {
+        const bool coded = r.ranks == WS_RANKS_HOST_CODED;
+        const WsSeedCodes codes{(const uint32_t *)r.hb_sval.p, (const uint32_t *)r.hb_sval.p + (coded ? r.code_words : 0), r.code_d, (const u64 *)r.hb_sid.p};
+        if (r.plain) {
+            if (coded) wsr_expand(r.M, codes, (u64 *)r.hb_sk.p);
+            r.popped = ws_reference_ranks_plain(r.M, (const u64 *)r.hb_sk.p, nullptr, r.nQ, val, nbr, j->n_nbr, r.vmax, rank, &n_ranked);
+        } else
+            r.popped = ws_reference_ranks_dense(r.M, (u64 *)r.hb_sk.p, r.nQ, val, nbr, j->n_nbr, r.vmax, rank, &n_ranked, coded ? &codes : nullptr);
+    }
+    r.n_ranked = n_ranked;
+    r.replay_done = true;
+    r.ms_replay = ws_now_ms() - t0;
+    if (r.popped < 0) r.replay_rc = ws_no_host_memory();
+    return r.replay_rc;
+}
+
+// ---- finish ----------------------------------------------------------------------------------------------------------------
 // pop ranks of the finished replay -> rank_dev (one entry per relevant pixel)
 static int ws_upload_ranks(tf_ws_job *j)
 {
     hipStream_t s = j->s;
-    const unsigned nbr_blocks = (unsigned)((j->R + 255) / 256);
+    const WsRef &r = j->ref;
     int *stg_rank = j->Q.q[0];
-    TF_CHECK_HIP(hipMemcpyAsync(stg_rank, j->hb_rank.p, (size_t)j->nQ * sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ws_scatter_ranks, dim3(nbr_blocks), dim3(256), 0, s, j->identity ? (const uint8_t *)nullptr : (const uint8_t *)j->scan,
-                       (const int *)j->subid, (const int *)stg_rank, j->n_ranked, j->R, j->rank_dev);
+    TF_CHECK_HIP(hipMemcpyAsync(stg_rank, r.hb_rank.p, (size_t)r.nQ * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ws_scatter_ranks, dim3(ws_blocks(j->R)), dim3(256), 0, s, r.identity ? (const uint8_t *)nullptr : (const uint8_t *)j->scan,
+                       (const int *)j->subid, (const int *)stg_rank, r.n_ranked, j->R, j->rank_dev);
     TF_CHECK_LAUNCH();
     TF_CHECK_HIP(hipStreamSynchronize(s));                              // (the staging queue is a frontier queue again right after)
     return TF_OK;
+}
+
+// The pop ranks of the current export into rank_dev, for the next root phase: the host replay (a no-op if the caller has run
+// it) and the upload; the device form filled rank_dev at the export.  Books what that cost onto the detour.
+static int ws_ranks_up(tf_ws_job *j)
+{
+    WsRef &r = j->ref;
+    r.ms_detour += r.ms_export;
+    if (ws_ranks_on_host(r.ranks)) {
+        int rc = ws_job_replay(j);
+        if (rc) return rc;
+        const double t0 = ws_now_ms();
+        rc = ws_upload_ranks(j);
+        if (rc) return rc;
+        r.ms_detour += r.ms_replay + (ws_now_ms() - t0);
+    }
+    j->ranked = true;
+    return TF_OK;
+}
+
+// stage RANKED_ROOT: replay, ranks up, the root phase again with the pop rank in place of the raster index, and the labels
+// are the reference's.  Chain levels, origins and label sets do not depend on that order, only the choice among tying
+// candidates does (so the check's counts stay what they were).
+static int ws_ranked_root(tf_ws_job *j)
+{
+    int rc = ws_ranks_up(j);
+    if (rc) return rc;
+    const double t0 = ws_now_ms();
+    rc = ws_root_and_check(j);
+    if (rc) return rc;
+    j->ref.applied = true;
+    if (ws_ranks_on_host(j->ref.ranks)) j->ref.ms_detour += ws_now_ms() - t0;      // (the device form books its export alone)
+    return TF_OK;
+}
+
+// stage ROOT: the root phase at the job's depth -- with the ranks of the export on a guess, if there was one -- and one more
+// chain level while the cut-off leaves ties.  Then, with TF_WS_REFERENCE_ORDER and labels that hang on the order of
+// equal-valued markers: the tie value; unless ranks for it are already in, the export for it, and the stage is RANKED_ROOT --
+// at once (TF_OK) if the ranks came from the device, after the caller's replay (TF_WS_REPLAY_PENDING) if not.
+static int ws_job_root(tf_ws_job *j)
+{
+    hipStream_t s = j->s;
+    WsRef &r = j->ref;
+    int rc = r.ranks != WS_RANKS_NONE ? ws_ranks_up(j) : TF_OK;
+    if (rc) return rc;
+    for (;;) {
+        rc = ws_root_and_check(j);
+        if (rc) return rc;
+        if (j->h_amb[2] == 0 || j->depth >= j->depth_max) break;
+        j->depth += 1;                                                   // ties left by the cut-off: one more chain level
+        rc = ws_chain_levels(j);
+        if (rc) return rc;
+    }
+    j->stage = WS_STAGE_LABELS;
+    if (!((j->flags & TF_WS_REFERENCE_ORDER) && j->h_amb[1] > 0 && j->h_amb[2] == 0)) return TF_OK;
+    // Labels hang on the order of equal-valued markers.  The largest marker value at which they do:
+    unsigned *d_vmax = (unsigned *)(j->d_cnt + 3);
+    TF_CHECK_HIP(hipMemsetAsync(d_vmax, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(k_ws_tie_value_max, dim3(ws_blocks(j->R)), dim3(256), 0, s, j->c, (const int *)j->org, j->field, j->ranked ? 1 : 0, d_vmax);
+    TF_CHECK_LAUNCH();
+    unsigned h_vmax = 0;
+    TF_CHECK_HIP(hipMemcpyAsync(&h_vmax, d_vmax, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    TF_CHECK_HIP(hipStreamSynchronize(s));
+    r.true_vmax = h_vmax; r.has_tie = true;
+    if (j->ranked && h_vmax <= r.vmax) {                                 // the guess covered it: these ARE the labels
+        r.applied = true;
+        r.spec_hit = true;
+        return TF_OK;
+    }
+    // no ranks, or ranks for too low a value: that export is discarded, and a new one made for the value found
+    ws_ref_give_buffers(r);
+    r.replay_done = false; r.speculative = false; r.replay_rc = TF_OK;
+    j->ranked = false;
+    r.vmax = h_vmax;
+    rc = ws_job_export(j);
+    if (rc) return rc;
+    j->stage = WS_STAGE_RANKED_ROOT;
+    return ws_ranks_on_host(r.ranks) ? TF_WS_REPLAY_PENDING : TF_OK;     // the replay is the caller's to run (any thread); finish is entered again afterwards
 }
 
 static int ws_job_finish(tf_ws_job *j, int32_t *labels, uint8_t *amb_out)
 {
     TF_REQUIRE(labels, "tf_watershed: null pointer");
     hipStream_t s = j->s;
-    int64_t *st = j->st;
     const WsC &c = j->c;
     const int64_t R = j->R, N = j->N;
-    const unsigned nb1 = (unsigned)((N + 255) / 256);
-    bool ranked = j->ranked;                                             // root keys are (pop rank << 32) | compact id
-    if (R > 0 && j->sweeps_pending) {                                    // TF_WS_DEFER_SWEEPS and nobody has called tf_watershed_sweeps
-        const int rc_s = ws_job_sweeps(j);
-        if (rc_s) return rc_s;
+    int rc = ws_job_sweeps(j);                                           // (TF_WS_DEFER_SWEEPS and nobody has called tf_watershed_sweeps)
+    if (!rc && j->stage == WS_STAGE_ROOT) rc = ws_job_root(j);
+    if (!rc && j->stage == WS_STAGE_RANKED_ROOT) {
+        rc = ws_ranked_root(j);
+        if (!rc) j->stage = WS_STAGE_LABELS;
     }
-    if (R > 0 && j->late_export) {
-        // second entry: the replay of the export that followed the root phase has run (or runs here): ranks up, root phase again
-        j->late_export = false;
-        int rc = ws_job_replay(j);
-        if (rc) return rc;
-        const double t0 = ws_now_ms();
-        rc = ws_upload_ranks(j);
-        if (rc) return rc;
-        ranked = j->ranked = true;
-        rc = ws_root_and_check(j, true);                                 // (the check's counts do not depend on the order)
-        if (rc) return rc;
-        j->applied = true;
-        j->ms_detour += j->ms_export + j->ms_replay + (ws_now_ms() - t0);
-        st[13] = j->popped; st[14] = j->sparse ? j->S : j->M;
-        st[15] = (int64_t)(j->ms_detour * 1000.0);
-    } else if (R > 0 && j->root_pending) {
-        j->root_pending = false;
-        const unsigned nbr_blocks = (unsigned)((R + 255) / 256);
-        int rc;
-        double &ms_detour = j->ms_detour;
-        if (j->need_replay) {                                            // the speculative export's replay: ranks before the root phase
-            rc = ws_job_replay(j);                                       // (a no-op if the caller has run it)
-            if (rc) return rc;
-            const double t0 = ws_now_ms();
-            rc = ws_upload_ranks(j);
-            if (rc) return rc;
-            ranked = j->ranked = true;
-            ms_detour = j->ms_export + j->ms_replay + (ws_now_ms() - t0);
-        } else if (j->device_ranks) {                                    // the speculative export found one value class: rank_dev is filled
-            ranked = j->ranked = true;
-            ms_detour = j->ms_export;
-        }
-        for (;;) {
-            rc = ws_root_and_check(j, ranked);
-            if (rc) return rc;
-            if (j->h_amb[2] == 0 || j->depth >= j->depth_max) break;
-            j->depth += 1;                                               // ties left by the cut-off: one more chain level
-            rc = ws_chain_levels(j);
-            if (rc) return rc;
-        }
-        if ((j->flags & TF_WS_REFERENCE_ORDER) && j->h_amb[1] > 0 && j->h_amb[2] == 0) {
-            // Labels hang on the order of equal-valued markers.  The largest marker value at which they do:
-            unsigned *d_vmax = (unsigned *)(j->d_cnt + 3);
-            TF_CHECK_HIP(hipMemsetAsync(d_vmax, 0, sizeof(unsigned), s));
-            hipLaunchKernelGGL(k_ws_tie_value_max, dim3(nbr_blocks), dim3(256), 0, s, c, (const int *)j->org, j->field, ranked ? 1 : 0, d_vmax);
-            TF_CHECK_LAUNCH();
-            unsigned h_vmax = 0;
-            TF_CHECK_HIP(hipMemcpyAsync(&h_vmax, d_vmax, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-            TF_CHECK_HIP(hipStreamSynchronize(s));
-            j->true_vmax = h_vmax; j->has_tie = true;
-            if (ranked && h_vmax <= j->vmax) {
-                j->applied = true;                                       // the guess covered it: these ARE the labels
-                j->spec_hit = true;
-            } else {
-                // the host replay (ws_reference_ranks*) gives the reference's order, and the root phase is repeated with the
-                // pop rank in place of the raster index.  Chain levels, origins and label sets do not depend on that order,
-                // only the choice among tying candidates does.
-                ws_host_give(j->hb_val); ws_host_give(j->hb_nbr); ws_host_give(j->hb_rank);
-                ws_host_give(j->hb_sk); ws_host_give(j->hb_sval); ws_host_give(j->hb_sid);
-                j->need_replay = false; j->replay_done = false; j->speculative = false; j->replay_rc = TF_OK;
-                j->vmax = h_vmax;
-                rc = ws_job_export(j);
-                if (rc) return rc;
-                if (j->device_ranks) {                                   // closed form on the device: no host pass, root phase again at once
-                    ranked = j->ranked = true;
-                    rc = ws_root_and_check(j, true);                     // (the check's counts do not depend on the order)
-                    if (rc) return rc;
-                    j->applied = true;
-                    ms_detour += j->ms_export;
-                    st[13] = j->popped; st[14] = j->S; st[15] = (int64_t)(ms_detour * 1000.0);
-                    goto labels_out;
-                }
-                // the replay is the caller's to run (any thread); finish is entered again afterwards
-                j->late_export = true;
-                st[8] = j->depth; st[9] = (int64_t)j->h_amb[0]; st[10] = (int64_t)j->h_amb[1]; st[11] = (int64_t)j->h_amb[2];
-                return TF_WS_REPLAY_PENDING;
-            }
-        }
-        if (j->need_replay && j->replay_done) {
-            st[13] = j->popped; st[14] = j->sparse ? j->S : j->M;
-            st[15] = (int64_t)(ms_detour * 1000.0);
-        } else if (j->device_ranks) {
-            st[13] = j->popped; st[14] = j->S; st[15] = (int64_t)(ms_detour * 1000.0);
-        }
-    }
-labels_out:
-    st[8] = j->depth; st[9] = (int64_t)j->h_amb[0]; st[10] = (int64_t)j->h_amb[1]; st[11] = (int64_t)j->h_amb[2];
+    if (rc) return rc;
     {
         TfProfScope ps(TFK_WS_LABELS, 12.0 * (double)N, s);
-        if (j->raveled) { if (R > 0) hipLaunchKernelGGL(k_wsr_labels, dim3(nb1), dim3(256), 0, s, (const int *)j->cid, (const u64 *)c.Rt, c.pix, ranked ? 1 : 0, labels, N); }
-        else hipLaunchKernelGGL(k_ws_labels, dim3(nb1), dim3(256), 0, s, j->markers, j->cid, c.Rt, c.pix, ranked ? 1 : 0, c.Llo, c.Lhi, j->org, labels,
+        if (j->raveled) { if (R > 0) hipLaunchKernelGGL(k_wsr_labels, dim3(ws_blocks(N)), dim3(256), 0, s, (const int *)j->cid, (const u64 *)c.Rt, c.pix, j->ranked ? 1 : 0, labels, N); }
+        else hipLaunchKernelGGL(k_ws_labels, dim3(ws_blocks(N)), dim3(256), 0, s, j->markers, j->cid, c.Rt, c.pix, j->ranked ? 1 : 0, c.Llo, c.Lhi, j->org, labels,
                                 R > 0 ? amb_out : nullptr, N);
     }
     TF_CHECK_LAUNCH();
     if (R == 0 && amb_out) TF_CHECK_HIP(hipMemsetAsync(amb_out, 0, (size_t)N, s));
     TF_CHECK_HIP(hipStreamSynchronize(s));
-    if (st[11] > 0) {
+    if (j->h_amb[2] > 0) {
         tf_set_error("tf_watershed: %lld pixel(s) still tie at chain depth %d (the compared chains are cut off); "
                      "labels written, but they may differ from the reference there: raise max_depth",
-                     (long long)st[11], j->depth);
+                     (long long)j->h_amb[2], j->depth);
         return TF_EDEPTH;
     }
     // reference order applied: the labels ARE the reference's, whatever its heap did with the equal-valued markers
-    return (st[9] > 0 && !j->applied) ? TF_WS_AMBIGUOUS : TF_OK;
+    return (j->h_amb[0] > 0 && !j->ref.applied) ? TF_WS_AMBIGUOUS : TF_OK;
 }
 
+// ---- the entry points ------------------------------------------------------------------------------------------------------
 static tf_ws_job *ws_job_new()
 {
     tf_ws_job *j = new (std::nothrow) tf_ws_job;
-    if (!j) return nullptr;
+    if (!j) { tf_set_error("tf_watershed: out of host memory"); return nullptr; }
     memset((void *)j, 0, sizeof(*j));
     return j;
 }
 
-static int ws_run(const float *field, const int32_t *markers, const int8_t *mask,
-                  const float *fwd, const float *bwd, int64_t T, int64_t H, int64_t W,
-                  const int8_t *nbr_host, int n_nbr, int depth0, int depth_max, int flags, int32_t *labels,
-                  uint8_t *amb_out, void *ws, size_t ws_bytes, int64_t *st, void *stream,
-                  const WsRavel *rv = nullptr, const int64_t *rv_locs = nullptr, int64_t rv_n_locs = 0)
+// begin and finish back to back (the replay, if one is needed, on this thread); stats_host: null or n_stats slots
+static int ws_run(const WsArgs &a, int32_t *labels, uint8_t *amb_out, int64_t *stats_host, int n_stats = TF_WS_NSTATS)
 {
-    TF_REQUIRE(!(flags & TF_WS_DEFER_SWEEPS), "tf_watershed: unknown flag (TF_WS_DEFER_SWEEPS is tf_watershed_begin's)");
-    for (int i = 0; i < TF_WS_NSTATS; i++) st[i] = 0;
+    int64_t st[TF_WS_NSTATS];
+    for (int i = 0; i < n_stats && stats_host; i++) stats_host[i] = 0;
+    TF_REQUIRE(!(a.flags & TF_WS_DEFER_SWEEPS), "tf_watershed: unknown flag (TF_WS_DEFER_SWEEPS is tf_watershed_begin's)");
     TF_REQUIRE(labels, "tf_watershed: null pointer");
     tf_ws_job *j = ws_job_new();
-    if (!j) { tf_set_error("tf_watershed: out of host memory"); return TF_ENOMEM; }
-    int rc = ws_job_begin(j, field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, depth0, depth_max, flags, ws, ws_bytes, stream, rv, rv_locs, rv_n_locs);
+    if (!j) return TF_ENOMEM;
+    int rc = ws_job_begin(j, a);
     if (rc == TF_OK) {
         rc = ws_job_finish(j, labels, amb_out);
         if (rc == TF_WS_REPLAY_PENDING) rc = ws_job_finish(j, labels, amb_out);     // (runs the replay itself)
     }
-    for (int i = 0; i < TF_WS_NSTATS; i++) st[i] = j->st[i];
+    ws_publish(j, st, nullptr);
+    for (int i = 0; i < n_stats && stats_host; i++) stats_host[i] = st[i];
     ws_job_free(j);
     return rc;
 }
@@ -2148,21 +2325,22 @@ extern "C" int tf_watershed_begin(const float *field, const int32_t *markers, co
     *job_out = nullptr;
     TF_REQUIRE(guessed_tie_key >= -1 && guessed_tie_key <= 0xFFFFFFFFll, "tf_watershed_begin: guessed_tie_key must be -1 or a 32-bit ordered key");
     tf_ws_job *j = ws_job_new();
-    if (!j) { tf_set_error("tf_watershed: out of host memory"); return TF_ENOMEM; }
-    const int rc = ws_job_begin(j, field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, chain_depth, max_depth, flags, ws, ws_bytes, stream,
-                                nullptr, nullptr, 0, guessed_tie_key);
-    if (stats_host) for (int i = 0; i < TF_WS_NSTATS; i++) stats_host[i] = j->st[i];
+    if (!j) return TF_ENOMEM;
+    const WsArgs a{field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, chain_depth, max_depth, flags, ws, ws_bytes, stream,
+                   nullptr, nullptr, 0, guessed_tie_key};
+    const int rc = ws_job_begin(j, a);
+    ws_publish(j, stats_host, nullptr);
     if (rc != TF_OK) { ws_job_free(j); return rc; }
     *job_out = j;
     return TF_OK;
 }
-extern "C" int tf_watershed_needs_replay(const void *job) { return job && ((const tf_ws_job *)job)->need_replay ? 1 : 0; }
+extern "C" int tf_watershed_needs_replay(const void *job) { return job && ws_ranks_on_host(((const tf_ws_job *)job)->ref.ranks) ? 1 : 0; }
 extern "C" int tf_watershed_sweeps(void *job, int64_t *stats_host)
 {
     TF_REQUIRE(job, "tf_watershed_sweeps: null job");
     tf_ws_job *j = (tf_ws_job *)job;
-    const int rc = j->R > 0 ? ws_job_sweeps(j) : TF_OK;
-    if (stats_host) for (int i = 0; i < TF_WS_NSTATS; i++) stats_host[i] = j->st[i];
+    const int rc = ws_job_sweeps(j);
+    ws_publish(j, stats_host, nullptr);
     return rc;
 }
 extern "C" int tf_watershed_replay(void *job)
@@ -2170,14 +2348,12 @@ extern "C" int tf_watershed_replay(void *job)
     TF_REQUIRE(job, "tf_watershed_replay: null job");
     return ws_job_replay((tf_ws_job *)job);
 }
-extern "C" int tf_watershed_job_info(const void *job, int64_t *info);
 extern "C" int tf_watershed_finish(void *job, int32_t *labels, uint8_t *ambiguous, int64_t *stats_host, int64_t *info_host)
 {
     TF_REQUIRE(job, "tf_watershed_finish: null job");
     tf_ws_job *j = (tf_ws_job *)job;
     const int rc = ws_job_finish(j, labels, ambiguous);
-    if (stats_host) for (int i = 0; i < TF_WS_NSTATS; i++) stats_host[i] = j->st[i];
-    if (info_host) (void)tf_watershed_job_info(j, info_host);
+    ws_publish(j, stats_host, info_host);
     if (rc == TF_WS_REPLAY_PENDING) return rc;                            // the job lives on: replay, then finish again
     ws_job_free(j);
     return rc;
@@ -2192,12 +2368,7 @@ extern "C" int tf_watershed_set_stream(void *job, void *stream)
 extern "C" int tf_watershed_job_info(const void *job, int64_t *info)
 {
     TF_REQUIRE(job && info, "tf_watershed_job_info: null pointer");
-    const tf_ws_job *j = (const tf_ws_job *)job;
-    info[0] = j->need_replay ? (j->sparse ? 1 : 2) : (j->device_ranks ? 3 : 0);
-    info[1] = j->M; info[2] = j->S; info[3] = j->nQ; info[4] = j->R;
-    info[5] = (int64_t)(j->ms_export * 1000.0); info[6] = j->replay_done ? (int64_t)(j->ms_replay * 1000.0) : -1;
-    info[7] = j->has_tie ? (int64_t)j->true_vmax : -1;
-    info[8] = j->speculative ? 1 : 0; info[9] = j->spec_hit ? 1 : 0; info[10] = (j->need_replay || j->device_ranks) ? (int64_t)j->vmax : -1; info[11] = j->device_ranks ? 1 : 0;
+    ws_publish((const tf_ws_job *)job, nullptr, info);
     return TF_OK;
 }
 
@@ -2207,11 +2378,8 @@ extern "C" int tf_watershed_ex2(const float *field, const int32_t *markers, cons
                                 int32_t *labels, uint8_t *ambiguous, void *ws, size_t ws_bytes,
                                 int64_t *stats_host, void *stream)
 {
-    int64_t st[TF_WS_NSTATS];
-    const int rc = ws_run(field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, chain_depth, max_depth, flags, labels,
-                          ambiguous, ws, ws_bytes, st, stream);
-    if (stats_host) for (int i = 0; i < TF_WS_NSTATS; i++) stats_host[i] = st[i];
-    return rc;
+    const WsArgs a{field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, chain_depth, max_depth, flags, ws, ws_bytes, stream, nullptr, nullptr, 0, -1};
+    return ws_run(a, labels, ambiguous, stats_host);
 }
 
 extern "C" int tf_watershed_ex(const float *field, const int32_t *markers, const int8_t *mask,
@@ -2219,11 +2387,8 @@ extern "C" int tf_watershed_ex(const float *field, const int32_t *markers, const
                                const int8_t *nbr_host, int n_nbr, int chain_depth, int flags, int32_t *labels,
                                void *ws, size_t ws_bytes, int64_t *stats_host, void *stream)
 {
-    int64_t st[TF_WS_NSTATS];
-    const int rc = ws_run(field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, chain_depth, chain_depth, flags, labels,
-                          nullptr, ws, ws_bytes, st, stream);
-    if (stats_host) for (int i = 0; i < 8; i++) stats_host[i] = st[i];
-    return rc;
+    const WsArgs a{field, markers, mask, fwd, bwd, T, H, W, nbr_host, n_nbr, chain_depth, chain_depth, flags, ws, ws_bytes, stream, nullptr, nullptr, 0, -1};
+    return ws_run(a, labels, nullptr, stats_host, 8);                        // (the 8 slots this older form documents)
 }
 
 extern "C" int tf_watershed(const float *field, const int32_t *markers, const int8_t *mask,
@@ -2263,12 +2428,9 @@ extern "C" int tf_watershed_raveled_ex(const float *image, int64_t n, const int6
     for (int i = 0; i < n_structure; i++) {
         rv.structure[i] = structure_host[i]; rv.floc[i] = forward_offset_locations_host[i]; rv.bloc[i] = backward_offset_locations_host[i];
     }
-    int64_t st[TF_WS_NSTATS];
     const int d0 = max_depth < 3 ? max_depth : 3;
-    const int rc = ws_run(image, output, mask, nullptr, nullptr, 0, 0, 0, nullptr, n_structure, d0, max_depth, flags, output,
-                          nullptr, ws, ws_bytes, st, stream, &rv, marker_locations, n_markers);
-    if (stats_host) for (int i = 0; i < TF_WS_NSTATS; i++) stats_host[i] = st[i];
-    return rc;
+    const WsArgs a{image, output, mask, nullptr, nullptr, 0, 0, 0, nullptr, n_structure, d0, max_depth, flags, ws, ws_bytes, stream, &rv, marker_locations, n_markers, -1};
+    return ws_run(a, output, nullptr, stats_host);
 }
 
 extern "C" int tf_watershed_raveled(const float *image, int64_t n, const int64_t *marker_locations, int64_t n_markers,
@@ -2283,3 +2445,4 @@ extern "C" int tf_watershed_raveled(const float *image, int64_t n, const int64_t
                                    backward_offset, forward_offset_locations_host, backward_offset_locations_host, mask,
                                    strides_host, n_strides, compactness, output, wsl, max_depth, 0, ws, ws_bytes, stats_host, stream);
 }
+
