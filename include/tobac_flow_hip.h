@@ -1158,6 +1158,33 @@ int tf_grid_spacing(double a, double rf, const double *lat, const double *lon, i
 int tf_view_angles(int mode, const double *scalars, int n_scalars, const double *lat, const double *lon, int64_t n, const double *x,
                    const double *y, int64_t W, double *out0, double *out1, void *stream);
 
+/* ---- ECEF and the GLM parallax correction (version 116) ------------------------------------------------------------------
+ * What the reference's glm.py:25-57 does through the lmatools coordinate systems of _lmatools.py (pyproj Transformers
+ * between latlong, geocent and geos).  float64 inside, degrees and metres; one element per lane, one launch, no workspace,
+ * no atomics.  n = 0 is a successful no-op; a null pointer with n > 0 is TF_EINVAL.
+ *
+ * tf_ecef: mode TF_ECEF_FROM_GEODETIC (in = lon, lat, alt -> out = X, Y, Z) or TF_ECEF_TO_GEODETIC (in = X, Y, Z -> out =
+ *   lon, lat, alt) on the ellipsoid (a, rf); the geodetic triple is in pyproj's order.  To geodetic: Bowring's iteration
+ *   with two updates, no data-dependent loop (below 1e-16 rad up to 160 km above the ellipsoid); on the polar axis lon = 0
+ *   and lat = +-90; the origin, a NaN or an infinite coordinate give NaN in all three.
+ * tf_geos_to_ecef: scan angles (x, y) of the system `geos` -> the nearer point at which the ray meets the system's
+ *   ellipsoid, turned into the Earth's frame by lon_0, in metres.  The satellite stands a + h from the centre with the
+ *   system's own a, as PROJ places it.  A ray that misses gives +inf in all three (NaN for a NaN angle).
+ * tf_glm_parallax: for n flashes at (lat, lon) degrees (in_dtype TF_F32 or TF_F64; float32 is widened exactly): the
+ *   offsets (dlon, dlat) of get_glm_parallax_offsets -- the flash projected with `grid`, the ray with the same scan angles
+ *   of the system `ltg` (the lightning ellipsoid) met with that system's ellipsoid, the point read as longitude and
+ *   latitude on the ellipsoid (lla_a, lla_rf), minus the flash's own -- and the scan angles (x, y) on `grid` of the flash
+ *   moved back by them (get_corrected_glm_x_y).  The pair dlon, dlat and the pair x, y may each be NULL, not both.  `ltg`
+ *   shares lon_0 and sweep_y with `grid` (TF_EINVAL otherwise).  A flash beyond the limb of `grid`, or whose ray misses
+ *   the lightning ellipsoid: NaN offsets, x = y = +inf (tf_bin_points drops such a point).  NaN in: NaN in all four. */
+#define TF_ECEF_FROM_GEODETIC 0
+#define TF_ECEF_TO_GEODETIC 1
+int tf_ecef(int mode, double a, double rf, const double *in0, const double *in1, const double *in2, int64_t n, double *out0,
+            double *out1, double *out2, void *stream);
+int tf_geos_to_ecef(const TfGeos *geos, const double *x, const double *y, int64_t n, double *X, double *Y, double *Z, void *stream);
+int tf_glm_parallax(const TfGeos *grid, const TfGeos *ltg, double lla_a, double lla_rf, const void *lat, const void *lon, int in_dtype,
+                    int64_t n, double *dlon, double *dlat, double *x, double *y, void *stream);
+
 /* tf_copy16: dst = src, 16 bytes per lane per access -- the measured practical HBM ceiling of bench.py's roofline.
  * (Round 5's tf_stream_create_cu_mask / tf_stream_create_priority / tf_stream_destroy / tf_debug_cu_histogram served two
  * scheduling experiments that were not adopted; they live in tools/experiments/stream_experiments.hip now, outside the

@@ -54,6 +54,7 @@ class Geos(ctypes.Structure):
 
 GEOS_INF = 1
 VIEW_SZA, VIEW_SZA_AZI, VIEW_SATELLITE, VIEW_ABI_ZENITH = range(4)
+ECEF_FROM_GEODETIC, ECEF_TO_GEODETIC = 0, 1
 
 
 class FieldPlane(ctypes.Structure):
@@ -253,6 +254,10 @@ _PROTOS = {
     "tf_grid_spacing_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
     "tf_grid_spacing": (_c.c_int, [_c.c_double, _c.c_double, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "tf_view_angles": (_c.c_int, [_c.c_int, _P, _c.c_int, _P, _P, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P]),
+    "tf_ecef": (_c.c_int, [_c.c_int, _c.c_double, _c.c_double, _P, _P, _P, _c.c_int64, _P, _P, _P, _P]),
+    "tf_geos_to_ecef": (_c.c_int, [_c.POINTER(Geos), _P, _P, _c.c_int64, _P, _P, _P, _P]),
+    "tf_glm_parallax": (_c.c_int, [_c.POINTER(Geos), _c.POINTER(Geos), _c.c_double, _c.c_double, _P, _P, _c.c_int, _c.c_int64, _P, _P,
+                                   _P, _P, _P]),
     "tf_profile_enable": (_c.c_int, [_c.c_int]),
     "tf_profile_kernel_count": (_c.c_int, []),
     "tf_profile_kernel_name": (_c.c_char_p, [_c.c_int]),

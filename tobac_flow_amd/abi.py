@@ -17,6 +17,8 @@ from tobac_flow_amd import geo
 
 
 def _values(v):
+    if isinstance(v, np.ndarray):                                 # (a datetime64 array has no buffer to offer as `.data`)
+        return v
     for name in ("data", "values"):
         inner = getattr(v, name, None)
         if inner is not None and not callable(inner) and (geo._is_tensor(inner) or isinstance(inner, np.ndarray)):

@@ -7,6 +7,8 @@
 //   tf_grid_spacing                           geo.get_pixel_lengths / get_pixel_area (geo.py:224-246) and their two copies
 //   tf_view_angles                            geo.get_sza, get_sza_and_azi, get_satellite_viewing_angles (geo.py:14-221),
 //                                             abi.get_abi_zenith_angle (abi.py:68-89)
+//   tf_ecef, tf_geos_to_ecef                  the toECEF / fromECEF of the lmatools coordinate systems (_lmatools.py)
+//   tf_glm_parallax                           glm.get_glm_parallax_offsets and get_corrected_glm_x_y (glm.py:25-57), fused
 //
 // The arithmetic of one element is in geodesy_kernels.h (it compiles for the host as well); here are the work layouts.
 // No atomics: every output is the same in every run.
@@ -201,6 +203,48 @@ k_view_angles(int mode, const GdScalars sc, const double *__restrict__ lat, cons
     if (out1) out1[k] = a1;
 }
 
+__global__ void __launch_bounds__(GD_BLOCK)
+k_ecef(int mode, double a, double f, const double *__restrict__ in0, const double *__restrict__ in1, const double *__restrict__ in2,
+       int64_t n, double *__restrict__ out0, double *__restrict__ out1, double *__restrict__ out2)
+{
+    const int64_t k = (int64_t)blockIdx.x * GD_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    double o0, o1, o2;
+    if (mode == TF_ECEF_FROM_GEODETIC) gd_geodetic_to_ecef_one(a, f, in0[k], in1[k], in2[k], o0, o1, o2);
+    else gd_ecef_to_geodetic_one(a, f, in0[k], in1[k], in2[k], o0, o1, o2);
+    out0[k] = o0;
+    out1[k] = o1;
+    out2[k] = o2;
+}
+
+__global__ void __launch_bounds__(GD_BLOCK)
+k_geos_to_ecef(const GdGeos s, const double *__restrict__ x, const double *__restrict__ y, int64_t n, double *__restrict__ X,
+               double *__restrict__ Y, double *__restrict__ Z)
+{
+    const int64_t k = (int64_t)blockIdx.x * GD_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    double px, py, pz;
+    gd_geos_to_ecef_one(s, x[k], y[k], px, py, pz);
+    X[k] = px;
+    Y[k] = py;
+    Z[k] = pz;
+}
+
+// One flash per lane: 8 or 16 bytes in and 16 or 32 out against some 400 float64 operations, so the lanes' plain
+// consecutive loads and stores are all the memory system is asked for.
+template <typename T>
+__global__ void __launch_bounds__(GD_BLOCK)
+k_glm_parallax(const GdParallax c, const T *__restrict__ lat, const T *__restrict__ lon, int64_t n, double *__restrict__ dlon,
+               double *__restrict__ dlat, double *__restrict__ x, double *__restrict__ y)
+{
+    const int64_t k = (int64_t)blockIdx.x * GD_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    double dlo, dla, px, py, alt;
+    gd_glm_parallax_one(c, (double)lat[k], (double)lon[k], dlo, dla, px, py, alt);
+    if (dlon) { dlon[k] = dlo; dlat[k] = dla; }
+    if (x) { x[k] = px; y[k] = py; }
+}
+
 // ---- entry points ----------------------------------------------------------------------------------------------------------
 #define GD_MAX_N ((((int64_t)1 << 31) - 1) * GD_BLOCK)
 
@@ -349,6 +393,58 @@ extern "C" int tf_view_angles(int mode, const double *scalars, int n_scalars, co
     GdScalars sc = {{0, 0, 0, 0}};
     for (int k = 0; k < n_scalars; k++) sc.v[k] = scalars[k];
     hipLaunchKernelGGL(k_view_angles, dim3(gd_blocks(n)), dim3(GD_BLOCK), 0, (hipStream_t)stream, mode, sc, lat, lon, n, x, y, W, out0, out1);
+    TF_CHECK_LAUNCH();
+    return TF_OK;
+}
+
+extern "C" int tf_ecef(int mode, double a, double rf, const double *in0, const double *in1, const double *in2, int64_t n, double *out0,
+                       double *out1, double *out2, void *stream)
+{
+    TF_REQUIRE(mode == TF_ECEF_FROM_GEODETIC || mode == TF_ECEF_TO_GEODETIC, "tf_ecef: unknown mode");
+    TF_REQUIRE(gd_ellipsoid_ok(a, rf), "tf_ecef: a is positive and finite, rf is 0 (a sphere) or above 1");
+    TF_REQUIRE(n >= 0 && n <= GD_MAX_N, "tf_ecef: bad number of points");
+    if (n == 0) return TF_OK;
+    TF_REQUIRE(in0 && in1 && in2 && out0 && out1 && out2, "tf_ecef: null pointer");
+    hipLaunchKernelGGL(k_ecef, dim3(gd_blocks(n)), dim3(GD_BLOCK), 0, (hipStream_t)stream, mode, a, rf != 0.0 ? 1.0 / rf : 0.0, in0, in1, in2,
+                       n, out0, out1, out2);
+    TF_CHECK_LAUNCH();
+    return TF_OK;
+}
+
+extern "C" int tf_geos_to_ecef(const TfGeos *geos, const double *x, const double *y, int64_t n, double *X, double *Y, double *Z,
+                               void *stream)
+{
+    const int rc = gd_check_geos(geos, "tf_geos_to_ecef");
+    if (rc != TF_OK) return rc;
+    TF_REQUIRE(n >= 0 && n <= GD_MAX_N, "tf_geos_to_ecef: bad number of points");
+    if (n == 0) return TF_OK;
+    TF_REQUIRE(x && y && X && Y && Z, "tf_geos_to_ecef: null pointer");
+    hipLaunchKernelGGL(k_geos_to_ecef, dim3(gd_blocks(n)), dim3(GD_BLOCK), 0, (hipStream_t)stream, gd_geos_setup(*geos), x, y, n, X, Y, Z);
+    TF_CHECK_LAUNCH();
+    return TF_OK;
+}
+
+extern "C" int tf_glm_parallax(const TfGeos *grid, const TfGeos *ltg, double lla_a, double lla_rf, const void *lat, const void *lon,
+                               int in_dtype, int64_t n, double *dlon, double *dlat, double *x, double *y, void *stream)
+{
+    int rc = gd_check_geos(grid, "tf_glm_parallax (grid)");
+    if (rc == TF_OK) rc = gd_check_geos(ltg, "tf_glm_parallax (ltg)");
+    if (rc != TF_OK) return rc;
+    TF_REQUIRE(grid->lon_0 == ltg->lon_0 && grid->sweep_y == ltg->sweep_y, "tf_glm_parallax: ltg shares lon_0 and sweep_y with grid");
+    TF_REQUIRE(gd_ellipsoid_ok(lla_a, lla_rf), "tf_glm_parallax: lla_a is positive and finite, lla_rf is 0 (a sphere) or above 1");
+    TF_REQUIRE(in_dtype == TF_F32 || in_dtype == TF_F64, "tf_glm_parallax: lat and lon are float32 or float64");
+    TF_REQUIRE(n >= 0 && n <= GD_MAX_N, "tf_glm_parallax: bad number of flashes");
+    if (n == 0) return TF_OK;
+    TF_REQUIRE(lat && lon, "tf_glm_parallax: null pointer");
+    TF_REQUIRE((dlon != nullptr) == (dlat != nullptr) && (x != nullptr) == (y != nullptr), "tf_glm_parallax: dlon goes with dlat, x with y");
+    TF_REQUIRE(dlon || x, "tf_glm_parallax: no output");
+    const GdParallax c = gd_parallax_setup(*grid, *ltg, lla_a, lla_rf);
+    if (in_dtype == TF_F64)
+        hipLaunchKernelGGL(k_glm_parallax<double>, dim3(gd_blocks(n)), dim3(GD_BLOCK), 0, (hipStream_t)stream, c, (const double *)lat,
+                           (const double *)lon, n, dlon, dlat, x, y);
+    else
+        hipLaunchKernelGGL(k_glm_parallax<float>, dim3(gd_blocks(n)), dim3(GD_BLOCK), 0, (hipStream_t)stream, c, (const float *)lat,
+                           (const float *)lon, n, dlon, dlat, x, y);
     TF_CHECK_LAUNCH();
     return TF_OK;
 }

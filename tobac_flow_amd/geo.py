@@ -1,6 +1,8 @@
 """Geodesy without pyproj: the reference's tobac_flow/geo.py (get_sza, get_sza_and_azi, get_satellite_viewing_angles,
 get_pixel_lengths, get_pixel_area) and the two pyproj classes it and its neighbours use, `Geod` (its `.inv`) and `Proj`
-with `proj="geos"` (here `GeosProj`).
+with `proj="geos"` (here `GeosProj`); and what the lmatools coordinate systems of tobac_flow/_lmatools.py take from pyproj's
+Transformers: `geodetic_to_ecef`, `ecef_to_geodetic`, `GeosProj.to_ecef` / `.from_ecef`, and the chain of them that is the
+GLM parallax correction, fused (`glm_parallax`).
 
 NumPy arrays in: the NumPy float64 path, the same algorithm written in NumPy.  Device tensors (or a DeviceField) in: the
 HIP kernels of csrc/geodesy.hip, device tensors out, nothing visits the host but the status word of the geodesic inverse.
@@ -173,22 +175,27 @@ class Geod:
 
 
 # ---- geos projection -------------------------------------------------------------------------------------------------------
+def _np_geos_ray(p, x, y):
+    """gd_geos_ray over arrays: (dy, dz, k, det) of the rays with scan angles (x, y)"""
+    ty = np.tan(y)
+    if not p.sweep_y:
+        vz = ty
+        vy = np.tan(x) * np.hypot(1.0, ty)
+    else:
+        vy = np.tan(x)
+        vz = ty * np.hypot(1.0, vy)
+    a = vz / p._rp
+    a = vy * vy + a * a + 1.0
+    b = -2.0 * p._rg
+    det = b * b - 4.0 * a * p._c
+    return vy, vz, (-b - np.sqrt(det)) / (2.0 * a), det
+
+
 def _np_geos_inverse(p, x, y):
     """gd_geos_inverse_one over arrays: scan angles (rad) -> (lat, lon) in degrees, NaN off the disk"""
     x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
     with np.errstate(all="ignore"):
-        ty = np.tan(y)
-        if not p.sweep_y:
-            vz = ty
-            vy = np.tan(x) * np.hypot(1.0, ty)
-        else:
-            vy = np.tan(x)
-            vz = ty * np.hypot(1.0, vy)
-        a = vz / p._rp
-        a = vy * vy + a * a + 1.0
-        b = -2.0 * p._rg
-        det = b * b - 4.0 * a * p._c
-        k = (-b - np.sqrt(det)) / (2.0 * a)
+        vy, vz, k, det = _np_geos_ray(p, x, y)
         vx = p._rg - k
         vy = vy * k
         vz = vz * k
@@ -205,17 +212,23 @@ def _ieee_remainder(v, m):
     return np.where(r > m / 2, r - m, np.where(r < -m / 2, r + m, r))
 
 
+def _np_geos_surface(p, lat, lon):
+    """gd_geos_surface over arrays: the points on the ellipsoid in the satellite's frame, in units of a, and the value of
+    PROJ's visibility test"""
+    lam = _ieee_remainder(lon - p.lon_0, 360.0) * _D2R
+    phi = np.arctan(p._rp2 * np.tan(lat * _D2R))
+    cp, sp = np.cos(phi), np.sin(phi)
+    r = p._rp / np.hypot(p._rp * cp, sp)
+    vx, vy, vz = r * np.cos(lam) * cp, r * np.sin(lam) * cp, r * sp
+    return vx, vy, vz, (p._rg - vx) * vx - vy * vy - vz * vz * p._rp_inv2
+
+
 def _np_geos_forward(p, lat, lon):
     """gd_geos_forward_one over arrays: degrees -> scan angles (rad), +inf beyond the limb"""
     lat, lon = np.broadcast_arrays(np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64))
     with np.errstate(all="ignore"):
-        lam = _ieee_remainder(lon - p.lon_0, 360.0) * _D2R
-        phi = np.arctan(p._rp2 * np.tan(lat * _D2R))
-        cp, sp = np.cos(phi), np.sin(phi)
-        r = p._rp / np.hypot(p._rp * cp, sp)
-        vx, vy, vz = r * np.cos(lam) * cp, r * np.sin(lam) * cp, r * sp
+        vx, vy, vz, vis = _np_geos_surface(p, lat, lon)
         tmp = p._rg - vx
-        vis = tmp * vx - vy * vy - vz * vz * p._rp_inv2
         if not p.sweep_y:
             x, y = np.arctan(vy / np.hypot(vz, tmp)), np.arctan(vz / tmp)
         else:
@@ -233,6 +246,161 @@ def _np_geos_forward_alt(p, lat, lon, alt):
         dlat = (alt * np.tan((lat - 0.0) * _D2R + y0 / p.h) / 6.371e6) * _R2D
         dlon = (alt * np.tan((lon - p.lon_0) * _D2R + x0 / p.h) / 6.371e6) * _R2D
     return _np_geos_forward(p, lat + dlat, lon + dlon)
+
+
+# ---- ECEF ------------------------------------------------------------------------------------------------------------------
+def _np_geodetic_to_ecef(a, f, lon, lat, alt):
+    """gd_geodetic_to_ecef_one over arrays"""
+    lon, lat, alt = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (lon, lat, alt)))
+    with np.errstate(all="ignore"):
+        e2 = f * (2.0 - f)
+        phi, lam = lat * _D2R, lon * _D2R
+        sp, cp = np.sin(phi), np.cos(phi)
+        n = a / np.sqrt(1.0 - e2 * sp * sp)
+        return (n + alt) * cp * np.cos(lam), (n + alt) * cp * np.sin(lam), (n * (1.0 - e2) + alt) * sp
+
+
+def _np_ecef_to_geodetic(a, f, X, Y, Z):
+    """gd_ecef_to_geodetic_one over arrays: Bowring, two updates -> (lon, lat, alt)"""
+    X, Y, Z = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (X, Y, Z)))
+    with np.errstate(all="ignore"):
+        p = np.hypot(X, Y)
+        e2, b = f * (2.0 - f), (1.0 - f) * a
+        ep2b, e2a = e2 / (1.0 - e2) * b, e2 * a
+        st, ct = Z, (1.0 - f) * p
+        for _ in range(2):
+            n = np.hypot(st, ct)
+            st, ct = st / n, ct / n
+            num = Z + ep2b * st * st * st
+            den = p - e2a * ct * ct * ct
+            st, ct = (1.0 - f) * num, den
+        n = np.hypot(num, den)
+        sp, cp = num / n, den / n
+        lon = np.arctan2(Y, X) * _R2D
+        lat = np.arctan2(num, den) * _R2D
+        alt = p * cp + Z * sp - a * np.sqrt(1.0 - e2 * sp * sp)
+        axis = p == 0.0
+        lon = np.where(axis, 0.0, lon)
+        lat = np.where(axis, np.where(Z > 0.0, 90.0, -90.0), lat)
+        alt = np.where(axis, np.abs(Z) - b, alt)
+        bad = ~(np.isfinite(X) & np.isfinite(Y) & np.isfinite(Z)) | (axis & (Z == 0.0))
+        return np.where(bad, np.nan, lon), np.where(bad, np.nan, lat), np.where(bad, np.nan, alt)
+
+
+def _np_geos_to_ecef(p, x, y):
+    """gd_geos_to_ecef_one over arrays: (X, Y, Z) in metres, +inf where the ray misses the ellipsoid"""
+    x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+    with np.errstate(all="ignore"):
+        dy, dz, k, det = _np_geos_ray(p, x, y)
+        vx, vy, vz = p._rg - k, dy * k, dz * k
+        resid = vx * vx + vy * vy + vz * vz * p._rp_inv2 - 1.0
+        slope = 2.0 * (vy * dy + vz * dz * p._rp_inv2 - vx)
+        dk = np.where(slope < 0.0, resid / slope, 0.0)
+        vx, vy, vz = vx + dk, vy - dk * dy, vz - dk * dz
+        l0 = p.lon_0 * _D2R
+        c0, s0 = np.cos(l0), np.sin(l0)
+        out = p.a * (vx * c0 - vy * s0), p.a * (vx * s0 + vy * c0), p.a * vz
+        bad = np.where(det < 0.0, np.inf, np.nan)
+        return tuple(np.where(det >= 0.0, v, bad) for v in out)
+
+
+def _second_ecc2(rf):
+    f = 1.0 / rf if rf else 0.0
+    e2 = f * (2.0 - f)
+    return e2 / (1.0 - e2)
+
+
+def _np_glm_parallax(grid, ltg, lla_a, lla_rf, lat, lon):
+    """gd_glm_parallax_one over arrays: (dlon, dlat, x, y, alt); the constants are gd_parallax_setup's"""
+    lat, lon = np.broadcast_arrays(np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64))
+    shift = (ltg.a - grid.a) + (ltg.h - grid.h)
+    shift_rel = shift / grid.a
+    ke = (grid.a - ltg.a) * (grid.a + ltg.a) / (ltg.a * ltg.a)
+    eg, el = _second_ecc2(grid.rf), _second_ecc2(ltg.rf)
+    kp = ke + el + ke * el - eg
+    me = 1.0 + ke
+    mp = me * (1.0 + el)
+    with np.errstate(all="ignore"):
+        vx, vy, vz, vis = _np_geos_surface(grid, lat, lon)
+        dx, wx = vx - grid._rg, vx + shift_rel
+        C = (vx * vx + vy * vy) * ke + vz * vz * kp + (2.0 * vx * shift_rel + shift_rel * shift_rel) * me
+        B = 2.0 * ((wx * dx + vy * vy) * me + vz * vz * mp)
+        A = (dx * dx + vy * vy) * me + vz * vz * mp
+        disc = B * B - 4.0 * A * C
+        tau = np.where(C != 0.0, 2.0 * C / (np.sqrt(disc) - B), 0.0)
+        qx = (grid.a * vx + shift) + tau * (grid.a * dx)
+        qy = grid.a * vy + tau * (grid.a * vy)
+        qz = grid.a * vz + tau * (grid.a * vz)
+        lon_q, lat_q, alt = _np_ecef_to_geodetic(lla_a, 1.0 / lla_rf if lla_rf else 0.0, qx, qy, qz)
+        lon_q = lon_q + grid.lon_0
+        lon_q = np.where(np.abs(lon_q) > 180.0, _ieee_remainder(lon_q, 360.0), lon_q)
+        hit = (vis >= 0.0) & (disc >= 0.0)
+        dlon, dlat = np.where(hit, lon_q - lon, np.nan), np.where(hit, lat_q - lat, np.nan)
+        x, y = _np_geos_forward(grid, lat - dlat, lon - dlon)
+        bad = np.where((vis < 0.0) | (disc < 0.0), np.inf, np.nan)
+        return dlon, dlat, np.where(hit, x, bad), np.where(hit, y, bad), np.where(hit, alt, np.nan)
+
+
+ECEF_FROM_GEODETIC, ECEF_TO_GEODETIC = 0, 1
+
+
+def _dev_ecef(mode, a, rf, v0, v1, v2):
+    lib = _lib()
+    t = lib.torch()
+    shape = t.broadcast_shapes(*(tuple(v.shape) if hasattr(v, "shape") else () for v in (v0, v1, v2)))
+    v0, v1, v2 = (_dev_f64(v, shape) for v in (v0, v1, v2))
+    out = [lib.empty(shape, t.float64) for _ in range(3)]
+    lib.check(lib.lib().tf_ecef(mode, a, rf, lib.ptr(v0), lib.ptr(v1), lib.ptr(v2), v0.numel(), lib.ptr(out[0]), lib.ptr(out[1]),
+                                lib.ptr(out[2]), lib.stream_ptr()), "tf_ecef")
+    return tuple(out)
+
+
+def geodetic_to_ecef(lon, lat, alt=0.0, ellps="WGS84", a=None, rf=None):
+    """`(X, Y, Z)` in metres of geodetic longitude, latitude (degrees) and height (metres) on the ellipsoid: what pyproj's
+    latlong -> geocent transform gives.  The inputs broadcast; the argument order is pyproj's."""
+    a, rf = _ellipsoid(ellps, a, rf)
+    lon, lat, alt = (_unwrap(v) for v in (lon, lat, alt))
+    if _any_tensor(lon, lat, alt):
+        return _dev_ecef(ECEF_FROM_GEODETIC, a, rf, lon, lat, alt)
+    return _np_geodetic_to_ecef(a, 1.0 / rf if rf else 0.0, lon, lat, alt)
+
+
+def ecef_to_geodetic(X, Y, Z, ellps="WGS84", a=None, rf=None):
+    """`(lon, lat, alt)` of ECEF metres on the ellipsoid: pyproj's geocent -> latlong, by Bowring's iteration with two
+    updates (within 1e-16 rad up to 160 km above the ellipsoid).  On the polar axis lon = 0 and lat = +-90; the origin,
+    NaN and infinite coordinates give NaN."""
+    a, rf = _ellipsoid(ellps, a, rf)
+    X, Y, Z = (_unwrap(v) for v in (X, Y, Z))
+    if _any_tensor(X, Y, Z):
+        return _dev_ecef(ECEF_TO_GEODETIC, a, rf, X, Y, Z)
+    return _np_ecef_to_geodetic(a, 1.0 / rf if rf else 0.0, X, Y, Z)
+
+
+def glm_parallax(grid, ltg, lla, lat, lon, offsets=True, scan_angles=True):
+    """The GLM parallax correction for flashes at (lat, lon) degrees: `(dlon, dlat, x, y)` -- the offsets of
+    glm.get_glm_parallax_offsets and the scan angles of the corrected positions on `grid`; a pair that is not asked for is
+    None.  grid: the GeosProj of the ABI file; ltg: the GeosProj of the lightning ellipsoid (same lon_0 and sweep);
+    lla: (a, rf) of the ellipsoid the lightning point is read on.  float32 or float64 in (float32 is widened exactly),
+    float64 out; device tensors in: one launch of tf_glm_parallax.  A flash beyond the limb, or whose ray misses the
+    lightning ellipsoid: NaN offsets, +inf scan angles."""
+    lat, lon = _unwrap(lat), _unwrap(lon)
+    if ltg.lon_0 != grid.lon_0 or ltg.sweep_y != grid.sweep_y:
+        raise ValueError("the lightning system shares lon_0 and the sweep axis with the grid's")
+    if _any_tensor(lat, lon):
+        lib = _lib()
+        t = lib.torch()
+        lat, lon = (v if _is_tensor(v) else t.from_numpy(np.ascontiguousarray(v)) for v in (lat, lon))
+        shape = t.broadcast_shapes(tuple(lat.shape), tuple(lon.shape))
+        dtype = t.float32 if lat.dtype == lon.dtype == t.float32 else t.float64
+        lat, lon = (v.to(lib.device(), dtype).expand(shape).contiguous() for v in (lat, lon))
+        out = [lib.empty(shape, t.float64) if want else None for want in (offsets, offsets, scan_angles, scan_angles)]
+        g, l = grid._params(), ltg._params()
+        lib.check(lib.lib().tf_glm_parallax(ctypes.byref(g), ctypes.byref(l), lla[0], lla[1], lib.ptr(lat), lib.ptr(lon),
+                                            lib.TF_F32 if dtype == t.float32 else lib.TF_F64, lat.numel(), lib.ptr(out[0]),
+                                            lib.ptr(out[1]), lib.ptr(out[2]), lib.ptr(out[3]), lib.stream_ptr()), "tf_glm_parallax")
+        return tuple(out)
+    dlon, dlat, x, y, _ = _np_glm_parallax(grid, ltg, lla[0], lla[1], lat, lon)
+    return (dlon if offsets else None, dlat if offsets else None, x if scan_angles else None, y if scan_angles else None)
 
 
 class GeosProj:
@@ -324,6 +492,29 @@ class GeosProj:
         if alt is None:
             return _np_geos_forward(self, lat, lon)
         return _np_geos_forward_alt(self, lat, lon, alt)
+
+    def to_ecef(self, x, y):
+        """scan angles (radians) -> ECEF `(X, Y, Z)` in metres of the nearer point at which the ray meets this projection's
+        ellipsoid, +inf in all three where it misses: Transformer.from_crs(geos, geocent) at height 0"""
+        x, y = _unwrap(x), _unwrap(y)
+        if _any_tensor(x, y):
+            lib = _lib()
+            t = lib.torch()
+            shape = t.broadcast_shapes(*(tuple(v.shape) if hasattr(v, "shape") else () for v in (x, y)))
+            x, y = _dev_f64(x, shape), _dev_f64(y, shape)
+            out = [lib.empty(shape, t.float64) for _ in range(3)]
+            geos = self._params()
+            lib.check(lib.lib().tf_geos_to_ecef(ctypes.byref(geos), lib.ptr(x), lib.ptr(y), x.numel(), lib.ptr(out[0]),
+                                                lib.ptr(out[1]), lib.ptr(out[2]), lib.stream_ptr()), "tf_geos_to_ecef")
+            return tuple(out)
+        return _np_geos_to_ecef(self, x, y)
+
+    def from_ecef(self, X, Y, Z):
+        """ECEF metres -> `(x, y, alt)`: the scan angles (radians) of the geodetic position on this projection's ellipsoid,
+        +inf beyond the limb, and the height above it in metres"""
+        lon, lat, alt = ecef_to_geodetic(X, Y, Z, a=self.a, rf=self.rf)
+        x, y = self.forward_points(lat, lon)
+        return x, y, alt
 
     def __call__(self, x, y, inverse=False):
         x, y = _unwrap(x), _unwrap(y)

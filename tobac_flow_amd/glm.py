@@ -1,17 +1,23 @@
-"""GLM flashes onto the ABI grid on the GPU: the array-level form of tobac_flow/glm.py:77-145 (regrid_glm with
-get_uncorrected_glm_hist / get_corrected_glm_hist).  The reference opens every flash file inside the window of every
-frame and calls np.histogram2d once per frame; here the flashes of all files are binned onto the whole (T, H, W) stack by
-one launch of tf_bin_points (tobac_flow_amd.binning).  Reading the files stays with the caller.  The projection to ABI
-coordinates is tobac_flow_amd.abi.get_abi_x_y (tf_geos_forward: device tensors in, device tensors out), whose x and y go
-in here as they are.  The GLM parallax correction (get_glm_parallax_offsets and the lmatools coordinate systems behind it)
-is not taken: for the "corrected" grid the caller hands in corrected coordinates.
+"""GLM flashes onto the ABI grid on the GPU: the array-level form of tobac_flow/glm.py (regrid_glm with
+get_uncorrected_glm_hist / get_corrected_glm_hist, and create_gridded_flash_ds above them).  The reference opens every
+flash file inside the window of every frame and calls np.histogram2d once per frame; here the flashes of all files are
+binned onto the whole (T, H, W) stack by one launch of tf_bin_points (tobac_flow_amd.binning).  Reading the files stays
+with the caller: where the reference takes `glm_files`, the functions here take the flashes of all files as arrays --
+flash_lat, flash_lon, flash_file (for every flash the index of its file) -- and file_times.
+
+`regrid_glm` takes projected coordinates.  `regrid_glm_lat_lon` takes latitudes and longitudes and projects them itself:
+uncorrected by tobac_flow_amd.abi.get_abi_x_y (tf_geos_forward), or corrected for the GLM parallax (glm.py:25-57:
+get_glm_parallax_offsets through the lmatools coordinate systems, tobac_flow_amd._lmatools) by one launch of
+tf_glm_parallax per call.  Device tensors in, device tensors out, nothing visits the host; NumPy arrays in, NumPy out.
 
 The counts equal the reference's bit for bit.  The result feeds tobac_flow_amd.validation (`glm_grid`)."""
 from datetime import datetime, timedelta
 
 import numpy as np
 
+from tobac_flow_amd import _lmatools, abi, geo
 from tobac_flow_amd.binning import _is_tensor, _lib, bin_points, time_ticks
+from tobac_flow_amd.utils.xarray_utils import get_coord_bin_edges
 
 _EPOCH = datetime(1970, 1, 1)
 
@@ -73,3 +79,149 @@ def regrid_glm(flash_x, flash_y, flash_file, file_times, goes_dates, x_bins, y_b
     if not has_file.all():
         grid[lib.to_dev((~has_file).astype(np.uint8)).to(t.bool)] = -1
     return grid if device else lib.to_host(grid).astype(np.int64)
+
+
+# ---- from latitude and longitude -------------------------------------------------------------------------------------------
+def _parallax_systems(goes_ds, ellipse_rev=0):
+    """(grid, ltg, lla): the file's projection, the GOES-R fixed grid on the lightning ellipsoid over the same nadir
+    (_lmatools.get_GOESR_coordsys_alt_ellps) and the ellipsoid of _lmatools.get_GOESR_coordsys' geographic system"""
+    grid = abi.get_abi_proj(goes_ds)
+    re, rp = _lmatools.lightning_ellipse_rev[ellipse_rev]
+    ltg = geo.GeosProj(h=_lmatools.GOESR_SAT_ECEF_HEIGHT, lon_0=grid.lon_0, sweep="x", a=re,
+                       rf=_lmatools.semiaxes_to_invflattening(re, rp))
+    return grid, ltg, geo.ELLIPSOIDS["GRS80"]
+
+
+def get_glm_parallax_offsets(lon, lat, goes_ds, ellipse_rev=0):
+    """`(lon_offset, lat_offset)` in degrees of GLM flashes at (lon, lat), float32 or float64 (reference: glm.py:25-37):
+    where the ray towards the flash's position on the ABI's ellipsoid meets the lightning ellipsoid
+    `_lmatools.lightning_ellipse_rev[ellipse_rev]`, read as longitude and latitude on GRS80, minus the flash's own.  NaN
+    beyond the limb.  Device tensors in: one launch of tf_glm_parallax."""
+    grid, ltg, lla = _parallax_systems(goes_ds, ellipse_rev)
+    return geo.glm_parallax(grid, ltg, lla, lat, lon, scan_angles=False)[:2]
+
+
+def _n_flashes(v):
+    return int(v.numel()) if _is_tensor(v) else int(np.size(v))
+
+
+def get_corrected_glm_x_y(flash_lon, flash_lat, goes_ds):
+    """the ABI scan angles `(x, y)` of flashes moved back by their parallax offsets, +inf beyond the limb (reference:
+    glm.py:40-57, the file's flash_lon and flash_lat handed in).  Device tensors in: the same single launch."""
+    if _n_flashes(flash_lon) == 0 and not _is_tensor(flash_lon):
+        return np.array([]), np.array([])
+    grid, ltg, lla = _parallax_systems(goes_ds)
+    return geo.glm_parallax(grid, ltg, lla, flash_lat, flash_lon, offsets=False)[2:]
+
+
+def get_uncorrected_glm_x_y(flash_lon, flash_lat, goes_ds):
+    """the ABI scan angles `(x, y)` of flashes as they are (reference: glm.py:60-74)"""
+    if _n_flashes(flash_lon) == 0 and not _is_tensor(flash_lon):
+        return np.array([]), np.array([])
+    return abi.get_abi_x_y(flash_lat, flash_lon, goes_ds)
+
+
+def _np_regrid(flash_x, flash_y, flash_file, file_times, goes_dates, x_bins, y_bins, max_time_diff):
+    """regrid_glm as the reference runs it, np.histogram2d per frame: the host path of a machine without a HIP device"""
+    start, end = glm_windows(goes_dates, max_time_diff)
+    files = time_ticks(file_times)
+    flash_file = np.asarray(flash_file)
+    if flash_file.size and (flash_file.min() < 0 or flash_file.max() >= files.size):
+        raise ValueError("flash_file holds an index outside file_times")
+    x_bins, y_bins = np.asarray(x_bins, dtype=np.float64), np.asarray(y_bins, dtype=np.float64)
+    grid = np.full((start.size, y_bins.size - 1, x_bins.size - 1), -1, dtype=np.int64)
+    for i, (s, e) in enumerate(zip(start, end)):
+        inside = (files > s) & (files < e)
+        if inside.any():
+            pick = inside[flash_file]
+            grid[i] = np.histogram2d(np.asarray(flash_y)[pick], np.asarray(flash_x)[pick], bins=(y_bins[::-1], x_bins))[0][::-1]
+    return grid
+
+
+def _regrid_lat_lon(flash_lat, flash_lon, flash_file, file_times, goes_ds, goes_dates, x_bins, y_bins, corrected, max_time_diff, device):
+    tensors = any(_is_tensor(a) for a in (flash_lat, flash_lon, flash_file))
+    if device is False and tensors:
+        raise ValueError("device=False with flashes that are device tensors")
+    if device is None:
+        device = tensors or _lib().torch().cuda.is_available()
+    elif device and not tensors:                                  # device=True: NumPy in, device tensors out
+        lib = _lib()
+        flash_lat, flash_lon, flash_file = (lib.to_dev(np.ascontiguousarray(a)) for a in (flash_lat, flash_lon, flash_file))
+    project = get_corrected_glm_x_y if corrected else get_uncorrected_glm_x_y
+    flash_x, flash_y = project(flash_lon, flash_lat, goes_ds)
+    if device:
+        return regrid_glm(flash_x, flash_y, flash_file, file_times, goes_dates, x_bins, y_bins, max_time_diff)
+    return _np_regrid(flash_x, flash_y, flash_file, file_times, goes_dates, x_bins, y_bins, max_time_diff)
+
+
+def regrid_glm_lat_lon(flash_lat, flash_lon, flash_file, file_times, goes_ds, goes_dates, x_bins, y_bins, corrected=False,
+                       max_time_diff=15):
+    """regrid_glm from the flashes' latitudes and longitudes (float32 as in a GLM file, or float64; the arithmetic is
+    float64 either way): projected onto the grid of `goes_ds` as they are, or with `corrected` moved back by the GLM
+    parallax first -- what the reference's regrid_glm(glm_files, goes_ds, corrected) does per file (glm.py:107-145).  The
+    other arguments, the -1 of a frame without a file and the result are regrid_glm's.  Device tensors in: two launches,
+    the projection and the binning, and the grid stays on the device.  NumPy arrays in: the projection is the NumPy path;
+    the binning is regrid_glm's launch where a HIP device is visible and np.histogram2d per frame where none is."""
+    return _regrid_lat_lon(flash_lat, flash_lon, flash_file, file_times, goes_ds, goes_dates, x_bins, y_bins, corrected,
+                           max_time_diff, None)
+
+
+def _window_hist(flash_lat, flash_lon, flash_file, file_times, goes_ds, start_time, end_time, corrected):
+    """np.histogram2d(y, x, bins=(y_bins[::-1], x_bins))[0][::-1] over the flashes of the files with
+    start_time < t < end_time, float64 like np.histogram2d's; no such file is a ValueError (in the reference
+    np.concatenate of nothing raises it, and regrid_glm leaves the frame at -1)"""
+    files = time_ticks(file_times)
+    if _is_tensor(files):
+        files = files.cpu().numpy()
+    start, end = (int(time_ticks(np.asarray(v, dtype="datetime64[us]").reshape(1))[0]) for v in (start_time, end_time))
+    inside = (files > start) & (files < end)
+    if not inside.any():
+        raise ValueError("no GLM file between start_time and end_time")
+    x_bins, y_bins = (get_coord_bin_edges(v.cpu().numpy() if _is_tensor(v) else v) for v in (abi._values(goes_ds.x), abi._values(goes_ds.y)))
+    tensors = any(_is_tensor(a) for a in (flash_lat, flash_lon, flash_file))
+    project = get_corrected_glm_x_y if corrected else get_uncorrected_glm_x_y
+    flash_x, flash_y = project(flash_lon, flash_lat, goes_ds)
+    y_rev = np.ascontiguousarray(y_bins[::-1])
+    if not (tensors or _lib().torch().cuda.is_available()):
+        pick = inside[np.asarray(flash_file)]
+        return np.histogram2d(flash_y[pick], flash_x[pick], bins=(y_rev, x_bins))[0][::-1]
+    lib = _lib()
+    t = lib.torch()
+    keep = lib.to_dev(inside.astype(np.uint8))[lib.to_dev(flash_file).to(t.int64)]
+    hist = bin_points([flash_y, flash_x], [y_rev, x_bins], keep=keep, flip=(0,), outputs=("count",))["count"][0].to(t.float64)
+    return hist if tensors else lib.to_host(hist)
+
+
+def get_corrected_glm_hist(flash_lat, flash_lon, flash_file, file_times, goes_ds, start_time, end_time):
+    """the (H, W) flash counts of one window on the grid of `goes_ds`, parallax-corrected (reference: glm.py:77-89)"""
+    return _window_hist(flash_lat, flash_lon, flash_file, file_times, goes_ds, start_time, end_time, True)
+
+
+def get_uncorrected_glm_hist(flash_lat, flash_lon, flash_file, file_times, goes_ds, start_time, end_time):
+    """the (H, W) flash counts of one window on the grid of `goes_ds`, flashes as they are (reference: glm.py:92-104)"""
+    return _window_hist(flash_lat, flash_lon, flash_file, file_times, goes_ds, start_time, end_time, False)
+
+
+def create_gridded_flash_ds(detection_ds, flash_lat, flash_lon, flash_file, file_times, device=None):
+    """The gridded flash product of glm.py:148-220: dataset.create_new_goes_ds(detection_ds) -- `lat`, `lon`, `area` on the
+    grid -- plus `glm_flashes`, int32 on (t, y, x): regrid_glm_lat_lon(..., corrected=True) on the frames `detection_ds.t`,
+    -1 where no file covers a frame; and `glm_flash_count`, int32 of shape (): the sum of its positive entries.  A
+    LabelDataset; finding, downloading and reading the GLM files stays with the caller (no file at all is the reference's
+    ValueError), and so does writing the result.  device: create_new_goes_ds' switch -- None: device tensors out for flashes
+    that are device tensors, NumPy out otherwise (computed on the GPU where one is visible); True: device tensors out;
+    False: the NumPy path."""
+    from tobac_flow_amd.dataset import create_new_goes_ds
+    if time_ticks(file_times).shape[0] == 0:
+        raise ValueError("No GLM Files discovered, skipping validation")
+    tensors = any(_is_tensor(a) for a in (flash_lat, flash_lon, flash_file))
+    ds = create_new_goes_ds(detection_ds, device=True if tensors and device is None else device)
+    x_bins, y_bins = get_coord_bin_edges(ds.coords["x"]), get_coord_bin_edges(ds.coords["y"])
+    grid = _regrid_lat_lon(flash_lat, flash_lon, flash_file, file_times, ds, ds.coords["t"], x_bins, y_bins, True, 15, device)
+    if _is_tensor(grid):
+        t = _lib().torch()
+        ds.add("glm_flashes", grid.to(t.int32), ("t", "y", "x"))
+        ds.add("glm_flash_count", grid.clamp(min=0).sum().to(t.int32), ())
+    else:
+        ds.add("glm_flashes", grid, ("t", "y", "x"), np.int32)
+        ds.add("glm_flash_count", np.sum(grid[grid > 0]), (), np.int32)
+    return ds

@@ -4,6 +4,8 @@ copy kernel in the same run and to the package's NumPy path on this machine's CP
   grid inverse     tf_geos_inverse on N x N (float64 and float32 out) against tf_copy16 over buffers of the float64 outputs' size
   spacing          tf_grid_spacing on the N x N lat / lon (area alone, and dx, dy, area), and the whole create_new_goes_ds
   points           tf_geod_inverse and tf_geos_forward (without and with alt) on P points
+  GLM parallax     tf_glm_parallax on P flashes (float32 and float64 in), tf_ecef in both modes on P points, and
+                   glm.regrid_glm_lat_lon end to end onto a FRAMES x N x N grid, corrected against uncorrected
 
 Device events around the entry point alone, operands on the device; create_new_goes_ds by a host clock around a
 synchronise.  Median (min .. max) of RUNS windows of REPS calls each, per call, after WARM warm-ups.  The NumPy path runs on a CPU_SHARE-th of the rows / points
@@ -18,12 +20,14 @@ sys.path.insert(0, ".")
 import numpy as np
 import torch
 
-from tobac_flow_amd import _lib, dataset, geo
+from tobac_flow_amd import _lib, _lmatools, dataset, geo, glm
+from tobac_flow_amd.utils.xarray_utils import get_coord_bin_edges
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 5424
 P = int(sys.argv[2]) if len(sys.argv) > 2 else 10 ** 7
 OUT = open(sys.argv[3], "w") if len(sys.argv) > 3 else None
 WARM, RUNS, REPS, CPU_SHARE = 2, 9, 20, 10
+FRAMES = 16
 H_GOES, LON_0 = 35786023.0, -75.0
 
 
@@ -140,6 +144,39 @@ def main():
                                                         _lib.ptr(out[1]), _lib.stream_ptr()), "tf_geos_forward"))
         say(f"tf_geos_forward{label:<9} {P} points                          {fmt(t)}   {P / t[0] / 1e6:.2f} G points/s, {P * moved / t[0] / 1e6:.0f} GB/s moved")
 
+    ltg = geo.GeosProj(H_GOES, LON_0, a=_lmatools.ltg_ellps_re, rf=_lmatools.semiaxes_to_invflattening(_lmatools.ltg_ellps_re, _lmatools.ltg_ellps_rp))
+    ltg_geos = ltg._params()
+    lla = geo.ELLIPSOIDS["GRS80"]
+    more = [torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2)]
+    for label, code, size, flat, flon in (("float64", _lib.TF_F64, 8, dp[0], dp[1]), ("float32", _lib.TF_F32, 4, dp[0].float(), dp[1].float())):
+        for what, outs, stored in (("offsets and scan angles", (out[0], out[1], more[0], more[1]), 32), ("scan angles alone", (None, None, out[0], out[1]), 16)):
+            t = timed(lambda: _lib.check(L.tf_glm_parallax(ctypes.byref(geos), ctypes.byref(ltg_geos), lla[0], lla[1], _lib.ptr(flat), _lib.ptr(flon), code, P,
+                                                            _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.ptr(outs[3]), _lib.stream_ptr()),
+                                         "tf_glm_parallax"))
+            say(f"tf_glm_parallax {P} flashes, {label} in, {what:<24}    {fmt(t)}   {P / t[0] / 1e6:.2f} G flashes/s, "
+                f"{P * (2 * size + stored) / t[0] / 1e6:.0f} GB/s moved")
+    ecef = [torch.empty(P, dtype=torch.float64, device=dev) for _ in range(3)]
+    t = timed(lambda: _lib.check(L.tf_ecef(_lib.ECEF_FROM_GEODETIC, lla[0], lla[1], _lib.ptr(dp[1]), _lib.ptr(dp[0]), _lib.ptr(dp[2]), P, _lib.ptr(ecef[0]),
+                                           _lib.ptr(ecef[1]), _lib.ptr(ecef[2]), _lib.stream_ptr()), "tf_ecef"))
+    say(f"tf_ecef geodetic -> ECEF {P} points                          {fmt(t)}   {P / t[0] / 1e6:.2f} G points/s, {P * 48 / t[0] / 1e6:.0f} GB/s moved")
+    t = timed(lambda: _lib.check(L.tf_ecef(_lib.ECEF_TO_GEODETIC, lla[0], lla[1], _lib.ptr(ecef[0]), _lib.ptr(ecef[1]), _lib.ptr(ecef[2]), P, _lib.ptr(out[0]),
+                                           _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_ptr()), "tf_ecef"))
+    say(f"tf_ecef ECEF -> geodetic {P} points                          {fmt(t)}   {P / t[0] / 1e6:.2f} G points/s, {P * 48 / t[0] / 1e6:.0f} GB/s moved")
+    del ecef, more
+
+    grid_ds = Abi()
+    grid_ds.x, grid_ds.y = x_host, y_host
+    x_bins, y_bins = get_coord_bin_edges(x_host), get_coord_bin_edges(y_host)
+    start = np.datetime64("2018-06-19T17:00:00", "us")
+    goes_dates = start + np.arange(FRAMES) * np.timedelta64(300, "s")
+    file_times = start - np.timedelta64(140, "s") + np.arange(FRAMES * 15) * np.timedelta64(20, "s")
+    flash_file = torch.from_numpy(rng.integers(0, file_times.size, P)).to(dev)
+    flat, flon = dp[0].float(), dp[1].float()
+    for corrected in (False, True):
+        t = timed(lambda: glm.regrid_glm_lat_lon(flat, flon, flash_file, file_times, grid_ds, goes_dates, x_bins, y_bins, corrected=corrected), wall, 1)
+        say(f"regrid_glm_lat_lon {P} float32 flashes -> {FRAMES} x {N} x {N}, corrected={corrected!s:<5} (wall)   {fmt(t)}")
+    del flash_file, flat, flon
+
     say(f"NumPy path on this machine's CPU, one call on a {CPU_SHARE}th of the work, scaled by {CPU_SHARE}:")
     rows = max(2, N // CPU_SHARE)
 
@@ -158,6 +195,12 @@ def main():
     say(f"  forward_points {P}                       {t:10.0f} ms")
     t, _ = cpu(lambda: p.forward_points(plat[:m], plon[:m], alt[:m]))
     say(f"  forward_points with alt {P}              {t:10.0f} ms")
+    t, _ = cpu(lambda: geo.glm_parallax(p, ltg, lla, plat[:m], plon[:m]))
+    say(f"  glm_parallax {P}                         {t:10.0f} ms")
+    t, xyz = cpu(lambda: geo.geodetic_to_ecef(plon[:m], plat[:m], alt[:m], ellps="GRS80"))
+    say(f"  geodetic_to_ecef {P}                     {t:10.0f} ms")
+    t, _ = cpu(lambda: geo.ecef_to_geodetic(*xyz, ellps="GRS80"))
+    say(f"  ecef_to_geodetic {P}                     {t:10.0f} ms")
 
 
 if __name__ == "__main__":
