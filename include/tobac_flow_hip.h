@@ -540,9 +540,6 @@ int tf_watershed_raveled_ex(const float *image, int64_t n, const int64_t *marker
  *   (tobac_flow/detection.py:80-93, 509, 551-553, 571-573, 608-616; binary_opening = erosion then dilation).
  *   tmp: scratch of the same size, required when iterations > 1.
  * tf_linearise: tobac_flow/utils/normalisation_utils.py:36-56 linearise_field in float32.
- * tf_label_extent: per label 1..n_labels the first / last leading index (tobac_flow/analysis.py:15-35
- *   find_object_lengths = tmax - tmin + 1) and whether it touches `mask` (analysis.py:38-63 mask_labels);
- *   arrays of n_labels + 1 entries, entry 0 unused; absent labels: tmin = 0x7f7f7f7f, tmax = -1.
  * tf_apply_lut: out = lut[labels] (tobac_flow/utils/label_utils.py:265-309 remap_labels' gather). */
 /* tf_correlate1d_sym: one pass of scipy.ndimage.correlate1d along `axis` (0 = t, 1 = y, 2 = x) with a SYMMETRIC kernel
  *   of 2*radius+1 host doubles, mode 'reflect' -- the pass scipy.ndimage.gaussian_filter is made of
@@ -559,8 +556,6 @@ int tf_grey_morph(const void *in, int type, int64_t T, int64_t H, int64_t W, con
 int tf_binary_morph(const uint8_t *in, int64_t T, int64_t H, int64_t W, const uint8_t *structure_host,
                     int op, int iterations, int border_value, uint8_t *out, uint8_t *tmp, void *stream);
 int tf_linearise(const float *field, int64_t n, double lower, double upper, float *out, void *stream);
-int tf_label_extent(const int32_t *labels, const uint8_t *mask, int64_t T, int64_t H, int64_t W, int n_labels,
-                    int *tmin, int *tmax, uint8_t *hit, void *stream);
 int tf_apply_lut(const int32_t *labels, int64_t n, const int32_t *lut, int n_lut, int32_t *out, void *stream);
 /* tf_label_filter (version 107): tobac_flow/analysis.py:15-201 -- what find_object_lengths, mask_labels and the
  *   filter_labels_by_* family ask of one int32 (T, H, W) label volume, in ONE read of it: per label id 0 .. n_labels a
@@ -574,7 +569,7 @@ int tf_apply_lut(const int32_t *labels, int64_t n, const int32_t *lut, int n_lut
  *                            A NaN in the field satisfies nothing.
  *   Criterion operands are read only under voxels whose label lies in [1, n_labels]; ids outside are skipped, so record 0
  *   stays empty.  The call initialises the records itself; a label that does not occur keeps { 0x7fffffff, -1, 0, 0 }, so
- *   it is absent exactly when its last index is -1.  Shape contract as tf_label_extent (T < 65536); 64-bit indexing;
+ *   it is absent exactly when its last index is -1.  Shape contract: 0 < T < 65536; 64-bit indexing;
  *   `records` 16-byte aligned.  Every value is exact (integer atomics only).  TF_EINVAL before any launch: null pointers,
  *   n_criteria outside 0 .. 8, a criterion without data, an unknown dtype or op, a NaN threshold. */
 #define TF_CMP_GE 0
@@ -772,7 +767,7 @@ int tf_label_stats(const int32_t *labels, const float *field, const float *weigh
  *   area, lat, lon: (H, W) doubles; x: (W,), y: (H,) doubles; t_rank: (T,) int32 >= 0 -- the operands as they are, never
  *   broadcast to the volume; besides the labels nothing of T * H * W elements is read or allocated.  A NULL operand
  *   switches its sums off (they stay 0; NULL area switches k = 1 .. 6 off, NULL t_rank k = 7).  Ids outside
- *   [1, n_labels] are skipped, so record 0 stays empty.  Shape contract as tf_label_extent (T < 65536); 64-bit indexing.
+ *   [1, n_labels] are skipped, so record 0 stays empty.  Shape contract: 0 < T < 65536; 64-bit indexing.
  *   The sums are double atomics, one set per run of equal labels inside a lane's 16 voxels of a row: as with
  *   tf_label_stats the last bits of a sum depend on arrival order and can differ from run to run (N terms: N * 2^-53
  *   relative for terms of one sign); counts and the two ranks are exact. */

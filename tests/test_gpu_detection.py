@@ -269,7 +269,8 @@ def test_device_glue_matches_numpy_glue(scene):
         assert np.array_equal(get_watershed_mask(torch.from_numpy(lin).cuda(), e).cpu().numpy(), get_watershed_mask(lin, e))
     lab = ndi.label(lin > 0.3)[0].astype(np.int32)
     msk = lin >= 1
-    lengths, hit = nd.label_extent(torch.from_numpy(lab).cuda(), torch.from_numpy(msk).cuda())
+    lengths, hits, _ = nd.label_filter(torch.from_numpy(lab).cuda(), [torch.from_numpy(msk).cuda()])
+    hit = hits[:, 0]
     assert np.array_equal(lengths, find_object_lengths(lab)) and np.array_equal(hit, mask_labels(lab, msk))
     keep = np.logical_and(lengths > 1, hit)
     assert np.array_equal(nd.remap_labels(torch.from_numpy(lab).cuda(), keep).cpu().numpy(), remap_labels(lab, keep))
@@ -475,6 +476,58 @@ def test_detect_growth_markers_without_survivors_behaves_like_the_reference(scen
         assert outcome[0][1] is outcome[1][1] is ValueError
     else:
         assert np.array_equal(outcome[0][1], outcome[1][1]) and outcome[0][1].max() == 0
+
+
+@pytest.mark.parametrize("emptied_after", [None, 0, 1, 2])
+def test_growth_marker_filter_in_one_pass_equals_the_three_host_stages(emptied_after):
+    """detect_growth_markers filters by length, then by two masks, renumbering after each stage; the device form measures
+    once and renumbers once.  Hand-made labels: 1 lasts two frames (and touches both masks), 2 lasts four and misses the
+    first mask, 3 lasts four, touches the first and misses the second, 4 and 5 pass everything.  The variants leave nothing
+    after stage 0, 1 or 2: both forms must then return equal arrays or raise the same exception type."""
+    import torch
+    from tobac_flow_amd.analysis import filter_labels_by_length, filter_labels_by_mask
+    from tobac_flow_amd.detection import _growth_marker_filter_dev
+    lab = np.zeros((5, 4, 6), np.int32)
+    lab[0:2, 0, 0:2] = 1
+    lab[0:4, 1, 0:3] = 2
+    lab[1:5, 2, 1:4] = 3
+    lab[0:5, 3, 0:2] = 4
+    lab[1:4, 3, 4:6] = 5
+    filtered = np.zeros(lab.shape, np.float64)
+    wvd = np.full(lab.shape, -10.0, np.float32)
+    filtered[1, 0, 0] = filtered[2, 2, 2] = filtered[4, 3, 1] = 0.5
+    filtered[3, 3, 5] = 2.0
+    wvd[0, 0, 1] = wvd[3, 1, 0] = wvd[0, 3, 0] = -5.0
+    wvd[2, 3, 4] = 1.0
+    if emptied_after == 0:
+        lab[2:] = 0                                                     # nothing lasts three frames
+    elif emptied_after == 1:
+        filtered[lab > 1] = 0.25                                        # only the short label touches filtered >= 0.5
+    elif emptied_after == 2:
+        wvd[lab > 3] = -5.5                                             # labels 4 and 5 miss wvd >= -5
+
+    def host():
+        out = filter_labels_by_length(lab.copy(), 3)
+        out = filter_labels_by_mask(out, filtered >= 0.5)
+        return filter_labels_by_mask(out, wvd >= -5)
+
+    def device():
+        return _growth_marker_filter_dev(*(torch.from_numpy(a).cuda() for a in (lab, filtered, wvd))).cpu().numpy()
+
+    outcome = []
+    for fn in (host, device):
+        try:
+            outcome.append(("ok", fn()))
+        except Exception as e:                                       # noqa: BLE001 - the type is what is compared
+            outcome.append(("raised", type(e)))
+    assert outcome[0][0] == outcome[1][0]
+    if outcome[0][0] == "raised":
+        assert outcome[0][1] is outcome[1][1] and emptied_after in (0, 1)
+    else:
+        assert np.array_equal(outcome[0][1], outcome[1][1])
+        assert outcome[0][1].max() == (2 if emptied_after is None else 0)
+        if emptied_after is None:
+            assert np.array_equal(outcome[0][1], (lab == 4) + 2 * (lab == 5))
 
 
 def test_peak_local_max_2d_on_device_equals_scikit_image_goldens():

@@ -346,11 +346,12 @@ def test_remap_labels_equals_the_host_function(nd):
         assert np.array_equal(nd.remap_labels(torch.from_numpy(lab).cuda(), keep).cpu().numpy(), remap_labels(lab, keep))
 
 
-# ----------------------------------------------------------------------------- tf_label_extent
+# ----------------------------------------------------------------------------- tf_label_filter with zero or one TF_U8 criterion
 @pytest.mark.parametrize("shape", [(1, 7, 9), (4, 5, 13), (6, 1, 33), (3, 16, 16)], ids=lambda s: "x".join(map(str, s)))
-def test_label_extent_ignores_foreign_labels_and_sees_the_last_frame(L, shape):
-    """Labels above n_labels and negative labels are ignored; mask = NULL leaves `hit` zero; T = 1; a label that occurs in
-    the last frame only.  tmin / tmax / hit have n_labels + 1 entries, guarded on both sides."""
+def test_label_filter_ignores_foreign_labels_and_sees_the_last_frame(L, shape):
+    """Labels above n_labels and negative labels are ignored; no criterion leaves the hit bits zero; T = 1; a label that
+    occurs in the last frame only.  The records {tmin, tmax, hits, 0} have n_labels + 1 entries, guarded on both sides."""
+    from tobac_flow_amd import _lib
     T, H, W = shape
     rng = np.random.default_rng(sum(shape))
     n_labels = 9
@@ -362,29 +363,30 @@ def test_label_extent_ignores_foreign_labels_and_sees_the_last_frame(L, shape):
     for with_mask in (True, False):
         src = Guarded(lab.size, np.int32, 0, lab)
         m = Guarded(lab.size, np.uint8, 1, mask)
-        tmin, tmax, hit = (Guarded(n_labels + 1, d) for d in (np.int32, np.int32, np.uint8))
-        assert L.tf_label_extent(src.ptr, m.ptr if with_mask else None, T, H, W, n_labels, tmin.ptr, tmax.ptr, hit.ptr, _stream()) == 0
-        w_min, w_max, w_hit = np.full(n_labels + 1, 0x7f7f7f7f, np.int32), np.full(n_labels + 1, -1, np.int32), np.zeros(n_labels + 1, np.uint8)
+        rec = Guarded(4 * (n_labels + 1), np.int32)
+        crit = (_lib.LabelCriterion * 1)(_lib.LabelCriterion(m.ptr.value, _lib.TF_U8, 0, 0.0))
+        assert L.tf_label_filter(src.ptr, T, H, W, n_labels, crit, int(with_mask), rec.ptr, _stream()) == 0
+        want = np.tile(np.array([0x7fffffff, -1, 0, 0], np.int32), (n_labels + 1, 1))
         for l in range(1, n_labels + 1):
             frames = np.nonzero((lab == l).any((1, 2)))[0]
             if frames.size:
-                w_min[l], w_max[l] = frames[0], frames[-1]
-            w_hit[l] = with_mask and bool(((lab == l) & (mask != 0)).any())
-        assert np.array_equal(tmin.host(), w_min) and np.array_equal(tmax.host(), w_max) and np.array_equal(hit.host(), w_hit)
-        assert w_max[7] == T - 1 == w_min[7] and w_max[4] == -1
+                want[l, 0], want[l, 1] = frames[0], frames[-1]
+            want[l, 2] = with_mask and bool(((lab == l) & (mask != 0)).any())      # hit = bit 0
+        assert np.array_equal(rec.host((n_labels + 1, 4)), want)
+        assert want[7, 1] == T - 1 == want[7, 0] and want[4, 1] == -1 and (with_mask or not want[:, 2].any())
 
 
-def test_label_extent_wrapper_equals_the_host_functions(nd):
+def test_label_filter_wrapper_equals_the_host_functions(nd):
     import torch
     from tobac_flow_amd.analysis import find_object_lengths, mask_labels
     rng = np.random.default_rng(21)
     for shape in ((1, 9, 11), (5, 6, 7)):
         lab = ndi.label(rng.random(shape) < 0.4)[0].astype(np.int32)
         msk = rng.random(shape) < 0.1
-        lengths, hit = nd.label_extent(torch.from_numpy(lab).cuda(), torch.from_numpy(msk).cuda())
-        assert np.array_equal(lengths, find_object_lengths(lab)) and np.array_equal(hit, mask_labels(lab, msk))
-        lengths, hit = nd.label_extent(torch.from_numpy(lab).cuda())
-        assert np.array_equal(lengths, find_object_lengths(lab)) and not hit.any()
+        lengths, hits, _ = nd.label_filter(torch.from_numpy(lab).cuda(), [torch.from_numpy(msk).cuda()])
+        assert np.array_equal(lengths, find_object_lengths(lab)) and np.array_equal(hits[:, 0], mask_labels(lab, msk))
+        lengths, hits, _ = nd.label_filter(torch.from_numpy(lab).cuda())
+        assert np.array_equal(lengths, find_object_lengths(lab)) and hits.shape == (lab.max(), 0)
 
 
 # ----------------------------------------------------------------------------- tf_correlate1d_sym

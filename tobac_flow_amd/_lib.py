@@ -188,7 +188,6 @@ _PROTOS = {
     "tf_correlate1d_sym": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _c.c_int, _P, _P]),
     "tf_grey_morph": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P]),
     "tf_linearise": (_c.c_int, [_P, _c.c_int64, _c.c_double, _c.c_double, _P, _P]),
-    "tf_label_extent": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _P, _P, _P]),
     "tf_label_filter": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.POINTER(LabelCriterion), _c.c_int, _P, _P]),
     "tf_apply_lut": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int, _P, _P]),
     "tf_apply_lut_keep_nonpositive": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int, _P, _P]),

@@ -2,7 +2,6 @@
 //   tf_binary_morph   ndi.binary_erosion / binary_dilation with a 3x3x3 structuring element, `iterations`
 //                     and `border_value` (detection.py:80-93, 105-119, 509, 551-553, 571-573, 608-616)
 //   tf_linearise      utils/normalisation_utils.py:36-56 linearise_field
-//   tf_label_extent   analysis.py:15-35 find_object_lengths + :38-63 mask_labels (per-label t-extent / hit flag)
 //   tf_apply_lut      utils/label_utils.py:265-309 remap_labels' final gather
 // All are one-pass HBM-bound stencils / reductions on uint8 / int32 volumes.
 #include "tf_common.h"
@@ -241,38 +240,6 @@ extern "C" int tf_linearise(const float *field, int64_t n, double lower, double 
     else
         hipLaunchKernelGGL(k_linearise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, field, n,
                            (float)lower, (float)(upper - lower), flip, out);
-    TF_CHECK_LAUNCH();
-    return TF_OK;
-}
-
-// per-label first / last time step and "overlaps the mask" flag: tmin/tmax int32[n_labels + 1], hit u8[n_labels + 1]
-__global__ void __launch_bounds__(256)
-k_label_extent(const int32_t *__restrict__ labels, const uint8_t *__restrict__ mask, int64_t plane, int n_labels,
-               int *__restrict__ tmin, int *__restrict__ tmax, uint8_t *__restrict__ hit)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int t = blockIdx.y;
-    if (i >= plane) return;
-    const int64_t p = (int64_t)t * plane + i;
-    const int32_t l = labels[p];
-    if (l <= 0 || l > n_labels) return;
-    if (tmin[l] > t) atomicMin(&tmin[l], t);
-    if (tmax[l] < t) atomicMax(&tmax[l], t);
-    if (mask && mask[p] && !hit[l]) hit[l] = 1;
-}
-
-extern "C" int tf_label_extent(const int32_t *labels, const uint8_t *mask, int64_t T, int64_t H, int64_t W, int n_labels,
-                               int *tmin, int *tmax, uint8_t *hit, void *stream)
-{
-    TF_REQUIRE(labels && tmin && tmax && hit && n_labels >= 0, "tf_label_extent: bad arguments");
-    TF_REQUIRE(T > 0 && T < 65536 && H > 0 && W > 0, "tf_label_extent: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    TF_CHECK_HIP(hipMemsetAsync(tmin, 0x7f, (size_t)(n_labels + 1) * sizeof(int), s));
-    TF_CHECK_HIP(hipMemsetAsync(tmax, 0xff, (size_t)(n_labels + 1) * sizeof(int), s));       // -1
-    TF_CHECK_HIP(hipMemsetAsync(hit, 0, (size_t)(n_labels + 1), s));
-    const int64_t plane = H * W;
-    hipLaunchKernelGGL(k_label_extent, dim3((unsigned)((plane + 255) / 256), (unsigned)T), dim3(256), 0, s,
-                       labels, mask, plane, n_labels, tmin, tmax, hit);
     TF_CHECK_LAUNCH();
     return TF_OK;
 }

@@ -14,7 +14,7 @@ from functools import partial
 import numpy as np
 from scipy import ndimage as ndi, stats
 
-from tobac_flow_amd import _lib
+from tobac_flow_amd import _lib, ndimage_dev as nd
 from tobac_flow_amd.analysis import (filter_labels_by_length, filter_labels_by_length_and_multimask_legacy,
                                      filter_labels_by_mask, find_object_lengths, mask_labels)
 from tobac_flow_amd.convolve import tag_func
@@ -154,10 +154,17 @@ def filtered_tdiff(flow, raw_diff):
     return flow.convolve(raw_diff, structure=_time_struct(), func=_nanmean0)
 
 
+def _filter_labels_dev(labels, criteria, long_enough):
+    """(filtered labels, lengths, hits): one read of the labels (ndimage_dev.label_filter: extent along t, 0 for an id that
+    does not occur, and whether each criterion is met), then the ids that are `long_enough(lengths)` and meet every
+    criterion are kept and renumbered densely -- the filter every recipe ends in"""
+    lengths, hits, _ = nd.label_filter(labels, criteria)
+    return nd.remap_labels(labels, np.logical_and(long_enough(lengths), hits.all(axis=1))), lengths, hits
+
+
 def _get_curvature_filter_dev(field, sigma, threshold, direction):
     """get_curvature_filter on a device tensor: same operations, same dtypes (second differences in the field's
     dtype, comparison in float64 against the zero-initialised float64 arrays the reference assigns into)."""
-    from tobac_flow_amd import ndimage_dev as nd
     t = _lib.torch()
     if direction not in ("negative", "positive"):
         raise ValueError("Direction must be either positive or negative")
@@ -203,7 +210,6 @@ def detect_growth_markers(flow, wvd):
     reference; in between the field is uploaded once and every step (semi-Lagrangian derivative, moving average, grey
     opening, curvature filter, opening, flow labelling, label filters) stays in HBM.  The SciPy-glue variant
     _detect_growth_markers_host gives identical results (tests/test_gpu_detection.py)."""
-    from tobac_flow_amd import ndimage_dev as nd
     t = _lib.torch()
     wvd_d = _to_device(wvd)
     dt = t.from_numpy(np.asarray(get_time_diff_from_coord(wvd.t))).to(wvd_d.device)[:, None, None]
@@ -213,16 +219,7 @@ def detect_growth_markers(flow, wvd):
     s2_3d = _plane_struct()
     filtered = nd.grey_opening(wvd_diff_smoothed, s2) * get_curvature_filter(wvd_d)
     marker_labels = flow.label(nd.binary_opening(filtered >= 0.25, s2_3d))
-    lengths, _ = nd.label_extent(marker_labels)
-    marker_labels = nd.remap_labels(marker_labels, lengths >= 3)
-    for mask in (filtered >= 0.5, wvd_d >= -5):
-        if int(marker_labels.max().item()) == 0:
-            # nothing survived: the reference hands SciPy an empty label range here (analysis.py:78-86), which this
-            # SciPy rejects with a ValueError.  Run that very call so that the behaviour is the reference's, whatever it is
-            marker_labels = _lib.to_dev(filter_labels_by_mask(marker_labels.cpu().numpy(), mask.cpu().numpy()))
-            continue
-        _, hit = nd.label_extent(marker_labels, mask)
-        marker_labels = nd.remap_labels(marker_labels, hit)
+    marker_labels = _growth_marker_filter_dev(marker_labels, filtered, wvd_d)
     if _is_device(wvd):                                                # device-resident pipeline: nothing visits the host
         return wvd_diff_smoothed, marker_labels
     wvd_diff_smoothed, marker_labels = _lib.to_host(wvd_diff_smoothed), _lib.to_host(marker_labels, remember=True)
@@ -230,6 +227,23 @@ def detect_growth_markers(flow, wvd):
         import xarray as xr
         marker_labels = xr.DataArray(marker_labels, wvd.coords, wvd.dims)
     return wvd_diff_smoothed, marker_labels
+
+
+def _growth_marker_filter_dev(marker_labels, filtered, wvd_d):
+    """detect_growth_markers' three filters (length >= 3, touches filtered >= 0.5, touches wvd >= -5; detection.py:119-123) in
+    one pass: a dense renumbering after each stage equals one renumbering of the labels that pass all three"""
+    t = _lib.torch()
+    criteria = [(filtered, ">=", 0.5), (wvd_d, ">=", -5)]
+    marker_labels, lengths, hits = _filter_labels_dev(marker_labels, criteria, lambda n: n >= 3)
+    alive = lengths >= 3
+    for k, (field, op, threshold) in enumerate(criteria):
+        if not alive.any():
+            # nothing reaches this stage, marker_labels is all zero: the reference hands SciPy an empty label range here
+            # (analysis.py:78-86), a ValueError with this SciPy.  Run that very call: the reference's behaviour, whatever it is
+            mask = {">=": t.ge, ">": t.gt, "<=": t.le, "<": t.lt}[op](field, threshold)
+            marker_labels = _lib.to_dev(filter_labels_by_mask(marker_labels.cpu().numpy(), mask.cpu().numpy()))
+        alive = alive & hits[:, k]
+    return marker_labels
 
 
 def _detect_growth_markers_host(flow, wvd):
@@ -252,7 +266,6 @@ def nan_gaussian_filter(a, *args, propagate_nan=True, **kwargs):
     """Gaussian filter that ignores NaNs (normalised convolution) (reference: detection.py:128-146).
     A GPU tensor runs on the device: nan_gaussian_filter(tensor, sigma[, truncate=...])."""
     if isinstance(a, _lib.torch().Tensor):
-        from tobac_flow_amd import ndimage_dev as nd
         t = _lib.torch()
         nan = t.isnan(a)
         filled = t.where(nan, t.zeros_like(a), a)
@@ -283,7 +296,6 @@ def get_peak_filter(field, sigma=2, min_distance=10, direction="negative"):
         raise ValueError("Direction must be either positive or negative")
     sign = 1 if direction == "negative" else -1
     if isinstance(field, _lib.torch().Tensor):       # device-resident: only the candidate peaks visit the host
-        from tobac_flow_amd import ndimage_dev as nd
         t = _lib.torch()
         smooth = nd.gaussian_filter(field, (0, sigma, sigma))
         out = t.zeros(field.shape, dtype=t.int32, device=field.device)
@@ -317,7 +329,6 @@ def detect_growth_markers_multichannel(flow, wvd, bt, t_sigma=1, overlap=0.5, su
     length / multi-mask label filter) stays in HBM.  The filter reads its three criteria -- wvd_s >= upper, bt_s <= -upper,
     wvd > -5 -- from the fields themselves in one pass over the labels (ndimage_dev.label_filter), so no boolean volume
     is made for it.  _detect_growth_markers_multichannel_host gives identical results (tests/test_gpu_label_filter.py)."""
-    from tobac_flow_amd import ndimage_dev as nd
     from tobac_flow_amd.analysis import _dev_lengths
     t = _lib.torch()
     wvd_d, bt_d = _to_device(wvd), _to_device(bt)
@@ -376,7 +387,6 @@ def get_combined_filters(flow, bt, wvd, swd, use_wvd=True):
     t_struct[:, 1, 1] = True
     s = _plane_struct()
     if isinstance(bt, _lib.torch().Tensor):          # device-resident recipe (same operators, same dtypes)
-        from tobac_flow_amd import ndimage_dev as nd
         t = _lib.torch()
 
         def channel_dev(field, direction):
@@ -412,7 +422,6 @@ def detect_cores(flow, bt, wvd, swd, wvd_threshold=0.25, bt_threshold=0.5, overl
     reference.  The three fields are uploaded once; filters, growth rates, markers, flow labelling and the length / WVD
     label filters stay in HBM; the labels come back once for the per-core cooling-rate statistics, which are host numpy
     exactly as in the reference (their float32 means feed a threshold).  Same result as _detect_cores_host."""
-    from tobac_flow_amd import ndimage_dev as nd
     t = _lib.torch()
     # BT first (usually in HBM already: create_flow has just been handed the same array); WVD and SWD cross PCIe on a copy
     # stream while the kernels that need BT alone -- its growth rate, its curvature and peak filters -- are enqueued and run
@@ -442,10 +451,9 @@ def detect_cores(flow, bt, wvd, swd, wvd_threshold=0.25, bt_threshold=0.5, overl
     core_labels = flow.label(combined_markers, overlap=overlap, absolute_overlap=absolute_overlap,
                              subsegment_shrink=subsegment_shrink)
     print("Initial core count:", int(core_labels.max().item()))
-    lengths, wvd_ok = nd.label_extent(core_labels, wvd_d > -5)
+    core_labels, lengths, hits = _filter_labels_dev(core_labels, [(wvd_d, ">", -5)], lambda n: n > min_length)
     print("Core labels meeting length threshold:", np.sum(lengths > min_length))
-    print("Core labels meeting WVD threshold:", np.sum(wvd_ok))
-    core_labels = nd.remap_labels(core_labels, np.logical_and(lengths > min_length, wvd_ok))
+    print("Core labels meeting WVD threshold:", np.sum(hits[:, 0]))
     if bt_d.dtype != t.float32:
         # (a float64 BT: the reference's per-step means are float64 then, tf_label_stats reads float32 -- the host form keeps them)
         class _HostBT(np.ndarray):
@@ -469,7 +477,7 @@ def _core_cooling_filter_dev(core_d, bt_d, times, min_length):
     once -- the correctly rounded mean, within the spread of the reference's possible orders (a few float32 ulps).  It
     feeds `cooling >= 0.5`: cores whose cooling rate lies within 1e-4 K / min of the threshold are reported by a
     RuntimeWarning (none in any test scene)."""
-    from tobac_flow_amd import label as _label, ndimage_dev as nd
+    from tobac_flow_amd import label as _label
     from tobac_flow_amd.analysis import _label_stats
     t = _lib.torch()
     T = core_d.shape[0]
@@ -564,7 +572,6 @@ def _detect_cores_host(flow, bt, wvd, swd, wvd_threshold=0.25, bt_threshold=0.5,
                      cell_measures="area: area")
 def get_anvil_markers(flow, field, threshold=-5, overlap=0.5, absolute_overlap=5, subsegment_shrink=0, min_length=3):
     """Flow-linked labels of the regions above `threshold` (reference: detection.py:500-520)."""
-    from tobac_flow_amd import ndimage_dev as nd
     s = ndi.generate_binary_structure(3, 1) * np.array([0, 1, 0])[:, np.newaxis, np.newaxis].astype(bool)
     # one recipe, in HBM: host input is uploaded once and the labels come back once (every operator is SciPy's bit for bit,
     # tests/test_gpu_detection.py; _get_anvil_markers_host is the same recipe with the reference's own SciPy glue)
@@ -572,8 +579,7 @@ def get_anvil_markers(flow, field, threshold=-5, overlap=0.5, absolute_overlap=5
     mask = nd.binary_opening(field_d >= threshold, s)
     marker_labels = flow.label(mask, overlap=overlap, absolute_overlap=absolute_overlap,
                                subsegment_shrink=subsegment_shrink)
-    lengths, _ = nd.label_extent(marker_labels)
-    return _deliver(nd.remap_labels(marker_labels, lengths > min_length), field)
+    return _deliver(_filter_labels_dev(marker_labels, [], lambda n: n > min_length)[0], field)
 
 
 def _get_anvil_markers_host(flow, field, threshold=-5, overlap=0.5, absolute_overlap=5, subsegment_shrink=0, min_length=3):
@@ -627,7 +633,6 @@ def _detect_anvils_host(flow, field, markers=None, upper_threshold=-5, lower_thr
 
 def _detect_anvils_dev(flow, field, markers, upper_threshold, lower_threshold, erode_distance, min_length):
     """detect_anvils with every step on the GPU; same operations in the same order as the numpy path"""
-    from tobac_flow_amd import ndimage_dev as nd
     from tobac_flow_amd.watershed import neighbour_offsets, watershed_dev
     t = _lib.torch()
     field = nd.linearise_field(field, lower_threshold, upper_threshold)
@@ -648,8 +653,7 @@ def _detect_anvils_dev(flow, field, markers, upper_threshold, lower_threshold, e
     labels = labels * nd.binary_opening(labels != 0, s).to(t.int32)
     inside = markers_i > 0
     labels = t.where(inside, markers_i, labels)
-    lengths, touches = nd.label_extent(labels, markers_i != 0)
-    return nd.remap_labels(labels, np.logical_and(lengths > min_length, touches))
+    return _filter_labels_dev(labels, [markers_i != 0], lambda n: n > min_length)[0]
 
 
 def get_watershed_mask(field, erode_distance: int = 1):
@@ -657,7 +661,6 @@ def get_watershed_mask(field, erode_distance: int = 1):
     (reference: detection.py:590-617)."""
     t = _lib.torch()
     if isinstance(field, t.Tensor):
-        from tobac_flow_amd import ndimage_dev as nd
         nan = t.isnan(field)
         mask = nd.binary_erosion((field <= 0) | nan, np.ones([3, 3, 3]), iterations=erode_distance, border_value=1)
         return mask | nan
@@ -700,7 +703,7 @@ def relabel_anvils(flow, anvil_labels, markers=None, overlap: float = 0.5, absol
                    min_length: int = 3):
     """Split anvils per time step and re-link them by flow overlap (reference: detection.py:660-687).  One recipe, in
     HBM: host input is uploaded once, the labels come back once (_relabel_anvils_host: the reference's own glue)."""
-    from tobac_flow_amd import label as _label, ndimage_dev as nd
+    from tobac_flow_amd import label as _label
     like = anvil_labels
     if hasattr(anvil_labels, "values") and not _is_device(anvil_labels):
         anvil_labels = anvil_labels.values
@@ -709,12 +712,8 @@ def relabel_anvils(flow, anvil_labels, markers=None, overlap: float = 0.5, absol
         markers = markers.values
     markers_get = None if markers is None else _to_device_later(markers)[0]      # (recognised / uploaded beside the linking)
     linked = flow.link_overlap(_label.make_step_labels_dev(labels_d), overlap=overlap, absolute_overlap=absolute_overlap)
-    if markers is not None:
-        lengths, touches = nd.label_extent(linked, markers_get() != 0)
-        keep = np.logical_and(lengths > min_length, touches)
-    else:
-        keep = nd.label_extent(linked)[0] > min_length
-    return _deliver(nd.remap_labels(linked, keep), like)
+    criteria = [] if markers is None else [markers_get() != 0]
+    return _deliver(_filter_labels_dev(linked, criteria, lambda n: n > min_length)[0], like)
 
 
 def _relabel_anvils_host(flow, anvil_labels, markers=None, overlap: float = 0.5, absolute_overlap: int = 5, min_length: int = 3):

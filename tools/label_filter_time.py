@@ -1,14 +1,16 @@
 """Time the label filter of the multichannel growth recipe on one GPU.
 
 (a) tf_label_filter with the recipe's three criteria (w_s >= upper, b_s <= -upper, wvd > -5, three float32 fields) on a
-    synthetic T x N^2 label volume (flat labels of the cold blobs below 262 K), against what it replaces, built from the
-    kernels the tree already has: three threshold passes that materialise masks and three tf_label_extent calls.  Raw entry
-    points with the largest label known (no Python glue), and the two Python forms end to end.
+    synthetic T x N^2 label volume (flat labels of the cold blobs below 262 K).  The raw entry point with the largest label
+    known (no Python glue), and the Python form end to end.  (profiles/label_filter.txt also has the threshold passes and the
+    one-mask-per-call entry point this kernel retired.)
 (b) detect_growth_markers_multichannel device-resident (DeviceField in, tensors out) and on host arrays, against
     _detect_growth_markers_multichannel_host, on a T x H x W scene with a Farneback flow; then the device form stage by stage.
+(c) the recipes that end in a label filter -- get_anvil_markers, detect_anvils, relabel_anvils, detect_growth_markers,
+    detect_cores -- device-resident on the same T x H x W scene (profiles/label_extent_retired.txt).
 
 Wall time around each call with a device synchronise; median of RUNS after WARM warm-ups.
-Usage: python tools/label_filter_time.py [N] [T] [H] [W] [a|b|ab] (development aid; the figures are kept in profiles/label_filter.txt)"""
+Usage: python tools/label_filter_time.py [N] [T] [H] [W] [a|b|c|abc] (development aid; the figures are kept in profiles/label_filter.txt, those of part c in profiles/label_extent_retired.txt)"""
 import statistics
 import sys
 import time
@@ -72,37 +74,14 @@ def part_a():
     report("  tf_label_filter, no criterion (lengths only)", lambda: _lib.check(L.tf_label_filter(
         _lib.ptr(labels), T, N, N, n, none, 0, _lib.ptr(rec), _lib.stream_ptr()), "tf_label_filter"))
 
-    masks = {}
-
-    def thresholds():
-        masks["m"] = [(w_s >= UPPER).view(torch.uint8), (b_s <= -UPPER).view(torch.uint8), (wvd > -5).view(torch.uint8)]
-    t_thr = report("  three threshold passes (torch, bool volumes written)", thresholds)
-    tmin = torch.empty(n + 1, dtype=torch.int32, device="cuda")
-    tmax = torch.empty(n + 1, dtype=torch.int32, device="cuda")
-    hit = torch.empty(n + 1, dtype=torch.uint8, device="cuda")
-
-    def extents():
-        for m in masks["m"]:
-            _lib.check(L.tf_label_extent(_lib.ptr(labels), _lib.ptr(m), T, N, N, n, _lib.ptr(tmin), _lib.ptr(tmax), _lib.ptr(hit),
-                                         _lib.stream_ptr()), "tf_label_extent")
-    t_ext = report("  three tf_label_extent calls on those masks", extents)
-    print(f"  fused {fused:.2f} ms against {t_thr + t_ext:.2f} ms for the passes it replaces: x{(t_thr + t_ext) / fused:.1f}", flush=True)
     voxels = T * N * N
-    print(f"  bytes per voxel, algorithmic: fused 4 (labels) + 12 under the {set_share * 100:.1f} % labelled voxels at most = "
-          f"{4 + 12 * set_share:.2f}; replaced 3 x (4 read + 1 written) + 3 x (4 labels + 1 mask) = 30.  "
-          f"Fused: {voxels * (4 + 12 * set_share) / fused / 1e6:.0f} GB/s of that; replaced: {voxels * 30 / (t_thr + t_ext) / 1e6:.0f} GB/s", flush=True)
+    print(f"  bytes per voxel, algorithmic: 4 (labels) + 12 under the {set_share * 100:.1f} % labelled voxels at most = "
+          f"{4 + 12 * set_share:.2f}: {voxels * (4 + 12 * set_share) / fused / 1e6:.0f} GB/s of that", flush=True)
 
-    # the two Python forms end to end (both find the largest label on the device first and download the small result)
-    lengths, hits, _ = nd.label_filter(labels, criteria)
+    # the Python form end to end (finds the largest label on the device first and downloads the small result)
+    _, hits, _ = nd.label_filter(labels, criteria)
     report("  ndimage_dev.label_filter(labels, three criteria)", lambda: nd.label_filter(labels, criteria))
-
-    def old_form():
-        out = [nd.label_extent(labels, m) for m in (w_s >= UPPER, b_s <= -UPPER, wvd > -5)]
-        return out[0][0], np.stack([o[1] for o in out], 1)
-    report("  three ndimage_dev.label_extent(labels, field op threshold)", old_form)
-    old_lengths, old_hits = old_form()
-    assert np.array_equal(lengths, old_lengths) and np.array_equal(hits, old_hits)
-    print(f"  the two forms agree on all {n} labels; {int(hits.all(1).sum())} labels satisfy all three criteria", flush=True)
+    print(f"  {int(hits.all(1).sum())} of {n} labels satisfy all three criteria", flush=True)
 
 
 def part_b():
@@ -157,10 +136,48 @@ def part_b():
            lambda: ndi.binary_opening(s["m"].cpu().numpy() != 0, structure=ndi.generate_binary_structure(2, 1)[np.newaxis, ...]), runs=1, warm=0)
 
 
+def part_c():
+    import contextlib
+    import io
+    import tobac_flow_amd.flow as tf
+    from synth import blob_stack, field_with_time
+    from tobac_flow_amd import detection as det
+    bt_d = torch.nan_to_num(blob_stack(T, H, W), nan=290.0)
+    grow = torch.linspace(0.6, 1.4, T, device="cuda")[:, None, None]          # deepening cold tops, so that growth is detected
+    cold = ((290.0 - bt_d) * grow).contiguous()
+    bt_d = 290.0 - cold
+    flow = tf.create_flow(field_with_time(bt_d.cpu().numpy(), 2), vr_steps=1, smoothing_passes=1, interp_method="cubic")
+    bt_f, wvd_f = field_with_time(bt_d, 2), field_with_time((cold / 2.0 - 30.0).contiguous(), 2)
+    swd_f = field_with_time((8 - (cold - 40.0).clamp(min=0) / 8).clamp(min=0).contiguous(), 2)     # small inside the cold tops
+    print(f"(c) recipes, device-resident (DeviceField in, tensor out), on {T} x {H} x {W}", flush=True)
+    out = {}
+
+    def timed(name, fn, *args):
+        def run():
+            with warnings.catch_warnings(), contextlib.redirect_stdout(io.StringIO()):
+                warnings.simplefilter("ignore")
+                try:
+                    out[name] = fn(flow, *args)
+                except ValueError as e:                               # (a filter stage that leaves nothing: the reference's error)
+                    out[name] = e
+        report(f"  {name}", run, runs=3)
+        r = out[name][1] if isinstance(out[name], tuple) else out[name]
+        print(f"    -> {type(r).__name__ if isinstance(r, Exception) else int(r.max())} labels", flush=True)
+
+    timed("get_anvil_markers", det.get_anvil_markers, wvd_f)
+    timed("detect_anvils", lambda f, x: det.detect_anvils(f, x, markers=out["get_anvil_markers"]), wvd_f)
+    timed("relabel_anvils", lambda f: det.relabel_anvils(f, out["detect_anvils"], markers=out["get_anvil_markers"]))
+    timed("detect_growth_markers", det.detect_growth_markers, wvd_f)
+    timed("detect_cores", det.detect_cores, bt_f, wvd_f, swd_f)
+
+
 if __name__ == "__main__":
-    which = sys.argv[5] if len(sys.argv) > 5 else "ab"
+    which = sys.argv[5] if len(sys.argv) > 5 else "abc"
     if "a" in which:
         part_a()
         torch.cuda.empty_cache()
     if "b" in which:
         part_b()
+        torch.cuda.empty_cache()
+    if "c" in which:
+        part_c()
