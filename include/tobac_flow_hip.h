@@ -908,6 +908,50 @@ size_t tf_label_nanmin_workspace_bytes(int64_t n_labels);
 int tf_label_nanmin(const int32_t *labels, const void *field, int dtype, int64_t n, int64_t n_labels, const int64_t *ids,
                     int64_t n_ids, double *out_min, int64_t *out_count, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- the validation stage at the flashes only (version 118): validation.py:107-219, scripts/dcc_validation.py:145-250 ----
+ * tf_flash_count / tf_flash_list: np.repeat(np.arange(n), grid.astype(int).ravel()) -- the raveled voxel of every flash, in
+ *   order -- for a flash-count grid of n voxels, dtype TF_F32, TF_F64 or TF_I32.  A count is truncated toward zero (2.9 -> 2).
+ *   tf_flash_count sums the counts per tile of tf_flash_tile() voxels, scans the tile sums into 64-bit offsets (left in the
+ *   workspace) and hands two words to the host, synchronising the stream once: *total_host = the number of flashes,
+ *   *bad_host = 0, or bit 0 set where some count is < 0 or NaN (tested before truncation, as np.repeat refuses it) and bit 1
+ *   where some count is >= 2^31 (the list is then not defined and tf_flash_list must not be called).  tf_flash_list, with the same grid and workspace,
+ *   writes voxel[n_flashes] (int64), n_flashes = that total: only tiles that hold a flash are read again, and the flashes of
+ *   a tile are written by all lanes of its workgroup, each searching the tile's prefix sums for its voxel, however many
+ *   flashes one voxel holds.  Integer sums throughout: the list is the same in every run.
+ * tf_edt_cylinder_at: tf_edt_cylinder at the n voxels of a list instead of everywhere.  d2 / nearest: tf_edt2d_frames' of the
+ *   TF_I32 volume `markers` (T, hw).  For flash i at voxel[i] = t * hw + p: dist[i] (double) = the correctly rounded sqrt of the
+ *   smallest d2[k][p] over k = max(t - time_margin, 0) .. min(t + time_margin, T - 1), +inf where every one is INT32_MAX;
+ *   closest[i] (int64, may be NULL; needs nearest and markers) = markers[k * hw + nearest[k][p]] for the EARLIEST k that holds
+ *   the minimum, 0 where there is none: tf_edt_cylinder's dist gathered at voxel, and markers gathered at its src.
+ *   *n_within (int64, on the device) = the number of i with dist[i] <= margin, compared in double, accumulated in integers.
+ *   A voxel outside [0, T * hw) gets +inf and 0.  No workspace and no volume-sized output.
+ * tf_grid_has_missing: *flag (int32, on the device) = 1 where some voxel of the grid (TF_F32, TF_F64, TF_I32) equals -1, else
+ *   0; NaN is not -1.  One read of the grid.
+ * tf_edge_filter: validation.py:173-219 get_edge_filter as a (T, H, W) byte mask.  0 within time_margin frames of either end
+ *   and within margin pixels of the four borders (as NumPy's a[:k] = a[-k:] = False: everything for k == 0), in the frames
+ *   where frame_off[t] != 0 (T bytes on the device, may be NULL: the frames around a time gap, computed by the host as
+ *   validation.py:185-193 does), and, with has_missing != 0, where scipy.ndimage.binary_dilation of grid == -1 with the
+ *   reference's structure reaches: output (t, y, x) is cleared exactly when some voxel (k, y - dy, x - dx) equals -1 with
+ *   |k - t| <= time_margin, |dy|, |dx| <= margin and (dx + margin - 10)^2 + (dy + margin - 10)^2 < margin^2 (a disc around the
+ *   reference's hard-coded index 10 in a box whose origin is margin; margin 3 gives an empty structure, margin 10 the centred
+ *   open disc).  Per chunk of frames: the OR over the time window and its prefix count along every row go to the workspace
+ *   (4 B per voxel of the chunk, <= 1 GiB unless one frame needs more), then every voxel still set looks up one span per
+ *   row of the footprint.  has_missing == 0 (what tf_grid_has_missing found): the grid is not read and no workspace is
+ *   needed.  margin <= 4000. */
+int tf_flash_tile(void);
+size_t tf_flash_workspace_bytes(int64_t n);
+int tf_flash_count(const void *grid, int dtype, int64_t n, void *ws, size_t ws_bytes, int64_t *total_host, int *bad_host,
+                   void *stream);
+int tf_flash_list(const void *grid, int dtype, int64_t n, void *ws, size_t ws_bytes, int64_t *voxel, int64_t n_flashes,
+                  void *stream);
+int tf_edt_cylinder_at(const int32_t *d2, const int32_t *nearest, const int32_t *markers, int64_t T, int64_t hw,
+                       int64_t time_margin, const int64_t *voxel, int64_t n, double margin, double *dist, int64_t *closest,
+                       int64_t *n_within, void *stream);
+int tf_grid_has_missing(const void *grid, int dtype, int64_t n, int32_t *flag, void *stream);
+size_t tf_edge_filter_workspace_bytes(int64_t T, int64_t H, int64_t W, int has_missing);
+int tf_edge_filter(const void *grid, int dtype, int64_t T, int64_t H, int64_t W, int64_t margin, int64_t time_margin,
+                   const uint8_t *frame_off, int has_missing, uint8_t *out, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- subsegment_labels: tobac_flow/label.py:13-80 (version 106) -----------------------------------------------------------
  * The per-voxel passes between tf_label / tf_edt2d_frames / tf_label_sizes and the per-frame tf_watershed of the recipe
  * (tobac_flow_amd/label.py subsegment_labels).

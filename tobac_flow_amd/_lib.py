@@ -226,6 +226,15 @@ _PROTOS = {
     "tf_edt_time_envelope": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P]),
     "tf_label_nanmin_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
     "tf_label_nanmin": (_c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _c.c_size_t, _P]),
+    "tf_flash_tile": (_c.c_int, []),
+    "tf_flash_workspace_bytes": (_c.c_size_t, [_c.c_int64]),
+    "tf_flash_count": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_size_t, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int), _P]),
+    "tf_flash_list": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_size_t, _P, _c.c_int64, _P]),
+    "tf_edt_cylinder_at": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int64, _c.c_double, _P, _P, _P, _P]),
+    "tf_grid_has_missing": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _P]),
+    "tf_edge_filter_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64, _c.c_int64, _c.c_int]),
+    "tf_edge_filter": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int, _P, _P,
+                                  _c.c_size_t, _P]),
     "tf_subseg_prepare": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_double, _P, _P, _P]),
     "tf_subseg_rank": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P]),
     "tf_bin_points": (_c.c_int, [_c.POINTER(BinPoints), _P]),

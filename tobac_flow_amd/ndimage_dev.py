@@ -385,6 +385,102 @@ def edt_cylinder(d2, nearest, time_margin):
     return dist, src
 
 
+def _count_grid(grid):
+    """a flash grid as the validation kernels take it: float32, float64 or int32 and contiguous (bool and the narrower
+    integers widen to int32, everything else to float64)"""
+    t = _lib.torch()
+    if grid.dtype in (t.bool, t.uint8, t.int8, t.int16):
+        grid = grid.to(t.int32)
+    elif grid.dtype not in (t.float32, t.float64, t.int32):
+        grid = grid.to(t.float64)
+    return grid.contiguous(), {t.float32: _lib.TF_F32, t.float64: _lib.TF_F64, t.int32: _lib.TF_I32}[grid.dtype]
+
+
+def flash_tile():
+    """the number of voxels one workgroup of tf_flash_count / tf_flash_list handles"""
+    return int(_lib.lib().tf_flash_tile())
+
+
+def flash_list(grid):
+    """tf_flash_count + tf_flash_list: the int64 device tensor np.repeat(np.arange(n), grid.astype(int).ravel()) -- the
+    raveled voxel of every flash of the flash-count device tensor `grid`, in order, a count truncated toward zero.
+    ValueError, in np.repeat's words, for a negative or NaN count (tested before truncation), and a ValueError of its own
+    for a count >= 2^31.  The total crosses to the host once, to size the list."""
+    import ctypes
+    t = _lib.torch()
+    L = _lib.lib()
+    g, dtype = _count_grid(grid)
+    n = g.numel()
+    if n == 0:
+        return t.zeros(0, dtype=t.int64, device=g.device)
+    ws = _lib.workspace(L.tf_flash_workspace_bytes(n), "flash_list")
+    total, bad = ctypes.c_int64(0), ctypes.c_int(0)
+    _lib.check(L.tf_flash_count(_lib.ptr(g), dtype, n, _lib.ptr(ws), ws.numel(), ctypes.byref(total), ctypes.byref(bad),
+                                _lib.stream_ptr()), "tf_flash_count")
+    if bad.value & 1:
+        raise ValueError("repeats may not contain negative values (glm_grid holds a negative or NaN flash count)")
+    if bad.value:
+        raise ValueError("glm_grid holds a flash count of 2^31 or more: the list of its flashes cannot be held")
+    voxel = t.empty(total.value, dtype=t.int64, device=g.device)
+    _lib.check(L.tf_flash_list(_lib.ptr(g), dtype, n, _lib.ptr(ws), ws.numel(), _lib.ptr(voxel), total.value,
+                               _lib.stream_ptr()), "tf_flash_list")
+    return voxel
+
+
+def edt_cylinder_at(d2, nearest, markers, time_margin, voxel, margin, get_closest=False):
+    """tf_edt_cylinder_at: (float64 distances, int64 closest markers or None, int64 device scalar) -- edt_cylinder's
+    distance gathered at the raveled voxels `voxel` (int64 device tensor), with get_closest the value of `markers` (the
+    int32 volume d2 and nearest were made from) at the nearest feature of the earliest frame that holds the minimum (0 where
+    there is none), and the number of entries whose distance is <= margin.  No volume is written."""
+    t = _lib.torch()
+    if d2.dim() != 3 or 0 in d2.shape or d2.dtype != t.int32:
+        raise ValueError("d2 must be a non-empty (T, H, W) int32 tensor")
+    if get_closest and (nearest is None or markers is None or markers.dtype != t.int32 or markers.shape != d2.shape or
+                        nearest.shape != d2.shape or nearest.dtype != t.int32):
+        raise ValueError("get_closest needs nearest and the int32 marker volume, both of d2's shape")
+    if voxel.dtype != t.int64 or voxel.dim() != 1:
+        raise ValueError("voxel must be a one-dimensional int64 tensor")
+    T, H, W = d2.shape
+    d2, voxel = d2.contiguous(), voxel.contiguous()
+    n = voxel.numel()
+    dist = t.empty(n, dtype=t.float64, device=d2.device)
+    closest = t.empty(n, dtype=t.int64, device=d2.device) if get_closest else None
+    within = t.empty((), dtype=t.int64, device=d2.device)
+    _lib.check(_lib.lib().tf_edt_cylinder_at(_lib.ptr(d2), _lib.ptr(nearest.contiguous()) if get_closest else None,
+                                             _lib.ptr(markers.contiguous()) if get_closest else None, T, H * W, int(time_margin),
+                                             _lib.ptr(voxel), n, float(margin), _lib.ptr(dist), _lib.ptr(closest),
+                                             _lib.ptr(within), _lib.stream_ptr()), "tf_edt_cylinder_at")
+    return dist, closest, within
+
+
+def edge_filter(grid, margin, time_margin, frame_off=None):
+    """tf_grid_has_missing + tf_edge_filter: the bool (T, H, W) device tensor of validation.get_edge_filter for the flash
+    grid `grid` (device tensor): False within time_margin frames of the ends and margin pixels of the borders, in the frames
+    `frame_off` marks (T booleans, host or device), and where binary_dilation of grid == -1 with the reference's structure
+    reaches.  Whether the grid holds a -1 crosses to the host once; without one the dilation is not run."""
+    t = _lib.torch()
+    L = _lib.lib()
+    if grid.dim() != 3 or 0 in grid.shape:
+        raise ValueError("a non-empty (T, H, W) grid is required")
+    g, dtype = _count_grid(grid)
+    T, H, W = g.shape
+    off = None
+    if frame_off is not None:
+        off = _lib.to_dev(np.ascontiguousarray(_lib.to_host(frame_off) if _lib.is_tensor(frame_off) else frame_off, np.uint8))
+        if off.numel() != T:
+            raise ValueError(f"frame_off must hold one entry per frame ({T}), got {off.numel()}")
+    flag = t.empty((), dtype=t.int32, device=g.device)
+    _lib.check(L.tf_grid_has_missing(_lib.ptr(g), dtype, g.numel(), _lib.ptr(flag), _lib.stream_ptr()), "tf_grid_has_missing")
+    missing = int(flag)
+    nbytes = L.tf_edge_filter_workspace_bytes(T, H, W, missing)
+    ws = _lib.workspace(nbytes, "edge_filter") if nbytes else None
+    out = t.empty((T, H, W), dtype=t.uint8, device=g.device)
+    _lib.check(L.tf_edge_filter(_lib.ptr(g), dtype, T, H, W, int(margin), int(time_margin), _lib.ptr(off), missing,
+                                _lib.ptr(out), _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream_ptr()),
+               "tf_edge_filter")
+    return out.view(t.bool)
+
+
 def distance_transform_edt_frames(x, return_distances=True, return_indices=False):
     """scipy.ndimage.distance_transform_edt(x[t], return_distances=..., return_indices=...) for every frame t of a
     (T, H, W) device tensor: the float64 distance of every voxel to the nearest voxel of its frame where x == 0, and the
