@@ -1126,7 +1126,9 @@ int tf_profile_collect(int64_t *calls, double *ms, double *bytes);
  *   threads (<= 16, TF_STAGING_THREADS) chunk by chunk (8 MiB, TF_STAGING_CHUNK_MB) into a ring of pinned slots, each chunk's
  *   DMA enqueued as soon as it is staged; returns when the SOURCE has been read completely (the caller may free or change it),
  *   the last DMAs and everything enqueued after the call stay asynchronous.  A source inside a pool block goes out as one DMA
- *   (the block must stay untouched until `stream` has passed it).  hash_out_host != NULL: the 128-bit content checksum of the
+ *   and the call waits for it on `stream`: the same contract -- on return the block has been read, the caller may change it
+ *   or give it back to the pool (which orders nothing by stream: a freed block may be handed out or unmapped at once), and
+ *   everything enqueued after the call stays asynchronous.  hash_out_host != NULL: the 128-bit content checksum of the
  *   source (two uint64), computed by the copying threads on the way.
  * tf_download(dst_host, src, bytes, stream): device -> host, complete on return (DMA at the link's rate into a pool block).
  * tf_hash_host / tf_hash_dev: the same 128-bit checksum of a host buffer (host threads) / of device memory (one kernel; the

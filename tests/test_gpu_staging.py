@@ -197,7 +197,8 @@ def test_the_script_sequence_gives_the_same_labels_whatever_the_container_and_th
     """The drop-in script's call sequence (scripts/dcc_detect_goes.py:164-303) on one scene, four ways: host containers with
     recognition by content switched off (every array uploaded), switched on (twice in a row: the second pass finds results of
     the first still remembered), and device-resident (tobac_flow_amd.to_device).  Every result equal, array for array --
-    in particular no recipe writes into a device twin that a later call is served."""
+    in particular no recipe writes into a device twin that a later call is served: the cached passes run with
+    TF_HOST_CACHE_VERIFY=1, which re-hashes every twin before it is served."""
     import warnings
     import torch
     import tobac_flow_amd
@@ -230,12 +231,14 @@ def test_the_script_sequence_gives_the_same_labels_whatever_the_container_and_th
     plain = sequence(*host_fields())
     assert int(plain[1].max()) >= 1 and int(plain[4].max()) >= 1, [int(p.max()) for p in plain]
     monkeypatch.delenv("TF_HOST_CACHE_GB")
+    monkeypatch.setenv("TF_HOST_CACHE_VERIFY", "1")                      # every twin served below is re-hashed first: a stale one raises
     before = dict(_staging.stats)
     first = sequence(*host_fields())
     hits_first = _staging.stats["hits"] - before["hits"]
     second = sequence(*host_fields())
     assert hits_first >= 6                                               # bt, wvd - swd, the markers twice, the two anvil volumes
     assert _staging.stats["hits"] - before["hits"] >= 2 * hits_first     # (the second pass finds at least as much)
+    assert _staging.stats["verified"] - before["verified"] == _staging.stats["hits"] - before["hits"]
     device = sequence(*tobac_flow_amd.to_device(*host_fields()))
     for name, a, b, c, d in zip(("core", "markers", "thick0", "thick", "thin"), plain, first, second, device):
         assert a.dtype == b.dtype == c.dtype == d.dtype and np.array_equal(a, b) and np.array_equal(a, c) and np.array_equal(a, d), name

@@ -380,7 +380,8 @@ def to_dev(x, dtype=None, share=False):
 def to_host(x, remember=False):
     """device tensor -> numpy array in a pooled pinned block (_staging.download: DMA at the link's rate, no second host
     copy).  remember=True -- for results handed back through the reference's interface: the device tensor stays cached as
-    the array's twin, so that the array coming back as an input (`markers=`) does not cross PCIe again."""
+    the array's twin, so that the array coming back as an input (`markers=`) does not cross PCIe again.  That asserts
+    OWNERSHIP: `x` must be a tensor this package made and nobody writes into afterwards (never a tensor the caller holds)."""
     from tobac_flow_amd import _staging
     return _staging.download(x, remember=remember)
 

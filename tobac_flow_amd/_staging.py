@@ -16,7 +16,9 @@ staging"; csrc/staging.hip):
 The cache holds device memory: at most TF_HOST_CACHE_GB (default 32; 0 switches recognition off), least recently used
 first out; `clear()` drops it.  Cached twins are shared, read-only by convention: the recipes never write into their inputs
 (the same convention device-resident callers rely on), and `upload(..., fresh=True)` gives a private tensor where one is
-going to be written."""
+going to be written.  Only tensors this package made are remembered: an upload's destination, and a result downloaded with
+remember=True (the caller gets the host array, never the tensor).  TF_HOST_CACHE_VERIFY=1 checks the convention: every hit
+re-hashes the twin on the device and raises if it no longer holds the content it is remembered by."""
 import ctypes
 import os
 import threading
@@ -32,12 +34,30 @@ _LOCK = threading.Lock()
 _CACHE = OrderedDict()                    # (nbytes, dtype str, shape, device, h0, h1) -> (device tensor, event behind its last write)
 _cache_bytes = 0
 _SIGS = {}                                # (nbytes, dtype str, shape, device) -> {sample signature: entries with it} (see _sample_sig)
-stats = {"uploads": 0, "upload_bytes": 0, "hits": 0, "hit_bytes": 0, "downloads": 0, "download_bytes": 0,
+stats = {"uploads": 0, "upload_bytes": 0, "hits": 0, "hit_bytes": 0, "downloads": 0, "download_bytes": 0, "verified": 0,
          "hash_s": 0.0, "upload_s": 0.0, "download_s": 0.0, "pinned_alloc_s": 0.0}      # (host seconds spent in each part)
 
 
 def _budget():
     return int(float(os.environ.get("TF_HOST_CACHE_GB", "32")) * 1e9)
+
+
+def _verify():
+    """TF_HOST_CACHE_VERIFY=1: every hit re-hashes the twin on the device before it is served (_lookup)"""
+    return os.environ.get("TF_HOST_CACHE_VERIFY", "0") not in ("", "0")
+
+
+def _forget(key):
+    """drop one entry and its share of _SIGS and _cache_bytes (called with _LOCK held)"""
+    global _cache_bytes
+    entry = _CACHE.pop(key, None)
+    if entry is None:
+        return
+    _cache_bytes -= key[0]
+    left = _SIGS.get(key[:4], {})
+    left[entry[2]] = left.get(entry[2], 1) - 1
+    if left.get(entry[2], 0) <= 0:
+        left.pop(entry[2], None)
 
 
 def clear(trim=True):
@@ -86,12 +106,7 @@ def _remember(key, tensor, sig):
         by_sig = _SIGS.setdefault(key[:4], {})
         by_sig[sig] = by_sig.get(sig, 0) + 1
         while _cache_bytes > budget and len(_CACHE) > 1:
-            old, (_, _, old_sig) = _CACHE.popitem(last=False)
-            _cache_bytes -= old[0]
-            left = _SIGS.get(old[:4], {})
-            left[old_sig] = left.get(old_sig, 1) - 1
-            if left.get(old_sig, 0) <= 0:
-                left.pop(old_sig, None)
+            _forget(next(iter(_CACHE)))
 
 
 def _lookup(key):
@@ -105,6 +120,20 @@ def _lookup(key):
     cur = _lib.torch().cuda.current_stream()
     cur.wait_event(ev)                    # (no-op on the stream that produced it; a flood thread's stream waits for the DMA)
     tensor.record_stream(cur)             # the caching allocator must not recycle the block under this stream's kernels
+    if _verify():
+        # the twin must still hold the bytes whose checksum is its key: somebody wrote into a shared tensor, or a remembered
+        # result was a view of scratch that has been overwritten since.  One pass over HBM and a stream synchronisation per hit
+        h = np.zeros(2, np.uint64)
+        with _lib.torch().cuda.device(tensor.device):
+            _lib.check(_lib.lib().tf_hash_dev(_lib.ptr(tensor), key[0], h.ctypes.data_as(_lib._P), _lib.stream_ptr()), "tf_hash_dev")
+        if (int(h[0]), int(h[1])) != key[4:6]:
+            with _LOCK:
+                if _CACHE.get(key) is entry:
+                    _forget(key)
+            raise RuntimeError("host cache: the device twin of a %s array of shape %s no longer holds the content it is "
+                               "remembered by (written into in place, or a view of reused scratch): entry dropped"
+                               % (np.dtype(key[1]).name, key[2]))
+        stats["verified"] += 1
     return tensor
 
 
@@ -204,7 +233,10 @@ def empty_pinned(shape, dtype):
 
 
 def download(tensor, remember=True):
-    """device tensor -> numpy array in a pinned block (module docstring); CPU tensors are converted in place"""
+    """device tensor -> numpy array in a pinned block (module docstring); CPU tensors are converted in place.
+    remember=True ASSERTS OWNERSHIP: the tensor itself (not a copy) stays in the cache as the array's twin and is served to
+    whoever presents the array's content again, so nobody may write into it afterwards.  That is true of a result this
+    package computed and hands out only as the host array (_deliver); it is not true of a tensor a caller holds (to_host)."""
     t = _lib.torch()
     if not isinstance(tensor, t.Tensor):
         return np.asarray(tensor)
@@ -297,8 +329,10 @@ def to_device(*fields):
 
 
 def to_host(x):
-    """device tensor / DeviceField -> numpy array (pinned block); anything else passes through np.asarray"""
+    """device tensor / DeviceField -> numpy array (pinned block); anything else passes through np.asarray.  The tensor is the
+    caller's, who may go on writing into it: it is NOT remembered as the array's twin (the array presented to an entry point
+    later is uploaded like any other)."""
     inner = getattr(x, "data", None)
     if isinstance(inner, _lib.torch().Tensor) and not isinstance(x, _lib.torch().Tensor):
         x = inner
-    return download(x)
+    return download(x, remember=False)

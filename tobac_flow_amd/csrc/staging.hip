@@ -212,6 +212,9 @@ void *pinned_new(size_t cap)
     g_how[(uintptr_t)p] = PinnedHow{nullptr, 0, false};
     return p;
 }
+// Unregisters and unmaps: no copy may be pending on the block.  That holds by construction, not by a wait here: every transfer
+// that touches a pool block (tf_upload from one, tf_download into one, the ring's slots) has been synchronised before the entry
+// point that enqueued it returned, and a block reaches this function only from `cached`, i.e. after its owner let go of it.
 void pinned_delete(void *p)
 {
     PinnedHow how{nullptr, 0, false};
@@ -439,10 +442,14 @@ extern "C" int tf_upload(void *dst_dev, const void *src_host, size_t bytes, uint
     hipStream_t s = (hipStream_t)stream;
     const unsigned char *src = (const unsigned char *)src_host;
     if (tf_host_is_pinned(src_host, bytes)) {
-        // a block of the pool: the DMA engine reads it where it lies
+        // a block of the pool: the DMA engine reads it where it lies -- and has read it when this call returns, as on the
+        // pageable paths below.  The pool orders nothing by stream or event: a block dropped right after this call goes back to
+        // `cached`, its next owner (host writes, a tf_download on another stream) or pinned_delete may touch it at once.  The
+        // checksum pass runs on the host threads while the copy is in flight; only then does this thread wait.
         TF_CHECK_HIP(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, s));
-        if (hash_out) return tf_hash_host(src_host, bytes, hash_out);
-        return TF_OK;
+        const int rc = hash_out ? tf_hash_host(src_host, bytes, hash_out) : TF_OK;
+        TF_CHECK_HIP(hipStreamSynchronize(s));
+        return rc;
     }
     if (bytes < (1u << 20)) {                                   // small: the runtime's own staging does as well
         TF_CHECK_HIP(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, s));
