@@ -823,6 +823,51 @@ size_t tf_label_proportions_workspace_bytes(int64_t n_labels, int n_flags);
 int tf_label_proportions(const int32_t *labels, const int32_t *flags, const float *weights, int64_t T, int64_t hw,
                          int weights_plane, int64_t n_labels, const int32_t *flag_values_host, int n_flags, double *out,
                          void *ws, size_t ws_bytes, void *stream);
+/* tf_flux_cre (version 119, as tf_quality_weights and tf_label_wstats_multi): tobac_flow/postprocess.py:29-99 (`get_cre`, `add_cre_to_dataset`) in one launch.  planes_host: 13 device
+ *   pointers in host memory -- toa_swdn, toa_swup, toa_swup_clr, toa_lwup, toa_lwup_clr, boa_swdn, boa_swup, boa_lwdn,
+ *   boa_lwup, boa_swdn_clr, boa_swup_clr, boa_lwdn_clr, boa_lwup_clr -- of n elements each, all TF_F32 or all TF_F64;
+ *   out_host: 10 device pointers, the reference's order of insertion -- toa_swup_cre, toa_lwup_cre, boa_swdn_cre,
+ *   boa_swup_cre, boa_lwdn_cre, boa_lwup_cre, toa_net, toa_net_cre, boa_net, boa_net_cre.  Evaluated in the reference's
+ *   tree, every operation rounded in the planes' type: cre = flux - clr; toa_net = swdn - (swup + lwup);
+ *   toa_net_cre = -(swup_cre + lwup_cre); boa_net = swdn + lwdn - (swup + lwup); boa_net_cre = swdn_cre + lwdn_cre -
+ *   (swup_cre + lwup_cre).  Additions, subtractions and a negation only: NumPy's values, NaN placement included.  No
+ *   output may overlap an input.  Each plane is read once and each result written once. */
+int tf_flux_cre(const void *const *planes_host, void *const *out_host, int dtype, int64_t n, void *stream);
+/* tf_quality_weights: scripts/postprocess_seviri_nat_dcc.py:181-186.  out[t][p] = weights * (qcflag == 0) * (cth < 30) *
+ *   isfinite(cot), the factors 0 or 1, multiplied in that order in the weights' type (weight_dtype TF_F32 / TF_F64, also
+ *   the type of out): a NaN or infinite weight times 0 is NaN, a NaN cth compares false.  weights: (T, hw), or with
+ *   weights_plane != 0 ONE (hw,) plane; qcflag: int32 (T, hw); cth, cot: (T, hw), both field_dtype TF_F32 / TF_F64. */
+int tf_quality_weights(const void *weights, int weight_dtype, int weights_plane, const int32_t *qcflag, const void *cth,
+                       const void *cot, int field_dtype, int64_t T, int64_t hw, void *out, void *stream);
+/* tf_label_wstats_multi: tf_label_wstats for a whole SET of fields over one int32 (T, hw) label volume: two passes over
+ *   the labels and one finish for all of them.  out[(f * n_labels + id - 1) * 10 + k], k = 0 .. 9 as tf_label_wstats
+ *   defines them, f the field's position in its set:
+ *     TF_FIELDS_PLAIN  n_planes = 1 .. 8 planes, the fields are the planes; errors_host: NULL, or n_planes pointers of which
+ *                      each may be NULL (k = 6 .. 9 NaN for that field)
+ *     TF_FIELDS_TOA    5 planes toa_swdn, toa_swup, toa_swup_clr, toa_lwup, toa_lwup_clr; 7 fields toa_swdn, toa_swup,
+ *                      toa_swup_cre, toa_lwup, toa_lwup_cre, toa_net, toa_net_cre
+ *     TF_FIELDS_BOA    8 planes boa_swdn, boa_swup, boa_lwdn, boa_lwup and their _clr planes in that order; 10 fields
+ *                      boa_swdn, boa_swdn_cre, boa_swup, boa_swup_cre, boa_lwdn, boa_lwdn_cre, boa_lwup, boa_lwup_cre,
+ *                      boa_net, boa_net_cre
+ *   (the field orders are those of scripts/postprocess_seviri_nat_dcc.py:274-291; errors_host must be NULL for TOA and BOA).
+ *   planes_host / errors_host: device pointers in host memory.  The derived fields are formed per voxel in registers by
+ *   tf_flux_cre's own expressions in the field type: the derived volumes never exist.  field_dtype (planes and errors)
+ *   and weight_dtype are TF_F32 or TF_F64 independently of each other; nothing is copied or cast, sums are accumulated in
+ *   double.  weights: (T, hw), or with weights_plane != 0 ONE (hw,) plane.
+ *   Every field has its OWN finite mask: a voxel counts for a field where THAT field's value is finite (a NaN in
+ *   toa_swup_clr leaves toa_swup untouched and drops the voxel from toa_swup_cre and toa_net_cre).  Everything else is
+ *   tf_label_wstats's rule field by field: min and max include weight-0 voxels, a NaN weight at a finite value makes the
+ *   field's label NaN, the smallest raveled index wins among tied extremes, -0.0 equals +0.0, ids outside [1, n_labels]
+ *   are background, 64-bit indexing.  Labels, weights and every input plane are read once per pass, the planes only in
+ *   steps that hold a labelled voxel; errors are read by element under labelled voxels.  n, min, max and the selected
+ *   errors are exact, the sums as tf_label_wstats's.  The workspace holds 128 B per field and label. */
+#define TF_FIELDS_PLAIN 0
+#define TF_FIELDS_TOA 1
+#define TF_FIELDS_BOA 2
+size_t tf_label_wstats_multi_workspace_bytes(int set, int n_planes, int64_t n_labels);
+int tf_label_wstats_multi(const int32_t *labels, int set, const void *const *planes_host, const void *const *errors_host,
+                          int n_planes, const void *weights, int field_dtype, int weight_dtype, int64_t T, int64_t hw,
+                          int weights_plane, int64_t n_labels, double *out, void *ws, size_t ws_bytes, void *stream);
 /* tf_label_reduce (version 110): what tobac_flow/utils/label_utils.py:8-55 (`labeled_comprehension`) and :58-140
  *   (`apply_func_to_labels`) need of a region when `func` is a plain NumPy reducer, for every label id of the span
  *   [id_lo, id_hi] in one read of the volume.  labels: int32 (T * hw,); ids outside the span are background, 0 and

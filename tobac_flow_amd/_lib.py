@@ -14,6 +14,7 @@ _SO = os.environ.get("TF_LIB_PATH") or os.path.join(_HERE, "csrc", "libtobac_flo
 
 INTERP = {"nearest": 0, "linear": 1, "cubic": 2, "lanczos": 3}
 TF_F32, TF_F64, TF_I32, TF_U8, TF_I16, TF_I8 = 0, 1, 2, 3, 4, 5
+TF_FIELDS_PLAIN, TF_FIELDS_TOA, TF_FIELDS_BOA = 0, 1, 2
 FUNC_STACK, FUNC_SOBEL, FUNC_SOBEL_UPHILL, FUNC_SOBEL_DOWNHILL, FUNC_NANMEAN, FUNC_DIFF, FUNC_ANY, FUNC_NANMAX = range(8)
 
 
@@ -214,6 +215,11 @@ _PROTOS = {
     "tf_label_wstats": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_proportions_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int]),
     "tf_label_proportions": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
+    "tf_flux_cre": (_c.c_int, [_P, _P, _c.c_int, _c.c_int64, _P]),
+    "tf_quality_weights": (_c.c_int, [_P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int64, _P, _P]),
+    "tf_label_wstats_multi_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int64]),
+    "tf_label_wstats_multi": (_c.c_int, [_P, _c.c_int, _P, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int,
+                                         _c.c_int64, _P, _P, _c.c_size_t, _P]),
     "tf_label_reduce_workspace_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int64]),
     "tf_label_reduce": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _P, _P,
                                    _c.c_size_t, _P]),

@@ -12,7 +12,7 @@ void tf_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-extern "C" int tf_version(void) { return 118; }   // 101: tf_warp_offsets, tf_gather_offsets, tf_convolve_step; 102: tf_label_wstats, tf_label_proportions; 103: tf_edt2d_frames, tf_edt_cylinder, tf_label_nanmin; 104: tf_norm8_pair; 105: tf_edt_time_envelope; 106: tf_subseg_prepare, tf_subseg_rank; 107: tf_label_filter; 108: tf_bin_points; 109: tf_stripe_deviation, tf_prepare_fields; 110: tf_label_reduce, tf_label_order; 111: tf_relabel_merge; 112: tf_field_stats; 113: tf_group_reduce; 114: tf_watershed* (t, y, x) forms refuse fwd / bwd not 8-byte and field / markers not 4-byte aligned (TF_EINVAL); 115: tf_geos_inverse*, tf_geos_forward, tf_geod_inverse, tf_grid_spacing, tf_view_angles; 116: tf_ecef, tf_geos_to_ecef, tf_glm_parallax; 117: tf_label_extent removed: tf_label_filter with zero or one TF_U8 criterion; 118: tf_flash_count, tf_flash_list, tf_edt_cylinder_at, tf_grid_has_missing, tf_edge_filter
+extern "C" int tf_version(void) { return 119; }   // 101: tf_warp_offsets, tf_gather_offsets, tf_convolve_step; 102: tf_label_wstats, tf_label_proportions; 103: tf_edt2d_frames, tf_edt_cylinder, tf_label_nanmin; 104: tf_norm8_pair; 105: tf_edt_time_envelope; 106: tf_subseg_prepare, tf_subseg_rank; 107: tf_label_filter; 108: tf_bin_points; 109: tf_stripe_deviation, tf_prepare_fields; 110: tf_label_reduce, tf_label_order; 111: tf_relabel_merge; 112: tf_field_stats; 113: tf_group_reduce; 114: tf_watershed* (t, y, x) forms refuse fwd / bwd not 8-byte and field / markers not 4-byte aligned (TF_EINVAL); 115: tf_geos_inverse*, tf_geos_forward, tf_geod_inverse, tf_grid_spacing, tf_view_angles; 116: tf_ecef, tf_geos_to_ecef, tf_glm_parallax; 117: tf_label_extent removed: tf_label_filter with zero or one TF_U8 criterion; 118: tf_flash_count, tf_flash_list, tf_edt_cylinder_at, tf_grid_has_missing, tf_edge_filter; 119: tf_flux_cre, tf_quality_weights, tf_label_wstats_multi
 extern "C" const char *tf_last_error(void) { return g_err; }
 extern "C" int tf_device_count(void) {
     int n = 0;

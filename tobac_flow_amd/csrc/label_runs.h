@@ -1,5 +1,5 @@
 // What the per-label reduction kernels share: the work layouts, the vector loads, and the two walkers that take a lane
-// through its voxels as runs of equal labels.  Users: wstats_kernels.h, edt_kernels.h (tf_label_nanmin), props.hip,
+// through its voxels as runs of equal labels.  Users: wstats_kernels.h, field_props_kernels.h, edt_kernels.h (tf_label_nanmin), props.hip,
 // label_reduce_kernels.h (the span form of the raveled walker);
 // label_filter.hip takes the row-chunk layout and its launch geometry and keeps its own loop (see there); bin_kernels.h
 // and subseg.hip take the loads and the alignment predicate only.  The same text compiles

@@ -13,7 +13,11 @@ array's `flag_values` and `name` are keyword arguments because there is no DataA
 
 The third stage is at the end of the module: process_core_properties, process_thick_anvil_properties,
 process_thin_anvil_properties and add_validity_flags (postprocess.py:313-1314) over the step records of a LabelDataset
-table, as batches of tf_group_reduce operations.  `add_cre_to_dataset` of the reference's module is out of scope."""
+table, as batches of tf_group_reduce operations.
+
+The fifth stage stands between the two: get_cre and add_cre_to_dataset (postprocess.py:29-99), cloud_quality_weights and
+the scripts' cloud and flux sections as add_weighted_stats_of_fields, add_cloud_properties and add_flux_properties, which
+evaluate a whole set of variables in one walk of a label volume (tf_label_wstats_multi)."""
 from functools import partial
 
 import numpy as np
@@ -272,6 +276,294 @@ def add_weighted_proportions_to_dataset(dcc_dataset, flag_da, weights, dim, dim_
     dcc_dataset.coords[name] = np.asarray(list(flag_values))
     dcc_dataset.add(f"{dim_name}_{name}_proportion", proportions, (dim, name))
     return dcc_dataset
+
+
+# ---- the fifth stage: cloud and flux properties per object (reference: postprocess.py:29-99 and the scripts) ---------------
+# scripts/postprocess_seviri_nat_dcc.py:180-298 (the same text in postprocess_seviri_dcc.py:79-165 and
+# relabel_postprocess_seviri_cci.py:210-330): the quality weights, eleven cloud variables and five flags, add_cre_to_dataset
+# and twenty flux variables, each over the three step-label volumes.  The reference makes ~100 calls of
+# add_weighted_stats_to_dataset; here the variables of a call group share the two reads of a label volume
+# (tf_label_wstats_multi) and the derived fluxes of the TOA / BOA sets are formed in registers.
+STEP_DIMS = ("core_step", "thick_anvil_step", "thin_anvil_step")
+CLOUD_VARIABLES = ("cot", "cer", "cwp", "ctp", "ctp_corrected", "cth", "cth_corrected", "ctt", "ctt_corrected", "stemp", "dem")
+CLOUD_FLAGS = ("lsflag", "lusflag", "illum", "cldtype", "phase")
+FLUX_VARIABLES = ("toa_swdn", "toa_swup", "toa_swup_cre", "toa_lwup", "toa_lwup_cre", "toa_net", "toa_net_cre",
+                  "boa_swdn", "boa_swdn_cre", "boa_swup", "boa_swup_cre", "boa_lwdn", "boa_lwdn_cre", "boa_lwup", "boa_lwup_cre",
+                  "boa_net", "boa_net_cre", "lts", "fth", "cbh")
+CRE_NAMES = ("toa_swup_cre", "toa_lwup_cre", "boa_swdn_cre", "boa_swup_cre", "boa_lwdn_cre", "boa_lwup_cre",
+             "toa_net", "toa_net_cre", "boa_net", "boa_net_cre")
+# the field sets of tf_label_wstats_multi: input planes and fields in the kernel's order (include/tobac_flow_hip.h)
+_SET_PLANES = {"TOA": ("toa_swdn", "toa_swup", "toa_swup_clr", "toa_lwup", "toa_lwup_clr"),
+               "BOA": ("boa_swdn", "boa_swup", "boa_lwdn", "boa_lwup", "boa_swdn_clr", "boa_swup_clr", "boa_lwdn_clr", "boa_lwup_clr")}
+_SET_FIELDS = {"TOA": FLUX_VARIABLES[:7], "BOA": FLUX_VARIABLES[7:17]}
+_CRE_PLANES = _SET_PLANES["TOA"] + _SET_PLANES["BOA"]
+# where a derived variable takes its dims from
+_CRE_LIKE = dict([(name, name[:-4]) for name in CRE_NAMES[:6]] + [("toa_net", "toa_swdn"), ("toa_net_cre", "toa_swup"),
+                                                                   ("boa_net", "boa_swdn"), ("boa_net_cre", "boa_swdn")])
+MAX_FUSED_FIELDS = 8
+
+
+def get_cre(flux, clear_flux):
+    """The cloud radiative effect of a flux: `flux - clear_flux` (reference: postprocess.py:29-36, whose attrs and name
+    are not carried here).  NumPy arrays or device tensors, one IEEE subtraction per element in the operands' type."""
+    return flux - clear_flux
+
+
+# the ten variables of add_cre_to_dataset in its order, each in the reference's expression tree over g(name) (the tree is
+# what fixes the rounding); the operands are NumPy arrays or tensors
+_CRE_TREES = {f"{v}_cre": (lambda g, v=v: get_cre(g(v), g(f"{v}_clr"))) for v in [name[:-4] for name in CRE_NAMES[:6]]}
+_CRE_TREES.update({
+    "toa_net": lambda g: g("toa_swdn") - (g("toa_swup") + g("toa_lwup")),
+    "toa_net_cre": lambda g: -(g("toa_swup_cre") + g("toa_lwup_cre")),
+    "boa_net": lambda g: g("boa_swdn") + g("boa_lwdn") - (g("boa_swup") + g("boa_lwup")),
+    "boa_net_cre": lambda g: g("boa_swdn_cre") + g("boa_lwdn_cre") - (g("boa_swup_cre") + g("boa_lwup_cre"))})
+
+
+def _cre_value(name, raw, memo):
+    """the derived variable `name` from the raw variables `raw(name)`; the derived ones it is made of are kept in `memo`"""
+    if name not in _CRE_TREES:
+        return raw(name)
+    if name not in memo:
+        with np.errstate(invalid="ignore", over="ignore"):
+            memo[name] = _CRE_TREES[name](lambda other: _cre_value(other, raw, memo))
+    return memo[name]
+
+
+def _float_dtype(arrays):
+    """np.float32 / np.float64 where every array has that one dtype, else None"""
+    dtypes = {_np_dtype(a) for a in arrays}
+    dtype = dtypes.pop()
+    return dtype if not dtypes and dtype in (np.float32, np.float64) else None
+
+
+def _tf_dtype(dtype):
+    return _lib().TF_F32 if np.dtype(dtype) == np.float32 else _lib().TF_F64
+
+
+def _pointers(tensors):
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[None if x is None else x.data_ptr() for x in tensors])
+
+
+def add_cre_to_dataset(dataset):
+    """Adds toa_swup_cre, toa_lwup_cre, boa_swdn_cre, boa_swup_cre, boa_lwdn_cre, boa_lwup_cre (flux - clear-sky flux),
+    toa_net, toa_net_cre, boa_net and boa_net_cre to `dataset`, a LabelDataset or any mutable mapping name -> array, in that
+    order, from its thirteen raw flux variables (reference: postprocess.py:39-99; no attrs here).  Returns `dataset`.
+
+    Every expression is evaluated in the reference's tree with each operation rounded in the variables' own type
+    (toa_net = swdn - (swup + lwup), boa_net = swdn + lwdn - (swup + lwup), ...): additions, subtractions and a negation, so
+    the values are NumPy's.  NumPy arrays are evaluated by NumPy; where the variables are float32 or float64 device tensors
+    of one shape, ONE kernel launch (tf_flux_cre) reads the thirteen planes once and writes the ten results.  The inputs
+    are not modified.  In a LabelDataset each result takes the dims of its first source variable."""
+    raw = [dataset[name] for name in _CRE_PLANES]                 # KeyError names what is missing
+    if any(_is_tensor(x) for x in raw):
+        lib = _lib()
+        dtype = _float_dtype(raw)
+        if dtype is None or len({_shape(x) for x in raw}) != 1:
+            raise ValueError("add_cre_to_dataset: on the device the thirteen flux variables are float32 or float64 tensors of "
+                             "one dtype and one shape")
+        planes = [lib.to_dev(x) for x in raw]
+        n = planes[0].numel()
+        outs = [lib.empty(tuple(planes[0].shape), planes[0].dtype) for _ in CRE_NAMES]
+        if n:
+            lib.check(lib.lib().tf_flux_cre(_pointers(planes), _pointers(outs), _tf_dtype(dtype), n, lib.stream_ptr()), "tf_flux_cre")
+        values = dict(zip(CRE_NAMES, outs))
+    else:
+        values = {}
+        for name in CRE_NAMES:
+            _cre_value(name, lambda raw: np.asarray(dataset[raw]), values)
+    dims =getattr(dataset, "dims", None)
+    for name in CRE_NAMES:
+        if hasattr(dataset, "add") and isinstance(dims, dict) and _CRE_LIKE[name] in dims:
+            dataset.add(name, values[name], dims[_CRE_LIKE[name]])
+        else:
+            dataset[name] = values[name]
+    return dataset
+
+
+def cloud_quality_weights(weights, qcflag, cth, cot):
+    """`weights * (qcflag == 0) * (cth < 30) * isfinite(cot)` with the three masks as float32: the weights the scripts use
+    for the cloud properties (postprocess_seviri_nat_dcc.py:181-186).  `weights` is (T, H, W), (H, W) or (1, H, W), the
+    others (T, H, W); the result is (T, H, W), float32 if `weights` is float32 and float64 otherwise.  The three
+    multiplications are made as written: a NaN or infinite weight times 0 is NaN, a NaN `cth` compares false.  NumPy
+    arrays are evaluated by NumPy; with a device tensor among the operands one kernel (tf_quality_weights) reads the
+    weights as the plane or volume they are."""
+    operands = (weights, qcflag, cth, cot)
+    shape = _shape(cth)
+    if len(shape) != 3 or _shape(qcflag) != shape or _shape(cot) != shape:
+        raise ValueError(f"cloud_quality_weights: qcflag {_shape(qcflag)}, cth {shape} and cot {_shape(cot)} are (T, H, W) arrays of one shape")
+    layout = "volume" if _shape(weights) == shape else "plane" if _shape(weights) in (shape[1:], (1,) + shape[1:]) else None
+    if layout is None:
+        raise ValueError(f"cloud_quality_weights: weights {_shape(weights)} are neither {shape} nor {shape[1:]}")
+    single = _np_dtype(weights) == np.float32
+    if not any(_is_tensor(x) for x in operands):
+        w = np.asarray(weights)
+        w = w if single else w.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            out = w * (np.asarray(qcflag) == 0).astype(np.float32) * (np.asarray(cth) < 30).astype(np.float32) \
+                * np.isfinite(cot).astype(np.float32)
+        return np.ascontiguousarray(np.broadcast_to(out, shape))
+    lib = _lib()
+    t = lib.torch()
+    w = lib.to_dev(weights, t.float32 if single else t.float64)
+    qd = _np_dtype(qcflag)
+    if qd.kind in "iub" and (qd.itemsize < 4 or qd == np.int32):
+        q = lib.to_dev(qcflag, t.int32)
+    else:                                                         # a width int32 does not hold, or a float flag: 0 stays the only 0
+        q = lib.to_dev(qcflag)
+        q = (q != 0).to(t.int32)
+    both32 = _np_dtype(cth) == np.float32 and _np_dtype(cot) == np.float32
+    work = t.float32 if both32 else t.float64                     # widening is exact: the comparison and the test are unchanged
+    h, c = lib.to_dev(cth, work), lib.to_dev(cot, work)
+    out = lib.empty(shape, w.dtype)
+    if out.numel():
+        lib.check(lib.lib().tf_quality_weights(lib.ptr(w), lib.TF_F32 if single else lib.TF_F64, int(layout == "plane"), lib.ptr(q),
+                                               lib.ptr(h), lib.ptr(c), lib.TF_F32 if both32 else lib.TF_F64, shape[0],
+                                               shape[1] * shape[2], lib.ptr(out), lib.stream_ptr()), "tf_quality_weights")
+    return out
+
+
+def _wstats_multi(lab, n_labels, set_name, planes, errors, w, plane):
+    """tf_label_wstats_multi: (fields of the set, n_labels, 10) float64 on the host.  planes / errors / w: device tensors,
+    the planes (and errors) of one float dtype, errors a list with None entries or None"""
+    lib = _lib()
+    t, L = lib.torch(), lib.lib()
+    set_id = {"PLAIN": lib.TF_FIELDS_PLAIN, "TOA": lib.TF_FIELDS_TOA, "BOA": lib.TF_FIELDS_BOA}[set_name]
+    n_fields = len(planes) if set_name == "PLAIN" else len(_SET_FIELDS[set_name])
+    T, hw = lab.shape[0], lab.shape[1] * lab.shape[2]
+    out = lib.empty((n_fields, n_labels, 10), t.float64)
+    ws = lib.workspace(L.tf_label_wstats_multi_workspace_bytes(set_id, len(planes), n_labels), "label_wstats_multi")
+    e = None if errors is None or all(x is None for x in errors) else _pointers(errors)
+    lib.check(L.tf_label_wstats_multi(lib.ptr(lab), set_id, _pointers(planes), e, len(planes), lib.ptr(w),
+                                      _tf_dtype(_np_dtype(planes[0])), _tf_dtype(_np_dtype(w)), T, hw, int(plane), n_labels,
+                                      lib.ptr(out), lib.ptr(ws), ws.numel(), lib.stream_ptr()), "tf_label_wstats_multi")
+    return out.cpu().numpy()
+
+
+def _stats_stage(dcc_dataset, source, weights, variables, dims, sets):
+    """The loop `for var in variables: for dim in dims: add_weighted_stats_to_dataset(dcc_dataset, source, weights, var,
+    dim)` with the variables of a dim evaluated together.  `sets`: the names of the field sets ("TOA", "BOA") whose
+    variables are evaluated from the RAW planes of `source`; a variable of no set is `source[var]`."""
+    variables, dims = list(variables), list(dims)
+    set_of = {var: s for s in sets for var in _SET_FIELDS[s]}
+    plans, memo = [], {}
+
+    for var in variables:
+        errors = source[f"{var}_uncertainty"] if f"{var}_uncertainty" in source else None
+        s = set_of.get(var)
+        if s is not None:
+            for name in _SET_PLANES[s]:
+                if name not in source:
+                    raise KeyError(name)
+            planes = [source[name] for name in _SET_PLANES[s]]
+            if errors is None and _float_dtype(planes) is not None and len({_shape(x) for x in planes}) == 1:
+                plans.append((var, s, planes[0], None))
+            else:                                                 # non-float planes, or errors: the variable itself, one call
+                plans.append((var, None, _cre_value(var, source.__getitem__, memo), errors))
+        else:
+            plans.append((var, None, source[var], errors))        # KeyError names what is missing
+    device = {}
+
+    def dev(x, dtype=None):                                       # every operand goes to the device once for all dims
+        key = (id(x), dtype)
+        if key not in device:
+            device[key] = (x, _lib().to_dev(x, dtype))            # x is kept: its id cannot be given to another array meanwhile
+        return device[key][1]
+
+    results = {}
+    for dim in dims:
+        labels, ids = dcc_dataset[f"{dim}_label"], _check_index(dcc_dataset.coords[dim])
+        fused = {"TOA": [], "BOA": [], np.dtype(np.float32): [], np.dtype(np.float64): []}
+        for var, s, field, errors in plans:
+            operands = (field,) if errors is None else (field, errors)
+            layout = _layout(labels, weights, *operands)          # ValueError where the shapes do not broadcast
+            takes = layout is not None and _np_dtype(labels).kind in "iu" and _np_dtype(weights).kind in "fiub"
+            if takes and s is not None:
+                fused[s].append(var)
+            elif takes and _float_dtype(operands) is not None:
+                fused[_np_dtype(field)].append((var, field, errors))
+            else:                                                 # the per-variable call of the loop (a set's variable as an array)
+                field = field if s is None else _cre_value(var, source.__getitem__, memo)
+                results[var, dim] = _label_wstats(labels, field, errors, weights, ids)
+        if not any(fused.values()):
+            continue
+        lab, n_labels = _device_labels(labels, ids)
+        if n_labels > 0:
+            plane = _layout(labels, weights) == "plane"
+            w = dev(weights, None if _np_dtype(weights) in (np.float32, np.float64) else _lib().torch().float64)
+        for s in ("TOA", "BOA"):
+            if not fused[s]:
+                continue
+            if n_labels > 0:
+                records = _wstats_multi(lab, n_labels, s, [dev(source[name]) for name in _SET_PLANES[s]], None, w, plane)
+            for var in fused[s]:                                  # the set's other fields are computed and dropped
+                k = _SET_FIELDS[s].index(var)
+                results[var, dim] = _scatter(records[k][:, 2:6], ids, n_labels, 4) if n_labels > 0 else np.full((len(ids), 4), np.nan)
+        for dtype in (np.dtype(np.float32), np.dtype(np.float64)):
+            group = fused[dtype]
+            for start in range(0, len(group), MAX_FUSED_FIELDS):
+                part = group[start:start + MAX_FUSED_FIELDS]
+                if n_labels > 0:
+                    records = _wstats_multi(lab, n_labels, "PLAIN", [dev(f) for _, f, _ in part],
+                                            [None if e is None else dev(e) for _, _, e in part], w, plane)
+                for k, (var, _, errors) in enumerate(part):
+                    n_out = 4 if errors is None else 8
+                    results[var, dim] = (_scatter(records[k][:, 2:2 + n_out], ids, n_labels, n_out) if n_labels > 0
+                                         else np.full((len(ids), n_out), np.nan))
+    kinds = {var: _np_dtype(field) for var, _, field, _ in plans}
+    for var in variables:
+        dtype = kinds[var] if kinds[var].kind == "f" else np.float64
+        for dim in dims:
+            stats = results[var, dim]
+            for k, stat in enumerate(STAT_NAMES[:stats.shape[1]]):
+                dcc_dataset.add(f"{dim}_{var}_{stat}", stats[:, k].astype(dtype), (dim,))
+    return dcc_dataset
+
+
+def add_weighted_stats_of_fields(dcc_dataset, field_dataset, weights, variables, dims=STEP_DIMS):
+    """The result of
+
+        for var in variables:
+            for dim in dims:
+                add_weighted_stats_to_dataset(dcc_dataset, field_dataset, weights, var, dim)
+
+    -- the same names f"{dim}_{var}_{stat}" in the same order of insertion with the same dims and dtypes, eight per
+    variable where `field_dataset` holds f"{var}_uncertainty" and four otherwise, KeyError for a missing variable,
+    ValueError for an id < 1 or shapes that do not broadcast -- evaluated with one tf_label_wstats_multi per dim and group
+    of at most eight variables of one float dtype: a label volume is read twice per group instead of twice per variable,
+    float32 fields meet float64 weights without a copy of either, and host arrays are uploaded once for all dims.
+    The exact results (min, max, the errors at them, the NaN pattern) are those of the loop; the summed ones agree to
+    the last bits of a double sum whose order of addition is not fixed.  A variable the fused kernel does not take -- a
+    non-float dtype, errors of another dtype than the field's, operands that merely broadcast -- goes through the
+    per-variable call of the loop; the order of the results does not depend on that.  All variables are looked up
+    before the first result is added.  Returns `dcc_dataset`."""
+    return _stats_stage(dcc_dataset, field_dataset, weights, variables, dims, ())
+
+
+def add_cloud_properties(dataset, cld_ds, weights, variables=CLOUD_VARIABLES, *, flags, dims=STEP_DIMS):
+    """The cloud section of the post-processing scripts (postprocess_seviri_nat_dcc.py:190-215): the weighted statistics of
+    `variables` (default: the scripts' eleven) through add_weighted_stats_of_fields, then for every flag of `flags` and
+    every dim add_weighted_proportions_to_dataset, in the mapping's order.  `flags` maps a flag variable of `cld_ds` to its
+    `flag_values` (the scripts' five are CLOUD_FLAGS; the values are an attribute of the DataArray there and have to be
+    given here).  `weights` are usually cloud_quality_weights(...).  Returns `dataset`."""
+    add_weighted_stats_of_fields(dataset, cld_ds, weights, variables, dims)
+    for name, flag_values in flags.items():
+        for dim in dims:
+            add_weighted_proportions_to_dataset(dataset, cld_ds[name], weights, dim, flag_values=flag_values, name=name)
+    return dataset
+
+
+def add_flux_properties(dataset, flx_ds, weights, variables=FLUX_VARIABLES, dims=STEP_DIMS):
+    """The flux section of the post-processing scripts (postprocess_seviri_nat_dcc.py:271-298): the result of
+    add_cre_to_dataset(flx_ds) followed by add_weighted_stats_of_fields(dataset, flx_ds, weights, variables, dims), with
+    `variables` defaulting to the scripts' twenty -- but `flx_ds` is NOT modified and the ten derived volumes never exist:
+    the variables of the TOA set (toa_swdn .. toa_net_cre) and of the BOA set (boa_swdn .. boa_net_cre) are evaluated from
+    the RAW planes of `flx_ds` by tf_label_wstats_multi, which forms the derived values per voxel with add_cre_to_dataset's
+    own expressions, whether or not `flx_ds` already holds the derived names (the same bits either way).  A set is
+    launched when one of its variables is requested; its other fields are computed and dropped.  The remaining variables
+    (lts, fth, cbh, ...) are grouped as in add_weighted_stats_of_fields.  A raw plane that a requested variable needs and
+    `flx_ds` lacks is a KeyError naming it.  Returns `dataset`."""
+    return _stats_stage(dataset, flx_ds, weights, variables, dims, ("TOA", "BOA"))
 
 
 # ---- the third stage: object properties from step records (reference: postprocess.py:313-1314) ---------------------------
@@ -535,5 +827,6 @@ def add_validity_flags(dataset):
 
 
 __all__ = ("weighted_label_stats", "add_weighted_stats_to_dataset", "get_weighted_proportions_da",
-           "add_weighted_proportions_to_dataset", "process_core_properties", "process_thick_anvil_properties",
+           "add_weighted_proportions_to_dataset", "get_cre", "add_cre_to_dataset", "cloud_quality_weights",
+           "add_weighted_stats_of_fields", "add_cloud_properties", "add_flux_properties", "process_core_properties", "process_thick_anvil_properties",
            "process_thin_anvil_properties", "add_validity_flags")
